@@ -8,6 +8,7 @@
     python bench.py --gpus 2 --dry-run                     (no GPU: ranks, shards and the gather shapes rehearsed over gloo)
     python bench.py --config 4 --gpus 8                    (BASELINE config 4: 65536 instances = 8192 per GPU)
     python bench.py --gpus N --gather every-step           (an all-gather behind EVERY cycle instead of one behind the last)
+    python bench.py --gpus 1 --steps K --dump-outputs DIR  (also writes the torques and status of the last timed cycle: DIR/tau.npy, DIR/status.npy)
 
 One "step" = one control cycle (updateModel + updateControllerTaskModels + computeControlTorques) of every instance of
 the rank's batch = one launch of the cycle kernel, inputs already resident in HBM.  Weak scaling: every rank owns
@@ -223,6 +224,31 @@ def _spawn_ranks(n: int, timeout_s: float) -> int:
     return max([abs(c) for c in codes if c != 0] + [1])
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write {name: array} as out_dir/<name>.npy, floating arrays as float64, the rest (status bytes) as float32.  Every array
+    has one row per instance; when the whole set would exceed `limit` bytes, the same fixed, seeded sample of rows is written for every array,
+    sorted, and its row indices go to out_dir/rows.npy."""
+    import numpy as np
+    arrays = {k: np.asarray(v, np.float64 if np.issubdtype(np.asarray(v).dtype, np.floating) else np.float32) for k, v in arrays.items()}
+    rows = {a.shape[0] for a in arrays.values()}
+    if len(rows) != 1:
+        raise ValueError(f"--dump-outputs: arrays differ in their number of instances: { {k: a.shape for k, a in arrays.items()} }")
+    nrows = rows.pop()
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    if total + 4096 > limit:
+        keep = max(1, int((limit - 4096) // (total / nrows + 8)))   # (+ 8 bytes per kept row for its index in rows.npy, 4 KB for the headers)
+        idx = np.sort(np.random.default_rng(0).choice(nrows, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["rows"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def _metric(n, ntasks, B):
     return f"control-cycles/sec (whole node), {n}-DoF {ntasks}-task hierarchy, batch={B}"
 
@@ -333,6 +359,8 @@ def run_multi(args):
     elapsed = time.perf_counter() - t0
     ngather = (args.steps if every else 1) if world > 1 else 0
     taus = [c.getTorques() for c in mc.controllers]
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, {"tau": np.concatenate(taus), "status": np.concatenate([c.status for c in mc.controllers])})
     ok = all(bool(np.isfinite(t).all()) for t in taus) and all(int((c.status & 1).sum()) == 0 for c in mc.controllers)
     if world > 1:
         for i in range(world):
@@ -398,9 +426,14 @@ def main():
     ap.add_argument("--spawn-timeout", type=float, default=1800.0, help="seconds the self-started ranks get before they are ended")
     ap.add_argument("--traffic", type=float, default=None, help="measured HBM bytes per launch (from a separate rocprofv3 --pmc pass); "
                     "default: the committed PMC summary profiles/pmc_traffic.json when it matches kernel/config/batch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed for every instance as DIR/<name>.npy: tau "
+                         "[global batch][dof] float64, status [global batch] float32 (a fixed, seeded sample of instances above 64 MB)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.dump_outputs is not None and args.dry_run:
+        raise SystemExit("--dump-outputs needs a real run: a dry run computes no torques")
     if args.launcher == "multi":
         if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != 1:
             raise SystemExit("--launcher multi is ONE process for all GPUs: do not start it under a multi-rank launcher")
@@ -544,6 +577,16 @@ def main():
 
     # correctness of what was timed: finite torques, no flagged instance, gather holds this rank's slab
     tau = ctrl.getTorques()
+    if args.dump_outputs is not None:
+        # what a caller receives from the last timed step: the gathered torques of every rank (its own slab on one rank) and every
+        # instance's status, collected from the ranks here, outside the timed region
+        statuses = [ctrl.status.copy()]
+        if world > 1:
+            statuses = [None] * world
+            dist.all_gather_object(statuses, ctrl.status.copy())
+        if rank == 0:
+            tau_all = tau if world == 1 else gathered[:, :, :B].permute(0, 2, 1).reshape(world * B, n).cpu().numpy()
+            dump_outputs(args.dump_outputs, {"tau": tau_all, "status": np.concatenate(statuses)})
     ok = bool(np.isfinite(tau).all() and (ctrl.status & 1).sum() == 0)  # bit 0 = flagged (torques held or NaN by policy); bits 1..3 are informational (truncated / POPC window / blended)
     ok = ok and bool(torch.equal(gathered[rank], tau_t))
     # cross-check of the timed kernel against the engine's other, independently written kernel (general workgroup-per-instance

@@ -12,6 +12,7 @@ import numpy as np
 
 _DIR = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(_DIR, "_ref", "libsaip_otg_ref.so")
+COMPARE = os.path.join(_DIR, "_ref", "otg3_compare")
 REFERENCE_TREE = "/root/reference/ruckig/include"
 _LIB = None
 
@@ -19,8 +20,10 @@ _LIB = None
 def build() -> str | None:
     """(re)build from the reference tree when it is present; otherwise keep whatever prebuilt file is there"""
     if os.path.isdir(REFERENCE_TREE):
-        src = os.path.join(_DIR, "ref_ruckig", "otg_ref_shim.cpp")
-        if not os.path.exists(SO) or os.path.getmtime(SO) < os.path.getmtime(src):
+        stale = False
+        for out, src in ((SO, "otg_ref_shim.cpp"), (COMPARE, "otg3_compare.cpp")):
+            stale = stale or not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(os.path.join(_DIR, "ref_ruckig", src))
+        if stale:
             subprocess.check_call(["make", "-C", _DIR, "-B", "ref"], stdout=subprocess.DEVNULL)
     return SO if os.path.exists(SO) else None
 

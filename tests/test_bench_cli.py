@@ -78,6 +78,28 @@ def test_single_process_launcher():
     assert r.returncode != 0 and r.stdout.strip() == "" and "ONE process" in r.stderr
 
 
+def test_dump_outputs_writes_float_arrays_and_samples_rows_above_the_limit(tmp_path):
+    """--dump-outputs' writer: float64 torques and float32 status as given; above the size limit the same seeded, sorted rows of every array
+    and their indices in rows.npy, identical from call to call"""
+    import numpy as np
+    import bench
+    tau = np.arange(1000 * 7, dtype=np.float64).reshape(1000, 7)
+    st = (np.arange(1000) % 3).astype(np.uint8)
+    assert bench.dump_outputs(str(tmp_path / "all"), {"tau": tau, "status": st}) == ["status", "tau"]
+    t, s = np.load(tmp_path / "all" / "tau.npy"), np.load(tmp_path / "all" / "status.npy")
+    assert t.dtype == np.float64 and s.dtype == np.float32 and np.array_equal(t, tau) and np.array_equal(s, st)
+    limit = 4096 + 100 * (7 * 8 + 4 + 8)
+    for d in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / d), {"tau": tau, "status": st}, limit=limit) == ["rows", "status", "tau"]
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    assert rows.size == 100 and np.all(np.diff(rows) > 0) and np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+    idx = rows.astype(int)
+    assert np.array_equal(np.load(tmp_path / "a" / "tau.npy"), tau[idx]) and np.array_equal(np.load(tmp_path / "a" / "status.npy"), st[idx])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= limit
+    r = _bench("--gpus", "2", "--dry-run", "--dump-outputs", str(tmp_path / "dry"))
+    assert r.returncode != 0 and r.stdout.strip() == "" and not os.path.exists(tmp_path / "dry")
+
+
 def test_a_rank_that_leaves_early_ends_the_run():
     """the self-started ranks are polled: when one exits non-zero before the rendezvous the others are ended, no line is printed and the
     launcher returns non-zero promptly (it used to wait for rank 0 for ever)"""

@@ -45,6 +45,30 @@ def test_every_step_gather_mode_on_one_rank_and_the_oracle_error_in_the_line():
     assert d5["roofline"]["bound"] == "mfma" and d5["config"]["kernel"] == "saip_cycle_wave"
 
 
+def test_dump_outputs_are_the_timed_torques_and_repeat_exactly(tmp_path):
+    """--dump-outputs: the torques and status of the last timed cycle, [4096][7] float64 and [4096] float32, identical from run to run and
+    between the two launchers, equal to what the facade computes on the same seeded inputs"""
+    from sai_primitives_amd.controller import controller_from_specs
+    dumps = []
+    for name, extra in (("a", ()), ("b", ()), ("multi", ("--launcher", "multi"))):
+        d = _bench("--steps", "7", "--warmup", "2", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / name), *extra)
+        assert d["valid"] is True and d["steps"] == 7
+        assert sorted(os.listdir(tmp_path / name)) == ["status.npy", "tau.npy"]
+        dumps.append((np.load(tmp_path / name / "tau.npy"), np.load(tmp_path / name / "status.npy")))
+    tau, st = dumps[0]
+    assert tau.dtype == np.float64 and tau.shape == (4096, 7) and st.dtype == np.float32 and st.shape == (4096,)
+    for t, s in dumps[1:]:
+        assert np.array_equal(t, tau) and np.array_equal(s, st)
+    inp = W.make_inputs(2, 4096)
+    robot, ctrl, _ = controller_from_specs(inp["model"].name, inp["tasks"], 4096, device=0)
+    robot.setQ(inp["q"])
+    robot.setDq(inp["dq"])
+    robot.updateModel()
+    ctrl.updateControllerTaskModels()
+    ctrl.setGoals(inp["goals"])
+    assert W.torque_error(tau, ctrl.computeControlTorques()) < 1e-12 and np.array_equal(st, ctrl.status.astype(np.float32))
+
+
 def test_time_steps_entry_points_agree():
     import ctypes as C
     from sai_primitives_amd import capi

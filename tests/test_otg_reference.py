@@ -28,7 +28,7 @@ def test_fixture_set_is_complete():
 @pytest.mark.parametrize("path", CART, ids=CIDS)
 def test_cartesian_fixtures_are_reference_outputs(path):
     if otg_ref.build() is None:
-        pytest.skip("oracle/_ref/libsaip_otg_ref.so not present (built only where /root/reference exists)")
+        pytest.skip("oracle/_ref/libsaip_otg_ref.so not present (built only where the reference tree is present)")
     sc, steps, desired, reached, meta = G.load_cart(path)
     s2, d2, r2, moving = G.run_reference_cart(sc)
     assert np.array_equal(s2, steps) and np.array_equal(r2, reached) and moving == meta["finished_with_velocity"]
@@ -59,7 +59,7 @@ def test_cartesian_trajectory_invariants(path):
 @pytest.mark.parametrize("path", FIX, ids=IDS)
 def test_fixtures_are_reference_outputs(path):
     if otg_ref.build() is None:
-        pytest.skip("oracle/_ref/libsaip_otg_ref.so not present (built only where /root/reference exists)")
+        pytest.skip("oracle/_ref/libsaip_otg_ref.so not present (built only where the reference tree is present)")
     sc, steps, desired, reached, meta = G.load(path)
     s2, d2, r2, moving = G.run_reference(sc)
     assert np.array_equal(s2, steps) and np.array_equal(r2, reached) and moving == meta["finished_with_velocity"]
@@ -144,7 +144,42 @@ def test_jerk_limited_core_matches_the_reference_classes():
     import subprocess
     exe = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "otg3_compare")
     if otg_ref.build() is None or not os.path.exists(exe):
-        pytest.skip("oracle/_ref/otg3_compare not present (built only where /root/reference exists)")
+        pytest.skip("oracle/_ref/otg3_compare not present (built only where the reference tree is present)")
     r = subprocess.run([exe, "60000"], capture_output=True, text=True, timeout=300)
     print(r.stdout[-400:])
     assert r.returncode == 0 and "mismatches 0" in r.stdout
+    # the stored vectors the next test runs on are what the reference answers today
+    import make_otg3_golden as G3
+    raw = subprocess.run([exe, "--record", str(G3.N_CASES)], capture_output=True, check=True, timeout=300).stdout
+    z = np.load(G3.PATH)
+    a = np.frombuffer(raw, np.float64).reshape(G3.N_CASES, G3.CASE + G3.RECORD)
+    assert np.array_equal(a[:, :G3.CASE], z["cases"], equal_nan=True) and np.array_equal(a[:, G3.CASE:], z["records"], equal_nan=True)
+
+
+# record entries that are decisions / enums (exact), the rest are numbers (relative 1e-9, like otg3_compare): step 1 found, has_a, has_b,
+# direction, control signs; per step 2 found, control signs, limits
+_DISCRETE = [4, 6, 7, 48, 49] + [50 + 41 * k + i for k in range(3) for i in (0, 39, 40)]
+
+
+def test_jerk_limited_core_matches_stored_reference_vectors(tmp_path):
+    """function level, without the reference: the product's third-order solver (csrc/saip_otg3.h compiled for the host by
+    tests/cpp/otg3_vectors.cpp) on the 800 stored cases of tests/golden/otg3_core_vectors.npz (brake pre-trajectory, step 1, step 2 at up to
+    three durations), against the answers the reference's Ruckig classes gave on them"""
+    import subprocess
+    import make_otg3_golden as G3
+    root = os.path.dirname(HERE)
+    exe = str(tmp_path / "otg3_vectors")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(root, "sai-primitives_amd", "csrc"), "-o", exe,
+                           os.path.join(HERE, "cpp", "otg3_vectors.cpp")])
+    z = np.load(G3.PATH)
+    cases, want = z["cases"], z["records"]
+    assert cases.shape == (G3.N_CASES, G3.CASE) and want.shape == (G3.N_CASES, G3.RECORD)
+    assert np.nansum(want[:, 4]) > 0.9 * G3.N_CASES and np.nansum(want[:, [50, 91, 132]]) > G3.N_CASES and (want[:, 0] > 0).sum() > 50
+    out = subprocess.run([exe], input=np.ascontiguousarray(cases).tobytes(), capture_output=True, check=True, timeout=120).stdout
+    got = np.frombuffer(out, np.float64).reshape(want.shape)
+    assert np.array_equal(np.isnan(got), np.isnan(want))          # same profiles found, same intervals, same step-2 outcomes
+    assert np.array_equal(got[:, _DISCRETE], want[:, _DISCRETE], equal_nan=True)
+    fin = ~np.isnan(want)
+    rel = np.abs(got[fin] - want[fin]) / np.maximum(1.0, np.abs(want[fin]))
+    print("stored reference vectors: worst relative deviation", rel.max())
+    assert rel.max() <= 1e-9
