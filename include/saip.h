@@ -282,6 +282,21 @@ saip_status saip_batch_reinitialize_tasks(saip_batch*);
 /* MotionForceTask::getCurrentPosition / getCurrentOrientation (MotionForceTask.h:121-138) at the state last set: pos [3][B], rot [9][B]
  * (row-major per instance); either pointer may be NULL */
 saip_status saip_batch_get_current_pose_host(saip_batch*, int task, double* pos, double* rot);
+/* Task-space diagnostics of one motion-force task at the state last set (q, dq) -- 24 rows per instance:
+ *    0..2   getPositionError()     sigmaPosition (x_goal - x)                        (MotionForceTask.cpp:540-542)
+ *    3..5   getOrientationError()  sigmaOrientation orientationError(R_goal, R)      (:544-546, :291)
+ *    6..8   getCurrentLinearVelocity()   rows 0-2 of (P J_world) dq, P = partial-task projection (:293-298)
+ *    9..11  getCurrentAngularVelocity()  rows 3-5 of (P J_world) dq
+ *   12..14  getSensedForceControlWorldFrame()   from goal entries 30..32 (sensor frame; zero unless closed-loop force or moment
+ *   15..17  getSensedMomentControlWorldFrame()  control gives the goal block those entries) through the control-to-sensor transform (:805-828)
+ *   18..23  getUnitMassForce()     the control law's position / orientation term (MotionForceTask.h:266, .cpp:478), here DEFINED as the law
+ *           evaluated at the state last set, with the desired state of the last cycle (the OTG output, or the goal when the OTG is off) and
+ *           the integrators as they stand, advanced by one step on a copy.  With zero integral gains and no closed-loop force / moment
+ *           control this is what the last cycle used at that state.
+ * Nothing of the task's state is written (integrators, OTG, passivity observer, goal, status).  Motion-force tasks only.
+ * _host: out [24][B], synchronous.  _device: out_dev [24][ld] (device memory), asynchronous on the batch stream. */
+saip_status saip_batch_get_task_diagnostics_host(saip_batch*, int task, double* out);
+saip_status saip_batch_task_diagnostics_device(saip_batch*, int task, double* out_dev);
 /* TemplateTask::reInitializeTask of ONE task (MotionForceTask.cpp:204-245, JointTask.cpp:95-106) */
 saip_status saip_batch_reinitialize_task(saip_batch*, int task);
 /* MotionForceTask::resetIntegrators / resetIntegratorsLinear / resetIntegratorsAngular (MotionForceTask.cpp:988-1002; the linear part

@@ -303,6 +303,17 @@ protected:
 		check(saip_batch_task_compute_torques(_batch, _id, tau_prec, tau.data(), _status.data()));
 		return tau;
 	}
+	// rows first .. first + comps - 1 of the goal block (desired = false) or of the desired state, [comps][B]; rows the task's goal block
+	// does not have (goal force / moment of a task without force or moment space) read as zero, their value in the reference
+	std::vector<double> blockRows(bool desired, int first, int comps) {
+		need();
+		const size_t B = _robot->batchSize();
+		const int gc = saip_batch_goal_components(_batch, _id);
+		std::vector<double> g((size_t)gc * B);
+		check(desired ? saip_batch_get_desired_host(_batch, _id, g.data()) : saip_batch_get_goal_host(_batch, _id, g.data()));
+		if (first + comps > gc) return std::vector<double>((size_t)comps * B, 0.0);
+		return std::vector<double>(g.begin() + (size_t)first * B, g.begin() + (size_t)(first + comps) * B);
+	}
 	void setField(int first, int comps, const std::vector<double>& v, const char* what) {
 		need();
 		if (v.size() != (size_t)comps * _robot->batchSize()) throw std::invalid_argument(what);
@@ -424,6 +435,42 @@ public:
 		check(saip_batch_get_current_pose_host(_batch, _id, nullptr, r.data()));
 		return r;
 	}
+	// goal and desired state, [3][B] (orientations [9][B], row-major per instance): MotionForceTask.h getGoal* / getDesired*
+	std::vector<double> getGoalPosition() { return blockRows(false, 0, 3); }
+	std::vector<double> getGoalOrientation() { return blockRows(false, 3, 9); }
+	std::vector<double> getGoalLinearVelocity() { return blockRows(false, 12, 3); }
+	std::vector<double> getGoalAngularVelocity() { return blockRows(false, 15, 3); }
+	std::vector<double> getGoalLinearAcceleration() { return blockRows(false, 18, 3); }
+	std::vector<double> getGoalAngularAcceleration() { return blockRows(false, 21, 3); }
+	std::vector<double> getGoalForce() { return blockRows(false, 24, 3); }
+	std::vector<double> getGoalMoment() { return blockRows(false, 27, 3); }
+	std::vector<double> getDesiredPosition() { return blockRows(true, 0, 3); }
+	std::vector<double> getDesiredOrientation() { return blockRows(true, 3, 9); }
+	std::vector<double> getDesiredLinearVelocity() { return blockRows(true, 12, 3); }
+	std::vector<double> getDesiredAngularVelocity() { return blockRows(true, 15, 3); }
+	std::vector<double> getDesiredLinearAcceleration() { return blockRows(true, 18, 3); }
+	std::vector<double> getDesiredAngularAcceleration() { return blockRows(true, 21, 3); }
+	// task-space diagnostics at the robot's current state, one launch (saip_batch_get_task_diagnostics_host): [24][B], rows 0-2 position
+	// error, 3-5 orientation error, 6-8 / 9-11 current linear / angular velocity, 12-14 / 15-17 sensed force / moment (control point,
+	// world frame), 18-23 unit-mass force
+	std::vector<double> getTaskDiagnostics() {
+		need();
+		std::vector<double> d((size_t)24 * _robot->batchSize());
+		pushState();
+		check(saip_batch_get_task_diagnostics_host(_batch, _id, d.data()));
+		return d;
+	}
+	std::vector<double> getPositionError() { return diagRows(0, 3); }                   // MotionForceTask.cpp:540-542
+	std::vector<double> getOrientationError() { return diagRows(3, 3); }                // :544-546
+	std::vector<double> getCurrentLinearVelocity() { return diagRows(6, 3); }           // :293-295
+	std::vector<double> getCurrentAngularVelocity() { return diagRows(9, 3); }          // :296-298
+	std::vector<double> getSensedForceControlWorldFrame() { return diagRows(12, 3); }   // :805-828
+	std::vector<double> getSensedMomentControlWorldFrame() { return diagRows(15, 3); }
+	std::vector<double> getUnitMassForce() { return diagRows(18, 6); }                  // MotionForceTask.h:266 (see saip.h)
+	// MotionForceTask.cpp:548-579: sqrt(e^T sigma e) < tolerance per instance.  sigmaPosition / sigmaOrientation are symmetric projectors,
+	// so e^T sigma e = |sigma e|^2: the norm of the error rows
+	std::vector<bool> goalPositionReached(double tolerance) { return errorBelow(0, tolerance); }
+	std::vector<bool> goalOrientationReached(double tolerance) { return errorBelow(3, tolerance); }
 	void resetIntegratorsLinear() {
 		need();
 		check(saip_batch_reset_integrators(_batch, _id, 1));
@@ -447,6 +494,18 @@ public:
 	void setOriControlGainsUnsafe(double kp, double kv, double ki = 0) { setOriControlGains(kp, kv, ki); }
 
 protected:
+	std::vector<double> diagRows(int first, int comps) {
+		const std::vector<double> d = getTaskDiagnostics();
+		const size_t B = _robot->batchSize();
+		return std::vector<double>(d.begin() + (size_t)first * B, d.begin() + (size_t)(first + comps) * B);
+	}
+	std::vector<bool> errorBelow(int first, double tolerance) {
+		const std::vector<double> e = diagRows(first, 3);
+		const size_t B = _robot->batchSize();
+		std::vector<bool> r(B);
+		for (size_t b = 0; b < B; b++) r[b] = std::sqrt(e[b] * e[b] + e[B + b] * e[B + b] + e[2 * B + b] * e[2 * B + b]) < tolerance;
+		return r;
+	}
 	saip_status add(saip_batch* b, int* id) override {
 		return saip_batch_add_motion_force_task(b, _task_name.c_str(), _link.c_str(), _pos, nullptr, _dt.empty() ? nullptr : _dt.data(),
 												_partial ? (int)_dt.size() / 3 : -1, _dr.empty() ? nullptr : _dr.data(),
@@ -474,6 +533,13 @@ public:
 	void setGoalPosition(const std::vector<double>& q) { setField(0, getTaskDof(), q, "goal position vector size not consistent with task dof in JointTask::setGoalPosition\n"); }
 	void setGoalVelocity(const std::vector<double>& dq) { setField(getTaskDof(), getTaskDof(), dq, "goal velocity vector size not consistent with task dof in JointTask::setGoalVelocity\n"); }
 	void setGoalAcceleration(const std::vector<double>& ddq) { setField(2 * getTaskDof(), getTaskDof(), ddq, "goal acceleration vector size not consistent with task dof in JointTask::setGoalAcceleration\n"); }
+	// goal and desired state, [task dof][B] (JointTask.h getGoal* / getDesired*; desired = the OTG output when enabled, else the goal)
+	std::vector<double> getGoalPosition() { return blockRows(false, 0, getTaskDof()); }
+	std::vector<double> getGoalVelocity() { return blockRows(false, getTaskDof(), getTaskDof()); }
+	std::vector<double> getGoalAcceleration() { return blockRows(false, 2 * getTaskDof(), getTaskDof()); }
+	std::vector<double> getDesiredPosition() { return blockRows(true, 0, getTaskDof()); }
+	std::vector<double> getDesiredVelocity() { return blockRows(true, getTaskDof(), getTaskDof()); }
+	std::vector<double> getDesiredAcceleration() { return blockRows(true, 2 * getTaskDof(), getTaskDof()); }
 	void setGains(double kp, double kv, double ki = 0) { cfg([=](saip_batch* b, int id) { return saip_batch_set_joint_gains(b, id, &kp, &kv, &ki, 1); }); }
 	void setGainsUnsafe(double kp, double kv, double ki = 0) { setGains(kp, kv, ki); }
 	// rows x dof, row-major (identity for the full task), JointTask.h getJointSelectionMatrix

@@ -578,6 +578,63 @@ class MotionForceTask(_Task):
         """(B, 3, 3) compliant-frame orientation in the world frame, MotionForceTask.h:136"""
         return self._current_pose()[1]
 
+    # task-space diagnostics (one kernel launch for all seven quantities; C-ABI saip_batch_get_task_diagnostics_host)
+    _DIAG_ROWS = {"position_error": (0, 3), "orientation_error": (3, 6), "linear_velocity": (6, 9), "angular_velocity": (9, 12),
+                  "sensed_force": (12, 15), "sensed_moment": (15, 18), "unit_mass_force": (18, 24)}
+
+    def getTaskDiagnostics(self):
+        """dict of (B, 3) / (B, 6) arrays at the robot's current state: position_error, orientation_error, linear_velocity, angular_velocity,
+        sensed_force, sensed_moment (control point, world frame) and unit_mass_force -- what the getters below return, from one launch.
+        unit_mass_force is the control law evaluated at that state (see saip.h); no task state is changed."""
+        ctrl = self._need_ctrl()
+        ctrl._push_state()
+        out = np.empty((24, ctrl._robot.batch_size))
+        capi.check(capi.lib().saip_batch_get_task_diagnostics_host(ctrl._h, self._id, _dptr(out)))
+        return {k: out[a:b].T.copy() for k, (a, b) in self._DIAG_ROWS.items()}
+
+    def getTaskDiagnosticsDevice(self, out):
+        """asynchronous variant on the batch stream: writes the 24 rows into device memory of shape (24, ld), ld = the batch's leading
+        dimension (row r, instance b at r * ld + b): `out` is a contiguous float64 device tensor of that shape or a raw device pointer (int)"""
+        ctrl = self._need_ctrl()
+        ctrl._push_state()
+        ld = capi.lib().saip_batch_ld(ctrl._h)
+        if isinstance(out, int):
+            ptr = out
+        else:
+            if tuple(out.shape) != (24, ld) or not out.is_contiguous() or str(out.dtype) != "torch.float64":
+                raise ValueError(f"getTaskDiagnosticsDevice: expected a contiguous float64 tensor of shape (24, {ld})")
+            ptr = out.data_ptr()
+        capi.check(capi.lib().saip_batch_task_diagnostics_device(ctrl._h, self._id, C.c_void_p(ptr)))
+        return out
+
+    def getPositionError(self):
+        """(B, 3) sigmaPosition (goal - current position), MotionForceTask.cpp:540-542"""
+        return self.getTaskDiagnostics()["position_error"]
+
+    def getOrientationError(self):
+        """(B, 3) sigmaOrientation orientationError(goal, current), MotionForceTask.cpp:544-546"""
+        return self.getTaskDiagnostics()["orientation_error"]
+
+    def getCurrentLinearVelocity(self):
+        """(B, 3) rows 0-2 of (P J) dq, MotionForceTask.cpp:293-295"""
+        return self.getTaskDiagnostics()["linear_velocity"]
+
+    def getCurrentAngularVelocity(self):
+        """(B, 3) rows 3-5 of (P J) dq, MotionForceTask.cpp:296-298"""
+        return self.getTaskDiagnostics()["angular_velocity"]
+
+    def getSensedForceControlWorldFrame(self):
+        """(B, 3) sensed force at the control point in the world frame, MotionForceTask.cpp:805-828"""
+        return self.getTaskDiagnostics()["sensed_force"]
+
+    def getSensedMomentControlWorldFrame(self):
+        """(B, 3) sensed moment at the control point in the world frame, MotionForceTask.cpp:805-828"""
+        return self.getTaskDiagnostics()["sensed_moment"]
+
+    def getUnitMassForce(self):
+        """(B, 6) position / orientation term of the control law (MotionForceTask.h:266) evaluated at the current state"""
+        return self.getTaskDiagnostics()["unit_mass_force"]
+
     def _sigma(self, dim, axis, sel, R):
         """sigmaPosition / sigmaOrientation, MotionForceTask.cpp:892-971: sel (I - sigma_force) sel^T with the force (moment) space given
         by `dim` and `axis`, in the compliant frame when the task is parametrised there"""

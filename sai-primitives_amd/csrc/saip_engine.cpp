@@ -24,6 +24,7 @@ hipError_t launch_cycle_oct(const CycleParams& P, hipStream_t stream);
 hipError_t launch_cycle_wave(const CycleParams& P, hipStream_t stream);
 hipError_t launch_cycle_octjf(const CycleParams& P, hipStream_t stream);
 hipError_t launch_pose(const CycleParams& P, int task, double* out, hipStream_t stream);
+hipError_t launch_task_diag(const CycleParams& P, int task, const double* goal, const double* desired, int gcomps, double* out, hipStream_t stream);
 hipError_t launch_otg_joints(const OtgDev& O, int B, int ld, int mode, hipStream_t stream);
 hipError_t launch_otg_cartesian(const OtgDev& O, int B, int ld, int mode, hipStream_t stream);
 hipError_t launch_otg_pair(const OtgDev& Oc, const OtgDev& Oj, int B, int ld, hipStream_t stream);
@@ -370,6 +371,7 @@ struct saip_batch {
 	TaskDev* tasks_dev = nullptr;
 	std::vector<void*> allocs;
 	double* pose_dev = nullptr;              // [12][ld] scratch of saip_batch_get_current_pose_host
+	double* task_diag_dev = nullptr;         // [24][ld] scratch of saip_batch_get_task_diagnostics_host
 	hipGraph_t rollout_graph = nullptr;      // one captured closed-loop period (saip_batch_rollout_async)
 	hipGraphExec_t rollout_exec = nullptr;
 	long state_epoch = 0;                    // bumped whenever the resident state changes (per-task models become stale)
@@ -1729,6 +1731,34 @@ extern "C" saip_status saip_batch_get_current_pose_host(saip_batch* b, int task,
 	if (pos && (st = copy_d2h(b, pos, b->pose_dev, 3))) return st;
 	if (rot && (st = copy_d2h(b, rot, b->pose_dev + 3 * (size_t)b->ld, 9))) return st;
 	return SAIP_OK;
+}
+// task diagnostics of one motion-force task (saip_task_diag.hip) for the state last pushed, into out_dev [24][ld] on the batch stream
+static saip_status launch_task_diagnostics(saip_batch* b, int task, double* out_dev, const char* fn) {
+	saip_status st = need_type(b, task, saip::TASK_MOTION_FORCE, fn);
+	if (st) return st;
+	if ((st = need_ready(b, fn))) return st;
+	if (!out_dev) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null output", fn);
+	CycleParams P;
+	if ((st = make_params(b, P, false))) return st;
+	TaskHost& T = b->tasks[task];
+	const bool otg = T.otg_enabled && T.otg_alloc && T.otg_inited;  // as saip_batch_get_desired_host
+	hipError_t e = saip::launch_task_diag(P, task, T.goal_dev, otg ? T.desired_dev : T.goal_dev, T.dev.goal_comps, out_dev, b->stream);
+	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "task diagnostics kernel launch failed: %s", hipGetErrorString(e));
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_get_task_diagnostics_host(saip_batch* b, int task, double* out) {
+	const char* fn = "saip_batch_get_task_diagnostics_host";
+	saip_status st = need_type(b, task, saip::TASK_MOTION_FORCE, fn);
+	if (st) return st;
+	if ((st = need_ready(b, fn))) return st;
+	if (!out) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null output", fn);
+	if (!b->task_diag_dev && (st = dev_alloc(b, &b->task_diag_dev, (size_t)24 * b->ld))) return st;
+	if ((st = launch_task_diagnostics(b, task, b->task_diag_dev, fn))) return st;
+	HIP_TRY(hipStreamSynchronize(b->stream));
+	return copy_d2h(b, out, b->task_diag_dev, 24);
+}
+extern "C" saip_status saip_batch_task_diagnostics_device(saip_batch* b, int task, double* out_dev) {
+	return launch_task_diagnostics(b, task, out_dev, "saip_batch_task_diagnostics_device");
 }
 extern "C" saip_status saip_batch_reinitialize_task(saip_batch* b, int task) {
 	saip_status st = need_ready(b, "saip_batch_reinitialize_task");

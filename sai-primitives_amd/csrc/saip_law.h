@@ -39,6 +39,43 @@ __device__ __forceinline__ void law_sigma_space(CP Pb, const int dim, CP axis, c
 		LAW_UNR for (int j = 0; j < 3; j++) out[3 * i + j] = T[3 * i] * Pb[3 * j] + T[3 * i + 1] * Pb[3 * j + 1] + T[3 * i + 2] * Pb[3 * j + 2];
 }
 
+// The selection projectors of a motion-force task, in place: sigmaForce / sigmaMoment (:892-925, :932-966), then sigmaPosition =
+// Ppos (I - sigmaForce) Ppos^T and sigmaOrientation = Pori (I - sigmaMoment) Pori^T (:927-930, :968-971).  Names in the caller's scope:
+// tk (task pointer), rot (Rc or I), the outputs sig_f, sig_m, sig_p, sig_o [9] and the scratch T, ImS [9].  Shared by the control law and
+// the task diagnostics (saip_task_diag.hip); a macro rather than a function so that the law compiles to exactly the code it did before.
+#define LAW_MOTION_SIGMAS \
+	law_sigma_space(tk->Ppos, tk->force_dim, tk->force_axis, rot, sig_f);                                                           \
+	law_sigma_space(tk->Pori, tk->moment_dim, tk->moment_axis, rot, sig_m);                                                         \
+	LAW_UNR for (int pass = 0; pass < 2; pass++) {                                                                                  \
+		const double* sg = pass ? sig_m : sig_f;                                                                                    \
+		double* so = pass ? sig_o : sig_p;                                                                                          \
+		LAW_UNR for (int i = 0; i < 9; i++) ImS[i] = ((i % 4) == 0 ? 1.0 : 0.0) - sg[i];                                            \
+		LAW_UNR for (int i = 0; i < 3; i++)                                                                                         \
+			LAW_UNR for (int j = 0; j < 3; j++) {                                                                                   \
+				const double p0 = pass ? tk->Pori[3 * i] : tk->Ppos[3 * i], p1 = pass ? tk->Pori[3 * i + 1] : tk->Ppos[3 * i + 1],  \
+							 p2 = pass ? tk->Pori[3 * i + 2] : tk->Ppos[3 * i + 2];                                                 \
+				T[3 * i + j] = p0 * ImS[j] + p1 * ImS[3 + j] + p2 * ImS[6 + j];                                                     \
+			}                                                                                                                       \
+		LAW_UNR for (int i = 0; i < 3; i++)                                                                                         \
+			LAW_UNR for (int j = 0; j < 3; j++) {                                                                                   \
+				const double p0 = pass ? tk->Pori[3 * j] : tk->Ppos[3 * j], p1 = pass ? tk->Pori[3 * j + 1] : tk->Ppos[3 * j + 1],  \
+							 p2 = pass ? tk->Pori[3 * j + 2] : tk->Ppos[3 * j + 2];                                                 \
+				so[3 * i + j] = T[3 * i] * p0 + T[3 * i + 1] * p1 + T[3 * i + 2] * p2;                                              \
+			}                                                                                                                       \
+	}
+
+// updateSensedForceAndMoment (:805-828), in place: sensed force FS / moment MS in the sensor frame -> control frame (tk->Rcs, tk->tcs,
+// with Rl = tk->Rcs) -> world (Rc).  Names in the caller's scope: tk, Rc, Rl [9], the scratch fc, mc [3] and the outputs fsw, msw [3].
+// Shared by the control law and the task diagnostics, a macro for the same reason as LAW_MOTION_SIGMAS.
+#define LAW_SENSED_WRENCH(FS, MS) \
+	law_mat3_vec(Rl, FS, fc);                        \
+	law_mat3_vec(Rl, MS, mc);                          \
+	mc[0] += tk->tcs[1] * fc[2] - tk->tcs[2] * fc[1];  \
+	mc[1] += tk->tcs[2] * fc[0] - tk->tcs[0] * fc[2];  \
+	mc[2] += tk->tcs[0] * fc[1] - tk->tcs[1] * fc[0];  \
+	law_mat3_vec(Rc, fc, fsw);                         \
+	law_mat3_vec(Rc, mc, msw);
+
 // General motion-force law.  tk: task constants (any address space); vw = Jw dq (unprojected world twist of the control point);
 // xp, Rc: control point / control frame; G: goal block (36: x3 R9 v3 w3 a3 alpha3 f3 m3 + sensed force 3, sensed moment 3 in the
 // sensor frame); ip, io: position / orientation integrators (in/out); ifm: force (0..2) and moment (3..5) integrators (in/out).
@@ -121,25 +158,7 @@ __device__ __forceinline__ void law_motion_force_general(TK tk, const double* vw
 	const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 	const double* rot = tk->param_in_compliant_frame ? Rc : I3;
 	double sig_f[9], sig_m[9], sig_p[9], sig_o[9], T[9], ImS[9];
-	law_sigma_space(tk->Ppos, tk->force_dim, tk->force_axis, rot, sig_f);
-	law_sigma_space(tk->Pori, tk->moment_dim, tk->moment_axis, rot, sig_m);
-	LAW_UNR for (int pass = 0; pass < 2; pass++) {  // sigmaPosition = Ppos (I - sigmaForce) Ppos^T, same for orientation (:927-930, :968-971)
-		const double* sg = pass ? sig_m : sig_f;
-		double* so = pass ? sig_o : sig_p;
-		LAW_UNR for (int i = 0; i < 9; i++) ImS[i] = ((i % 4) == 0 ? 1.0 : 0.0) - sg[i];
-		LAW_UNR for (int i = 0; i < 3; i++)
-			LAW_UNR for (int j = 0; j < 3; j++) {
-				const double p0 = pass ? tk->Pori[3 * i] : tk->Ppos[3 * i], p1 = pass ? tk->Pori[3 * i + 1] : tk->Ppos[3 * i + 1],
-							 p2 = pass ? tk->Pori[3 * i + 2] : tk->Ppos[3 * i + 2];
-				T[3 * i + j] = p0 * ImS[j] + p1 * ImS[3 + j] + p2 * ImS[6 + j];
-			}
-		LAW_UNR for (int i = 0; i < 3; i++)
-			LAW_UNR for (int j = 0; j < 3; j++) {
-				const double p0 = pass ? tk->Pori[3 * j] : tk->Ppos[3 * j], p1 = pass ? tk->Pori[3 * j + 1] : tk->Ppos[3 * j + 1],
-							 p2 = pass ? tk->Pori[3 * j + 2] : tk->Ppos[3 * j + 2];
-				so[3 * i + j] = T[3 * i] * p0 + T[3 * i + 1] * p1 + T[3 * i + 2] * p2;
-			}
-	}
+	LAW_MOTION_SIGMAS
 	double v[3], w[3], tmp[3], e3[3], gf[3], gm[3];
 	LAW_UNR for (int i = 0; i < 3; i++) {
 		v[i] = tk->Ppos[3 * i] * vw[0] + tk->Ppos[3 * i + 1] * vw[1] + tk->Ppos[3 * i + 2] * vw[2];  // J = P Jw (:293-298)
@@ -151,13 +170,7 @@ __device__ __forceinline__ void law_motion_force_general(TK tk, const double* vw
 		// updateSensedForceAndMoment (:805-828): sensor frame -> control frame -> world
 		double fc[3], mc[3], fsw[3], msw[3], t2[3], Rl[9];
 		LAW_UNR for (int i = 0; i < 9; i++) Rl[i] = tk->Rcs[i];
-		law_mat3_vec(Rl, G + 30, fc);
-		law_mat3_vec(Rl, G + 33, mc);
-		mc[0] += tk->tcs[1] * fc[2] - tk->tcs[2] * fc[1];
-		mc[1] += tk->tcs[2] * fc[0] - tk->tcs[0] * fc[2];
-		mc[2] += tk->tcs[0] * fc[1] - tk->tcs[1] * fc[0];
-		law_mat3_vec(Rc, fc, fsw);
-		law_mat3_vec(Rc, mc, msw);
+		LAW_SENSED_WRENCH(G + 30, G + 33)
 		const double kff_f = tk->cl_force ? tk->kff_force : 1.0, kff_m = tk->cl_force ? tk->kff_moment : 1.0;  // :484-487: both scaled by the FORCE flag
 		if (tk->cl_force) {  // :327-349 with the passivity controller disabled (POPCExplicitForceControl.cpp:31-33): vcl - kv vr
 			double d[3], sd[3], fb[3], nrm = 0.0;
