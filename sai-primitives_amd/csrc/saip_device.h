@@ -121,14 +121,13 @@ struct CycleParams {
 	int rank_bound[SAIP_MAXT];    // batch-uniform upper bound on the rank of each task in the hierarchy
 	int lane_task_is_joint[SAIP_MAXT];
 	int lane_prefetch_ok;         // stack is {motion-force, full joint task}: the prefetch layout of the latency variant applies
-	int lane_active;              // instances per wavefront in the lane kernel (64 = every lane)
+	int wave_general_joint;       // wavefront kernel: some joint task needs a range basis (anything but one full joint task closing the hierarchy)
 	int lane_general;             // some task needs the general control laws (velocity saturation / force or moment space)
 	int oct_general_joint;        // eight-lane kernel, joint task: 0 rank <= 1 behind a 6-dof task, 1 Gram path (<= 4 rows), 2 full task behind a partial one
 	int reinit_task, reinit_mask; // reinit kernel: task (-1 = all) and parts (1 linear/joint, 2 angular, 4 goal force+moment)
 	int any_bie;
 	int oct_partial_mf;           // eight-lane kernel: the motion-force task is partial (k < 6)
 	int oct_truncate;             // eight-lane kernel: singularity handling disabled -> near-singular instances are reduced in the kernel
-	int wave_general_joint;       // wavefront kernel: some joint task needs a range basis (anything but one full joint task closing the hierarchy)
 	double bie_thr;
 	// per-task entry points of the general kernel (TemplateTask::updateTaskModel(N_prec) / computeTorques() / computeTorques(tau_prec),
 	// TemplateTask.h:43-60): evaluate ONE task with a caller-supplied N_prec instead of walking the hierarchy

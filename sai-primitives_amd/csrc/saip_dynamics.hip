@@ -8,12 +8,11 @@
 //   dq <- dq + dt qdd ;  q <- q + dt dq     (semi-implicit Euler, `substeps` times per call with the torque held)
 //
 // One lane per instance (7-dof chains run saip_dynamics_oct.hip instead: eight lanes per instance).  Bias forces by one recursive Newton-Euler pass in world coordinates, M(q) from composite rigid bodies
-// (spatial inertias about the world origin, suffix sums along the chain), Cholesky solve; fully unrolled for 7-dof arms.  Per-body arrays are lane-private
+// (spatial inertias about the world origin, suffix sums along the chain), Cholesky solve.  Per-body arrays are lane-private
 // (scratch for NMAX = 32, mostly registers for NMAX = 8); the kernel is FP64-latency bound like the cycle kernels and is not on the
 // benchmarked path.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
 
 #include "saip_device.h"
 
@@ -126,9 +125,8 @@ __device__ void rnea(const ModelDev& md, int n, const Chain<NMAX>& K, const doub
 // Spatial inertia about the world origin O: mass m, first moment hm = m c, rotational inertia Io = R I R^T + m (c.c 1 - c c^T).
 // Column j: momentum of the composite body j.. under the unit motion of joint j, (p, L_O) = Ic_j s_j with s_j = (z_j, o_j x z_j) for a
 // revolute and (0, z_j) for a prismatic joint; M_ij = s_i . (L_O, p) for i <= j.
-template <int NMAX, bool EXACT>
-__device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, int n_rt, const Chain<NMAX>& K, double (&M)[NMAX][NMAX]) {
-	const int n = EXACT ? NMAX : n_rt;
+template <int NMAX>
+__device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, const int n, const Chain<NMAX>& K, double (&M)[NMAX][NMAX]) {
 	double cm = 0.0;
 	V3 ch = v3(0, 0, 0);
 	double cI[6] = {0, 0, 0, 0, 0, 0};  // xx yy zz xy xz yz
@@ -177,12 +175,12 @@ __device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, int n_rt, co
 	}
 }
 
-template <int NMAX, bool EXACT>
+template <int NMAX>
 __global__ void __launch_bounds__(64) saip_integrate_kernel(const SimParams S) {
 	const int b = blockIdx.x * blockDim.x + threadIdx.x;
 	if (b >= S.B) return;
 	const ModelDev& md = *S.model;
-	const int n = EXACT ? NMAX : S.n;
+	const int n = S.n;
 	double q[NMAX], dq[NMAX], tau[NMAX], h[NMAX], ddq[NMAX], e[NMAX];
 	double M[NMAX][NMAX];
 #pragma unroll
@@ -199,7 +197,7 @@ __global__ void __launch_bounds__(64) saip_integrate_kernel(const SimParams S) {
 	for (int step = 0; step < S.substeps; step++) {
 		chain_fk<NMAX>(md, n, q, K);
 		rnea<NMAX>(md, n, K, dq, e, a0, true, h);  // b(q, dq) + g(q)
-		mass_matrix_crb<NMAX, EXACT>(md, n, K, M);
+		mass_matrix_crb<NMAX>(md, n, K, M);
 		// Cholesky M = L L^T (lower, in place), then two triangular solves
 #pragma unroll
 		for (int k = 0; k < n; k++) {
@@ -255,13 +253,11 @@ hipError_t launch_integrate_oct(const SimParams& S, hipStream_t stream);  // sai
 
 hipError_t launch_integrate(const SimParams& S, hipStream_t stream) {
 	// 7-dof chains: the eight-lanes-per-instance kernel is faster at every batch size measured (8.7 vs 33.4 us at 4096, 46.8 vs 81.1 us at
-	// 65 536, 166 vs 218 us at 262 144 per two substeps); SAIP_OCT_DYN_MAX_BATCH=0 selects the lane-per-instance kernel for comparisons
-	static const char* oct_env = getenv("SAIP_OCT_DYN_MAX_BATCH");
-	if (S.n == 7 && (!oct_env || S.B <= atoi(oct_env))) return launch_integrate_oct(S, stream);
+	// 65 536, 166 vs 218 us at 262 144 per two substeps)
+	if (S.n == 7) return launch_integrate_oct(S, stream);
 	const int grid = (S.B + 63) / 64;
-	if (S.n == 7) hipLaunchKernelGGL((saip_integrate_kernel<7, true>), dim3(grid), dim3(64), 0, stream, S);   // Panda-class arms: unrolled
-	else if (S.n <= 8) hipLaunchKernelGGL((saip_integrate_kernel<8, false>), dim3(grid), dim3(64), 0, stream, S);
-	else hipLaunchKernelGGL((saip_integrate_kernel<32, false>), dim3(grid), dim3(64), 0, stream, S);
+	if (S.n <= 8) hipLaunchKernelGGL((saip_integrate_kernel<8>), dim3(grid), dim3(64), 0, stream, S);
+	else hipLaunchKernelGGL((saip_integrate_kernel<32>), dim3(grid), dim3(64), 0, stream, S);
 	return hipGetLastError();
 }
 

@@ -29,24 +29,16 @@ static_assert(sizeof(OctDynInst) % 256 == 16, "instance stride must be 2 (mod 32
 // inclusive prefix (towards higher joints) / suffix (towards lower joints) sums of K doubles over the 8 lanes of an instance
 // (interleaved lane layout of saip_oct_common.h: the scans need no masking)
 template <int K>
-__device__ __forceinline__ void oct_prefix_sum(double (&x)[K], const int r) {
-#define OCT_PSUM_STEP(D)                                                                              \
-	UNR for (int e = 0; e < K; e++) {                                                                 \
-		const double v = OCT_ILV ? octl_shr<D, false>(x[e]) : oct_dpp<DPP_ROW_SHR + D>(x[e]);         \
-		x[e] += (OCT_ILV || r >= D) ? v : 0.0;                                                        \
-	}
+__device__ __forceinline__ void oct_prefix_sum(double (&x)[K]) {
+#define OCT_PSUM_STEP(D) UNR for (int e = 0; e < K; e++) x[e] += octl_shr<D, false>(x[e]);
 	OCT_PSUM_STEP(1)
 	OCT_PSUM_STEP(2)
 	OCT_PSUM_STEP(4)
 #undef OCT_PSUM_STEP
 }
 template <int K>
-__device__ __forceinline__ void oct_suffix_sum(double (&x)[K], const int r) {
-#define OCT_SSUM_STEP(D)                                                                              \
-	UNR for (int e = 0; e < K; e++) {                                                                 \
-		const double v = OCT_ILV ? octl_shl<D>(x[e]) : oct_dpp<DPP_ROW_SHL + D>(x[e]);                \
-		x[e] += (OCT_ILV || r + D < 8) ? v : 0.0;                                                     \
-	}
+__device__ __forceinline__ void oct_suffix_sum(double (&x)[K]) {
+#define OCT_SSUM_STEP(D) UNR for (int e = 0; e < K; e++) x[e] += octl_shl<D>(x[e]);
 	OCT_SSUM_STEP(1)
 	OCT_SSUM_STEP(2)
 	OCT_SSUM_STEP(4)
@@ -100,9 +92,9 @@ __device__ __forceinline__ void integrate_oct_body(const SimParams& S, OctDynIns
 			oct_mat3_vec(R0, ax, d);
 			UNR for (int e = 0; e < 3; e++) Tw[9 + e] = p0[e] + d[e] * q_r;
 		}
-	OCT_FRAME_STEP(1, Tw, r)
-	OCT_FRAME_STEP(2, Tw, r)
-	OCT_FRAME_STEP(4, Tw, r)
+	OCT_FRAME_STEP(1, Tw)
+	OCT_FRAME_STEP(2, Tw)
+	OCT_FRAME_STEP(4, Tw)
 		double z[3], o[3] = {Tw[9], Tw[10], Tw[11]};
 		oct_mat3_vec(Tw, ax, z);
 		// joint motion axis about the world origin
@@ -157,7 +149,7 @@ __device__ __forceinline__ void integrate_oct_body(const SimParams& S, OctDynIns
 		if (!act) {
 			UNR for (int e = 0; e < 6; e++) V[e] = 0.0;
 		}
-		oct_prefix_sum<6>(V, r);  // spatial velocity of body r about the world origin: (omega, v_O)
+		oct_prefix_sum<6>(V);  // spatial velocity of body r about the world origin: (omega, v_O)
 		double A[6];
 		{
 			// d/dt S_r = V_r x S_r (motion cross product): (w x s_w, w x s_v + v x s_w)
@@ -167,7 +159,7 @@ __device__ __forceinline__ void integrate_oct_body(const SimParams& S, OctDynIns
 				A[3 + e] = act ? (wxsv[e] + vxsw[e]) * dq_r : 0.0;
 			}
 		}
-		oct_prefix_sum<6>(A, r);
+		oct_prefix_sum<6>(A);
 		UNR for (int e = 0; e < 3; e++) A[3 + e] -= S.gravity[e];  // base acceleration -g: gravity as a fictitious acceleration of the whole chain
 		double F[6];  // (moment about O, force)
 		{
@@ -181,11 +173,11 @@ __device__ __forceinline__ void integrate_oct_body(const SimParams& S, OctDynIns
 				F[3 + e] = pa[e] + wxp[e];
 			}
 		}
-		oct_suffix_sum<6>(F, r);  // wrench transmitted through joint r
+		oct_suffix_sum<6>(F);  // wrench transmitted through joint r
 		const double h_r = sw[0] * F[0] + sw[1] * F[1] + sw[2] * F[2] + sv[0] * F[3] + sv[1] * F[4] + sv[2] * F[5];
 		sm.rhs[r] = tau_r - h_r - S.damping * dq_r;
 		// ---- M(q): composite inertias (suffix sums), row r of the lower triangle: M_ri = S_i . (Ic_r S_r), i <= r
-		oct_suffix_sum<10>(Bd, r);
+		oct_suffix_sum<10>(Bd);
 		oct_wave_sync();
 		{
 			double L[3], p[3];

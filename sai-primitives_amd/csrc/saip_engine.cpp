@@ -2,12 +2,9 @@
 // C++ (the reference is a C++ library), HIP runtime only -- no PyTorch, no Eigen.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
-#include <climits>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -372,8 +369,6 @@ struct saip_batch {
 	std::vector<void*> allocs;
 	double* pose_dev = nullptr;              // [12][ld] scratch of saip_batch_get_current_pose_host
 	double* task_diag_dev = nullptr;         // [24][ld] scratch of saip_batch_get_task_diagnostics_host
-	hipGraph_t rollout_graph = nullptr;      // one captured closed-loop period (saip_batch_rollout_async)
-	hipGraphExec_t rollout_exec = nullptr;
 	long state_epoch = 0;                    // bumped whenever the resident state changes (per-task models become stale)
 	double* diag_tau = nullptr;              // scratch torques / status of diagnostic launches (the last cycle's results stay intact)
 	uint8_t* diag_status = nullptr;
@@ -389,27 +384,6 @@ struct saip_batch {
 	double sim_dt = 0, sim_damping = 0, sim_gravity[3] = {0, 0, 0};
 	bool sim_done = false;                   // ... and whether it did (eight-lane kernel, headline-type stack, no slow path behind)
 };
-
-// Waiting for the batch's stream.  hipStreamSynchronize parks the thread on an interrupt (4 - 5 us from the end of the last kernel to the
-// return when the thread is the only waiter); polling hipStreamQuery returns within ~1 us.  Opt-in (SAIP_SPIN_WAIT_US = how long to poll before
-// blocking; default 0 = block at once): a loop that waits once per cycle and then reads the torques from a bound device buffer gains the
-// difference, but a caller that follows up with ANOTHER runtime wait (hipDeviceSynchronize, torch.cuda.synchronize) pays for that one's own
-// marker round trip (~19 us instead of ~4 after a blocking wait) -- measured with bench.py at 20 steps: 10.2 us per step polling, 9.7 blocking.
-static hipError_t wait_stream(hipStream_t stream) {
-	static const long spin_us = [] {
-		const char* e = getenv("SAIP_SPIN_WAIT_US");
-		return e ? atol(e) : 0L;
-	}();
-	if (spin_us > 0) {
-		const auto t0 = std::chrono::steady_clock::now();
-		for (int it = 0;; it++) {
-			const hipError_t e = hipStreamQuery(stream);
-			if (e != hipErrorNotReady) return e;
-			if ((it & 15) == 15 && std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > spin_us) break;
-		}
-	}
-	return hipStreamSynchronize(stream);
-}
 
 static bool has_device(const saip_batch* b) { return b->device >= 0; }
 static saip_status need_ready(saip_batch* b, const char* fn);
@@ -453,8 +427,6 @@ extern "C" void saip_batch_destroy(saip_batch* b) {
 		if (b->sync_event) (void)hipEventDestroy(b->sync_event);
 		for (hipEvent_t e : b->time_ev)
 			if (e) (void)hipEventDestroy(e);
-		if (b->rollout_exec) (void)hipGraphExecDestroy(b->rollout_exec);
-		if (b->rollout_graph) (void)hipGraphDestroy(b->rollout_graph);
 		for (void* p : b->allocs) (void)hipFree(p);
 		if (b->stream) (void)hipStreamDestroy(b->stream);
 	}
@@ -1422,11 +1394,6 @@ static saip_status make_params(saip_batch* b, CycleParams& P, bool diag) {
 	}
 	P.lane_prefetch_ok = (b->tasks.size() == 2 && b->tasks[0].dev.type == saip::TASK_MOTION_FORCE && b->tasks[1].dev.type == saip::TASK_JOINT &&
 						  b->tasks[1].dev.m == P.n && !b->tasks[0].dev.general_law) ? 1 : 0;
-	{
-		static const char* la = getenv("SAIP_LANE_ACTIVE");  // diagnostic knob, read once
-		static const int a = la ? atoi(la) : 64;
-		P.lane_active = (a >= 1 && a <= 64) ? a : 64;
-	}
 	return SAIP_OK;
 }
 // the lane-per-instance register kernel covers 6..8 dof, at most two motion-force tasks and one shared BIE threshold
@@ -1596,16 +1563,15 @@ static saip_status launch_cycle(saip_batch* b, bool diag) {
 		}
 		// small batches of the headline stack: eight lanes per instance (the lane kernel would leave most of the chip idle)
 		// Up to which batch: 1024 wavefronts (8192 instances) are resident at once, larger launches run in rounds.  Measured against the lane
-		// kernel (tools/ab_cliff.sh, round 3): the lean instantiation (config 2's stack) stays ahead up to 24 576 instances (26.8 against
+		// kernel (round 3): the lean instantiation (config 2's stack) stays ahead up to 24 576 instances (26.8 against
 		// 31.1 us) and is level at 32 768; every other instantiation -- partial tasks, reduced tasks, joint task first, 6 / 8 dof -- is ahead
 		// at every size (config 3: 109 against 195 us at 65 536, 384 against 627 at 262 144; config 6: 102 against 190 at 65 536), and
 		// stacks whose instances leave the non-singular branch are not a contest (the lane kernel hands those to the general kernel).
-		static const char* oct_env = getenv("SAIP_OCT_MAX_BATCH");
 		const bool oct_ok = oct_eligible(b, P);
 		const bool oct_lean = oct_ok && P.oct_general_joint == 0 && !(P.jla || P.lane_general || P.oct_partial_mf);
-		const int oct_max = oct_env ? atoi(oct_env) : (oct_lean ? 24576 : INT_MAX);
-		const bool oct = oct_ok && (b->kernel_choice == 3 || (b->kernel_choice == 0 && b->B <= oct_max));
-		const bool octjf = !oct && octjf_eligible(b, P) && (b->kernel_choice == 3 || (b->kernel_choice == 0 && b->B <= oct_max));
+		const bool oct_size = !oct_lean || b->B <= 24576;
+		const bool oct = oct_ok && (b->kernel_choice == 3 || (b->kernel_choice == 0 && oct_size));
+		const bool octjf = !oct && octjf_eligible(b, P) && (b->kernel_choice == 3 || (b->kernel_choice == 0 && oct_size));
 		// the eight-lane kernel runs the blended singularity strategies of the headline stack itself (and passes a fully singular task
 		// through): with the handling enforced nothing is left for a slow path, and what it still refuses the general kernel would too
 		if (oct && P.oct_general_joint == 0 && b->tasks[0].dev.sing_handling) {
@@ -1613,10 +1579,9 @@ static saip_status launch_cycle(saip_batch* b, bool diag) {
 			P.flag_count = P.flag_count_next = P.flag_list = nullptr;
 		}
 		// every other eight-lane stack: the wavefront that flags an instance recomputes it itself behind its epilogue (the general kernel's body on
-		// its own LDS block) -- no list and no second launch behind the kernel (round 4; SAIP_NO_SLOW_TAIL=1 restores the list launch for A/B runs)
-		static const bool tail_on = getenv("SAIP_NO_SLOW_TAIL") == nullptr;
+		// its own LDS block) -- no list and no second launch behind the kernel (round 4)
 		P.slow_tail = 0;
-		if (slow && tail_on && !b->flagged_on_list && ((oct && P.oct_general_joint != 0) || octjf)) {
+		if (slow && !b->flagged_on_list && ((oct && P.oct_general_joint != 0) || octjf)) {
 			slow = false;
 			P.slow_tail = 1;
 			P.flag_count = P.flag_count_next = P.flag_list = nullptr;
@@ -1802,7 +1767,10 @@ extern "C" saip_status saip_batch_step_async(saip_batch* b) {
 extern "C" saip_status saip_batch_synchronize(saip_batch* b) {
 	saip_status st = need_ready(b, "saip_batch_synchronize");
 	if (st) return st;
-	HIP_TRY(wait_stream(b->stream));  // (kernels only: the host-copy entry points below keep the blocking wait of their hipMemcpyAsync)
+	// A blocking wait.  Polling hipStreamQuery returns ~1 us after the last kernel instead of 4 - 5, but a caller that follows up with ANOTHER
+	// runtime wait (hipDeviceSynchronize, torch.cuda.synchronize) then pays for that one's own marker round trip (~19 us instead of ~4 after a
+	// blocking wait) -- measured with bench.py at 20 steps: 10.2 us per step polling, 9.7 blocking.
+	HIP_TRY(hipStreamSynchronize(b->stream));
 	return SAIP_OK;
 }
 extern "C" saip_status saip_batch_get_torques_host(saip_batch* b, double* tau_host, uint8_t* status_host) {
@@ -2003,8 +1971,7 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 	S.tau = b->tau_bound ? b->tau_bound : b->tau;
 	S.ddq = nullptr;
 	hipError_t e;
-	static const bool no_fuse = getenv("SAIP_ROLLOUT_NO_FUSE") != nullptr;  // A/B measurements
-	if (with_next_otg && !no_fuse && S.n == 7 && otg_pair_ready(b)) {
+	if (with_next_otg && S.n == 7 && otg_pair_ready(b)) {
 		// rollouts: this integration and the NEXT period's trajectory generation in one launch (they are independent)
 		e = saip::launch_integrate_otg_pair(S, b->tasks[0].otg, b->tasks[1].otg, b->B, b->ld, b->stream);
 		b->otg_prelaunched = true;
@@ -2025,24 +1992,16 @@ extern "C" saip_status saip_batch_integrate(saip_batch* b, double dt, int subste
 // steps x { internal OTGs, control cycle, integrate } on the engine stream, no host synchronisation.  One period is 3-5 small
 // launches.  Plain back-to-back stream launches are the default: they were measured FASTER than replaying a hipGraph of the period
 // (68.6 vs 74.2 us per period at B = 4096, 65.7 vs 70.4 us at B = 256, tools/rollout_bench.py) -- the host enqueues far ahead of the
-// device either way, and the graph adds inter-node latency.  SAIP_ROLLOUT_GRAPH=1 selects the graph path (first period eager: it
-// uploads dirty task constants and initialises OTG state, which must not be baked into the graph; second period captured).
-static void drop_rollout_graph(saip_batch* b) {
-	if (b->rollout_exec) (void)hipGraphExecDestroy(b->rollout_exec);
-	if (b->rollout_graph) (void)hipGraphDestroy(b->rollout_graph);
-	b->rollout_exec = nullptr;
-	b->rollout_graph = nullptr;
-}
+// device either way, and the graph adds inter-node latency.
 extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double sim_dt, int substeps, const double* gravity, double damping) {
 	saip_status st = need_ready(b, "saip_batch_rollout_async");
 	if (st) return st;
 	if (steps < 1 || !(sim_dt > 0) || substeps < 1 || damping < 0) return fail(SAIP_ERR_INVALID_ARGUMENT, "saip_batch_rollout_async: bad arguments");
 	bool any_otg = false;
 	for (auto& T : b->tasks) any_otg = any_otg || T.otg_enabled;
-	static const bool no_fuse_sim = getenv("SAIP_ROLLOUT_NO_FUSE") != nullptr;  // A/B measurements
 	auto period = [&](const bool more = false) -> saip_status {  // more: another period follows inside this call
 		// no internal OTG in the stack: the cycle launch integrates the state itself when it can (eight-lane kernel, no slow path behind)
-		b->sim_want = (!any_otg && !no_fuse_sim && b->model->n == 7) ? substeps : 0;
+		b->sim_want = (!any_otg && b->model->n == 7) ? substeps : 0;
 		b->sim_dt = sim_dt;
 		b->sim_damping = damping;
 		for (int i = 0; i < 3; i++) b->sim_gravity[i] = gravity ? gravity[i] : b->model->dev.gravity[i];
@@ -2063,26 +2022,7 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 		if (s2) b->otg_prelaunched = false;
 		return s2;
 	};
-	static const bool use_graph = getenv("SAIP_ROLLOUT_GRAPH") != nullptr;
-	bool cycle_dependent = false;  // the device-side slow path and the blended singularity strategies read per-cycle launch parameters
-	for (auto& T : b->tasks)               // (list parity, CycleParams::task_cycle): not capturable
-		if (T.dev.type == saip::TASK_MOTION_FORCE && (!T.dev.sing_handling || T.dev.sing_strategies)) cycle_dependent = true;
-	int done = 0;
-	if (use_graph && steps >= 4 && !cycle_dependent) {
-		if ((st = period())) return st;  // eager: uploads, OTG initialisation
-		done = 1;
-		HIP_TRY(hipStreamSynchronize(b->stream));  // a graph still executing from an earlier call must not be destroyed under it
-		drop_rollout_graph(b);
-		HIP_TRY(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
-		st = period();
-		hipError_t ec = hipStreamEndCapture(b->stream, &b->rollout_graph);
-		if (st) return st;
-		if (ec != hipSuccess) return fail(SAIP_ERR_DEVICE, "hipStreamEndCapture failed: %s", hipGetErrorString(ec));
-		HIP_TRY(hipGraphInstantiate(&b->rollout_exec, b->rollout_graph, nullptr, nullptr, 0));
-		for (; done < steps; done++) HIP_TRY(hipGraphLaunch(b->rollout_exec, b->stream));
-		return SAIP_OK;
-	}
-	for (; done < steps; done++)
+	for (int done = 0; done < steps; done++)
 		if ((st = period(done + 1 < steps))) return st;
 	return SAIP_OK;
 }
@@ -2139,8 +2079,8 @@ extern "C" saip_status saip_batch_time_steps(saip_batch* b, int steps, int warmu
 		if ((st = launch_cycle(b, false))) return st;
 	HIP_TRY(hipEventRecord(e1, b->stream));
 	// one wait for the stream (not for the event and then, in the caller, for the stream or the device: each is its own ~15 us
-	// marker round trip, tools/bench_overhead_probe.py), polling first (wait_stream)
-	HIP_TRY(wait_stream(b->stream));
+	// marker round trip, tools/bench_overhead_probe.py)
+	HIP_TRY(hipStreamSynchronize(b->stream));
 	float ms = 0;
 	HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
 	*elapsed_ms = ms;

@@ -19,7 +19,6 @@
 // (wave-uniform branch on a ballot: no cost when no lane needs it, no CPU fallback ever).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
 
 #include "saip_device.h"
 #include "saip_law.h"
@@ -44,10 +43,11 @@ __device__ unsigned long long saip_stamps[256];
 	} while (0)
 #define DIAG_STAMP() PHASE_FENCE()
 #elif defined(SAIP_FENCE)
+// Scheduling barriers between the phases pay off under the default machine scheduler, which the lean instantiation is built with
+// (saip_kernel_lane_lean.hip defines SAIP_FENCE); under the max-ilp strategy of this translation unit the kernels are 0.4-1.5 % faster
+// without them (same session, tools/ab_multi.sh).
 #define PHASE_FENCE() __builtin_amdgcn_sched_barrier(0)
 #else
-// Scheduling barriers between the phases paid off under the default machine scheduler; with the max-ilp strategy the kernels are
-// 0.4-1.5 % faster without them (A/B in one session, tools/ab_multi.sh), so they are now a diagnostic option (-DSAIP_FENCE).
 #define PHASE_FENCE()
 #endif
 #ifndef DIAG_STAMP
@@ -61,9 +61,7 @@ typedef const TaskDev CONSTANT_AS* TaskCPtr;
 // above it (they would otherwise all be issued at kernel entry and exhaust the SGPR file -> v_writelane/v_readlane spills).
 template <typename Ptr>
 __device__ __forceinline__ Ptr launder(Ptr p) {
-#ifndef SAIP_NO_LAUNDER
 	asm volatile("" : "+s"(p));
-#endif
 	return p;
 }
 
@@ -828,15 +826,14 @@ __global__ void __launch_bounds__(64) saip_cycle_lane(const CycleParams P) {
 	constexpr int P_Z = 0, P_O = 3 * N, P_CAP = 6 * N, P_BODY = 6 * N + 24;
 	__shared__ SM sm;
 	const int lane = threadIdx.x;
-	const int act = P.lane_active;  // instances per wavefront (64 = full)
-	if (lane >= act) return;
-	int b = blockIdx.x * act + lane;
+	int b = blockIdx.x * 64 + lane;
 	const bool live = b < P.B;
 	if (!live) b = P.B - 1;  // dead lanes shadow the last instance and never store
 	const ModelCPtr md = (ModelCPtr)P.model;
 	const TaskCPtr tasks = (TaskCPtr)P.tasks;
 	const size_t ld = P.ld;
-#ifdef SAIP_PREWARM  // scalar-cache prewarm: helped the first versions, costs 1 % now (kept for experiments)
+#ifdef SAIP_PREWARM  // scalar-cache prewarm: the lean instantiation is built with it (saip_kernel_lane_lean.hip), where it still pays off;
+                     // it costs the latency variants of this translation unit 1 %
 	{
 		// warm the scalar cache: one double of every 64-byte line of the per-joint records and of the head of the task constants,
 		// all loads in flight at once (one exposed L2 latency) instead of one cold miss per FK iteration / per task phase
@@ -1211,7 +1208,7 @@ static int pick_rj(int n, int rj) {
 // Translation unit of the throughput (LEAN) instantiation only: built with the default machine scheduler, under which it is 6 %
 // faster than under max-ilp (the latency variants are the other way round); see capi.build_library.
 hipError_t launch_cycle_lane_lean(const CycleParams& P, hipStream_t stream) {
-	const dim3 grid((P.B + P.lane_active - 1) / P.lane_active), block(64);
+	const dim3 grid((P.B + 63) / 64), block(64);
 	hipLaunchKernelGGL((saip_cycle_lane<7, 1, SIG_MF_JT, false, true, false>), grid, block, 0, stream, P);
 	return hipGetLastError();
 }
@@ -1229,14 +1226,12 @@ hipError_t launch_cycle_lane(const CycleParams& P, hipStream_t stream, bool* sup
 	// (a variant that prefetched every input into LDS at kernel entry, template parameter PF, measured no faster -- 22.9 vs 22.8 us at
 	// cfg2 -- and is no longer instantiated; the joint-task inputs are requested early in registers instead, see lane_joint_task)
 	// throughput variant once the batch needs more than one wavefront per CU: 36 KB LDS per wavefront instead of 100 KB
-	static const char* lean_env = getenv("SAIP_LANE_LEAN");  // "0"/"1" forces the choice (profiling)
-	const bool lean = lean_env ? (lean_env[0] == '1') : (P.B > 64 * 256);
-	const dim3 grid((P.B + P.lane_active - 1) / P.lane_active), block(64);
+	const bool lean = P.B > 64 * 256;
+	const dim3 grid((P.B + 63) / 64), block(64);
 #define LAUNCH(NN, RR, SS, PP, GG) hipLaunchKernelGGL((saip_cycle_lane<NN, RR, SS, PP, false, GG>), grid, block, 0, stream, P)
 	const bool gl = P.lane_general != 0;
 	if (P.n == 7 && inst == 1 && mf_jt && !gl && lean) return launch_cycle_lane_lean(P, stream);
 	else if (P.n == 7 && inst == 1 && mf_jt && !gl) LAUNCH(7, 1, SIG_MF_JT, false, false);
-#ifndef SAIP_LANE_ONLY_71
 	else if (P.n == 7 && inst == 1 && mf_jt) LAUNCH(7, 1, SIG_MF_JT, false, true);
 	else if (P.n == 7 && inst == 1) LAUNCH(7, 1, SIG_GENERIC, false, true);
 	else if (P.n == 7 && inst == 4 && mf_jt && !gl) LAUNCH(7, 4, SIG_MF_JT, false, false);
@@ -1246,9 +1241,6 @@ hipError_t launch_cycle_lane(const CycleParams& P, hipStream_t stream, bool* sup
 	else if (P.n == 8 && inst == 2) LAUNCH(8, 2, SIG_GENERIC, false, true);
 	else if (P.n == 8) LAUNCH(8, 8, SIG_GENERIC, false, true);
 	else LAUNCH(6, 6, SIG_GENERIC, false, true);
-#else
-	else { *supported = false; return hipSuccess; }
-#endif
 #undef LAUNCH
 	return hipGetLastError();
 }

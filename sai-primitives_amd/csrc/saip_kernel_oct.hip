@@ -85,11 +85,10 @@ template <int R>
 __device__ __forceinline__ void oct_jacobi_n(double (&A)[R][R], double (&V)[R][R], const int lane) {
 	static_assert(R == 4 || R == 6, "even sizes with at most three pairs per round");
 	constexpr int NP = R / 2, RM = R - 1;
-	// which pair of a round this lane computes.  Side by side: lane m of each quad takes pair m (quad_perm broadcasts 0x00 / 0x55 / 0xAA).
-	// Interleaved: a quad holds joints 2 q, 2 q + 1 of two instances -- even joints take pair 0, odd joints pair 1 (quad_perm [0,1,0,1] /
-	// [2,3,2,3] hands them to the quad's lanes of the same instance), and the third pair of a 6 x 6 round is computed by every lane itself
-	// (fetching all three by ds_bpermute from joints 0, 1, 2 measured the same or slower: config 12 27.4 vs 26.7 us; side by side 25.0).
-	const int r = octl_r(lane), m = OCT_ILV ? (r & 1) : ((lane & 3) < NP ? (lane & 3) : 0);
+	// which pair of a round this lane computes.  A quad holds joints 2 q, 2 q + 1 of two instances -- even joints take pair 0, odd joints pair 1
+	// (quad_perm [0,1,0,1] / [2,3,2,3] hands them to the quad's lanes of the same instance), and the third pair of a 6 x 6 round is computed by
+	// every lane itself (fetching all three by ds_bpermute from joints 0, 1, 2 measured the same or slower: config 12 27.4 vs 26.7 us).
+	const int r = octl_r(lane), m = r & 1;
 	// t = tan of the rotation angle: sign(theta) / (|theta| + sqrt(theta^2 + 1)), theta = (aqq - app) / (2 apq), written without the
 	// division by apq; hardware reciprocal / rsqrt estimates + Newton steps (arguments are positive and in range)
 	auto rotation = [](const double apq, const double app, const double aqq, double& cs, double& sn, double& tn) {
@@ -124,7 +123,7 @@ __device__ __forceinline__ void oct_jacobi_n(double (&A)[R][R], double (&V)[R][R
 			}
 			double cs, sn, tn, cs2 = 1.0, sn2 = 0.0, tn2 = 0.0;
 			rotation(apq, app, aqq, cs, sn, tn);
-			if (OCT_ILV && NP == 3) {  // the third pair of the round, in every lane
+			if (NP == 3) {  // the third pair of the round, in every lane
 				const int a_ = (t + 2) % RM, b_ = (t + RM - 2) % RM;
 				const int p = a_ < b_ ? a_ : b_, q = a_ < b_ ? b_ : a_;
 				rotation(A[p][q], A[p][p], A[q][q], cs2, sn2, tn2);
@@ -133,13 +132,9 @@ __device__ __forceinline__ void oct_jacobi_n(double (&A)[R][R], double (&V)[R][R
 				const int a_ = j == 0 ? t : (t + j) % RM, b_ = j == 0 ? RM : (t + RM - j) % RM;
 				const int p = a_ < b_ ? a_ : b_, q = a_ < b_ ? b_ : a_;
 				double c, s_, tj;
-				if (OCT_ILV) {
-					if (j == 0) { c = oct_dpp<0x44>(cs); s_ = oct_dpp<0x44>(sn); tj = oct_dpp<0x44>(tn); }
-					else if (j == 1) { c = oct_dpp<0xEE>(cs); s_ = oct_dpp<0xEE>(sn); tj = oct_dpp<0xEE>(tn); }
-					else { c = cs2; s_ = sn2; tj = tn2; }
-				} else if (j == 0) { c = oct_dpp<0x00>(cs); s_ = oct_dpp<0x00>(sn); tj = oct_dpp<0x00>(tn); }
-				else if (j == 1) { c = oct_dpp<0x55>(cs); s_ = oct_dpp<0x55>(sn); tj = oct_dpp<0x55>(tn); }
-				else { c = oct_dpp<0xAA>(cs); s_ = oct_dpp<0xAA>(sn); tj = oct_dpp<0xAA>(tn); }
+				if (j == 0) { c = oct_dpp<0x44>(cs); s_ = oct_dpp<0x44>(sn); tj = oct_dpp<0x44>(tn); }
+				else if (j == 1) { c = oct_dpp<0xEE>(cs); s_ = oct_dpp<0xEE>(sn); tj = oct_dpp<0xEE>(tn); }
+				else { c = cs2; s_ = sn2; tj = tn2; }
 				const double apq_j = A[p][q];
 				UNR for (int k = 0; k < R; k++) {
 					if (k != p && k != q) {
@@ -191,9 +186,9 @@ __device__ __forceinline__ void oct_fk_frame(const ModelDev& md, const int rr, c
 		oct_mat3_vec(R0, a, d);
 		UNR for (int e = 0; e < 3; e++) Tw[9 + e] = md.p0[rr][e] + d[e] * q;
 	}
-	OCT_FRAME_STEP(1, Tw, r)
-	OCT_FRAME_STEP(2, Tw, r)
-	OCT_FRAME_STEP(4, Tw, r)
+	OCT_FRAME_STEP(1, Tw)
+	OCT_FRAME_STEP(2, Tw)
+	OCT_FRAME_STEP(4, Tw)
 }
 
 
@@ -224,10 +219,9 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	constexpr bool DUO = ROLE != 0;
 	constexpr bool roleA = ROLE != 2, roleB = ROLE != 1;
 	constexpr int N = NN;
-#if !defined(SAIP_OCT_NO_BROWS)
 	// Lean two-wavefront form: B does not wait where A takes the Jacobian from it -- A polls a flag in LDS instead of both meeting at a workgroup
 	// barrier (B was there 1.3 k clocks early) -- and B uses the time it gains to form the rows of A = T1 J^T from the T1 that A publishes
-	// (second flag), which takes the second half of the T1 / A phase off A's chain: 7.04 -> 6.91 us (same session; -DSAIP_OCT_NO_BROWS for the A/B).
+	// (second flag), which takes the second half of the T1 / A phase off A's chain: 7.04 -> 6.91 us (same session).
 	// The flags live in LDS, are zeroed behind one early workgroup barrier, and every poll loop is bounded.
 	constexpr bool BROWS = DUO && !FULL && GJ == 0;
 	auto flag_wait = [&](const int k) {
@@ -240,9 +234,6 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 		if ((threadIdx.x & 63) == 0) __hip_atomic_store(wgflags + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 	};
-#else
-	constexpr bool BROWS = false;
-#endif
 	bool lost = false;  // a bounded poll ran out (cannot happen while both wavefronts of the workgroup run; if it ever does, the instances end flagged, not silently wrong)
 	static_assert(NN == 7 || (FULL && GJ == 2), "6- and 8-dof chains: the general instantiation only");
 	const int lane = threadIdx.x & 63;
@@ -386,9 +377,9 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	const bool track_mf = ROLE == 0 ? track_mf_e : track_mf_l, track_jt = ROLE == 0 ? track_jt_e : track_jt_l;
 	const double mfi_pre = ROLE == 0 ? mfi_pre_e : mfi_pre_l, jti_pre = ROLE == 0 ? jti_pre_e : jti_pre_l;
 	const double jkp_r = ROLE == 0 ? jkp_r_e : jkp_r_l, jkv_r = ROLE == 0 ? jkv_r_e : jkv_r_l, jki_r = ROLE == 0 ? jki_r_e : jki_r_l;
-	OCT_FRAME_STEP(1, Tw, r)
-	OCT_FRAME_STEP(2, Tw, r)
-	OCT_FRAME_STEP(4, Tw, r)
+	OCT_FRAME_STEP(1, Tw)
+	OCT_FRAME_STEP(2, Tw)
+	OCT_FRAME_STEP(4, Tw)
 	UNR for (int e = 0; e < 12; e++) sm.X[r][e] = Tw[e];  // the motion-force task reads its body's frame from here
 	if (roleB && track_mf && r < 6) sm.ist[r] = mfi_pre;  // (behind the frames: the loads have had their time)
 	if (roleA && GJ == 1 && track_jt && r < 4) sm.ist[6 + r] = jti_pre;
@@ -436,20 +427,11 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		UNR for (int e = 0; e < 10; e++) Ic[e] = act ? Bd[e] : 0.0;
 	}
 	// composite inertia of the subtree of joint r (serial chain: bodies r..6): suffix sums over the instance's lanes by DPP row_shl
+	// (the row shifts fill 0 past joint 7: the other instance of the row does not leak in)
 	if (roleA) {
-		// (selects, not multiplications by 0: a neighbouring instance with non-finite state must not leak in)
-		UNR for (int e = 0; e < 10; e++) {
-			const double up = OCT_ILV ? octl_shl<1>(Ic[e]) : oct_dpp<DPP_ROW_SHL + 1>(Ic[e]);
-			Ic[e] += (OCT_ILV || r + 1 < 8) ? up : 0.0;
-		}
-		UNR for (int e = 0; e < 10; e++) {
-			const double up = OCT_ILV ? octl_shl<2>(Ic[e]) : oct_dpp<DPP_ROW_SHL + 2>(Ic[e]);
-			Ic[e] += (OCT_ILV || r + 2 < 8) ? up : 0.0;
-		}
-		UNR for (int e = 0; e < 10; e++) {
-			const double up = OCT_ILV ? octl_shl<4>(Ic[e]) : oct_dpp<DPP_ROW_SHL + 4>(Ic[e]);
-			Ic[e] += (OCT_ILV || r + 4 < 8) ? up : 0.0;
-		}
+		UNR for (int e = 0; e < 10; e++) Ic[e] += octl_shl<1>(Ic[e]);
+		UNR for (int e = 0; e < 10; e++) Ic[e] += octl_shl<2>(Ic[e]);
+		UNR for (int e = 0; e < 10; e++) Ic[e] += octl_shl<4>(Ic[e]);
 	}
 	oct_sync<DUO>();
 	STAMP(2);
@@ -513,13 +495,10 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			fi_pre = -jkp_r * e - jkv_r * (dq_r - jg_dq) - jki_r * ie;  // :342-345
 		}
 	}
-#if !defined(SAIP_OCT_NO_BROWS)
 	if (BROWS) {
 		if (ROLE == 2) flag_set(0, 1);  // B: the Jacobian is in its block
 		oct_sync<DUO>();
-	} else
-#endif
-	if (DUO && !trunc_mode) __syncthreads();  // workgroup barrier: B's Jacobian is complete (A arrives ~1 k clocks after B)
+	} else if (DUO && !trunc_mode) __syncthreads();  // workgroup barrier: B's Jacobian is complete (A arrives ~1 k clocks after B)
 	else oct_sync<DUO>();                     // (reduced tasks: A waits further down, for the Jacobian B has reduced)
 	STAMP(3);
 	// ---------------------------------------------------------------- M^-1: Cholesky factor in every lane, own column of the inverse
@@ -576,9 +555,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		__syncthreads();
 		keep_bits_b = (unsigned)smB.vec[6][7];
 	}
-#if !defined(SAIP_OCT_NO_BROWS)
 	if (BROWS && ROLE == 1) lost = flag_wait(0) == 0;
-#endif
 	UNR for (int a = 0; a < 6; a++)
 		UNR for (int j = 0; j < N; j++) Jf[a][j] = (ROLE == 1 ? smB : sm).J[a][j];
 	double vw[6] = {0, 0, 0, 0, 0, 0};
@@ -598,11 +575,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	STAMP(6);
 	// ---- SingularityHandler branch predicate on G = J J^T (N_prec = I for the first task), every lane of the instance alike
 	bool singular = false, truncated = false, blended_i = false;
-#if defined(SAIP_OCT_EXP_NO_BLEND)  // diagnostic build only: what the blended block costs the ordinary path
-	const bool strategies_on = false;
-#else
 	const bool strategies_on = GJ == 0 && mf.sing_handling && mf.sing_strategies && mf.sh != nullptr;  // batch-uniform; the blended branch lives in the headline stack's tail
-#endif
 	double G[6][6], U6[6][6];
 	bool keepm[6] = {true, true, true, true, true, true};
 	if (roleB) {
@@ -795,12 +768,8 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			sm.T1[a][r] = t1c[a];
 			if (general_bie) sm.Lam[a][r] = tbc[a];
 		}
-#if !defined(SAIP_OCT_NO_BROWS)
 		const bool rows_by_b = BROWS && ROLE == 1 && !general_bie;
 		if (BROWS && ROLE == 1) flag_set(1, general_bie ? 2 : 1);
-#else
-		const bool rows_by_b = false;
-#endif
 		oct_sync<DUO>();
 		if (rank1_bie) {
 			double mee = 0.0;
@@ -983,7 +952,6 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			}
 			if (r == 6) sm.vec[6][6] = (singular ? 1.0 : 0.0) + (truncated ? 2.0 : 0.0);
 		}
-#if !defined(SAIP_OCT_NO_BROWS)
 		if (BROWS && ROLE == 2) {
 			const int f1 = flag_wait(1);
 			lost = f1 == 0;
@@ -997,7 +965,6 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 				}
 			}
 		}
-#endif
 		STAMP(29);
 		__syncthreads();
 		STAMP(30);
@@ -1967,13 +1934,6 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	}
 	}  // GJ != 0
 	STAMP(14);
-#if defined(SAIP_OCT_EXP_FORCE_SCRATCH)  // diagnostic build only: does the mere use of scratch memory by a kernel cost launch time?
-	if (P.B < 0) {
-		volatile double spill[16];
-		spill[lane & 15] = tv;
-		tv += spill[(lane + 3) & 15];
-	}
-#endif
 	// ---------------------------------------------------------------- post-processing, RobotController.cpp:86-116
 	if (P.torque_sat) {
 		const double lim = md.effort[rr];
@@ -2066,8 +2026,8 @@ __device__ __forceinline__ void oct_slow_tail(const CycleParams& P, const bool f
 	static_assert(sizeof(WgSmem<8>) <= 8 * sizeof(OctInst), "the general kernel's block fits the eight instance blocks of a wavefront");
 	WgSmem<8>& wsm = *reinterpret_cast<WgSmem<8>*>(lds);
 	for (int g = 0; g < 8; g++) {
-		const int l0 = OCT_ILV ? (((g >> 1) << 4) | (g & 1)) : (g << 3);  // the lane of joint 0 of instance g (octl_grp / octl_r)
-		if (((votes >> l0) & 1ull) == 0ull) continue;                     // wave-uniform
+		const int l0 = ((g >> 1) << 4) | (g & 1);  // the lane of joint 0 of instance g (octl_grp / octl_r)
+		if (((votes >> l0) & 1ull) == 0ull) continue;    // wave-uniform
 		SAIP_WG_SYNC();  // the block's previous user (the cycle, or the instance before) is done with it
 		wg_cycle<8, 64>(P, (int)blockIdx.x * 8 + g, wsm);
 	}
@@ -2084,12 +2044,10 @@ __global__ void __launch_bounds__(DUO ? 128 : 64) saip_cycle_oct(const CyclePara
 	const bool wave_b = DUO && __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 1;
 	__shared__ int wgflags[2];
 	__shared__ double lawc[FULL ? 96 : 1];  // batch-uniform constants of the partial task's control law (the one wavefront of the workgroup that runs it)
-#if !defined(SAIP_OCT_NO_BROWS)
 	if (DUO && !FULL && GJ == 0) {
 		if (threadIdx.x == 0) wgflags[0] = wgflags[1] = 0;
 		__syncthreads();
 	}
-#endif
 	bool flagged = false;
 	if (DUO) {
 		if (wave_b) oct_cycle_body<FULL, GJ, DUO ? 2 : 0, NN>(P, smem + 8, smem, smem + 8, wgflags, lawc);
@@ -2123,16 +2081,15 @@ __global__ void __launch_bounds__(DUO ? 128 : 64) saip_cycle_oct(const CyclePara
 
 // two wavefronts per instance group for the lean stack while the launch still fits the chip in one round (two workgroups per CU = one
 // wavefront per SIMD: 4096 instances on 256 CUs); beyond that the second wavefront only competes for issue slots (measured, B = 6144:
-// 14.3 us against 10.8 us).  SAIP_OCT_NO_DUO=1: the one-wavefront form, for A/B measurements.
+// 14.3 us against 10.8 us)
 static bool oct_duo_enabled(const int workgroups) {
-	static const bool on = getenv("SAIP_OCT_NO_DUO") == nullptr;
 	static int cus = 0;
 	if (cus == 0) {
 		int dev = 0, n = 0;
 		if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
 		cus = n;
 	}
-	return on && workgroups <= 2 * cus;
+	return workgroups <= 2 * cus;
 }
 
 hipError_t launch_cycle_oct(const CycleParams& P, hipStream_t stream) {

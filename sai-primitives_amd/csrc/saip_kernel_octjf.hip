@@ -176,9 +176,9 @@ __device__ __forceinline__ bool jf_body(const CycleParams& P, JfInst* smem, doub
 		UNR for (int c = 0; c < 4; c++) sm.goal[8 * c + r] = gl[c];
 		if (r < 6) sm.ist[r] = mfi_pre;
 	}
-	OCT_FRAME_STEP(1, Tw, r)
-	OCT_FRAME_STEP(2, Tw, r)
-	OCT_FRAME_STEP(4, Tw, r)
+	OCT_FRAME_STEP(1, Tw)
+	OCT_FRAME_STEP(2, Tw)
+	OCT_FRAME_STEP(4, Tw)
 	double (*Xf)[12] = (ROLE == 2) ? bx[grp] : sm.X;  // the frames of this wavefront (B: its own block)
 	UNR for (int e = 0; e < 12; e++) Xf[r][e] = Tw[e];
 	const bool rev = jtype_r == 1;
@@ -225,20 +225,11 @@ __device__ __forceinline__ bool jf_body(const CycleParams& P, JfInst* smem, doub
 		Bd[9] = Iw[5] - ms * c[1] * c[2];
 		UNR for (int e = 0; e < 10; e++) Ic[e] = act ? Bd[e] : 0.0;
 	}
-	// (selects, not multiplications by 0: a neighbouring instance with non-finite state must not leak in)
+	// composite inertias, suffix sums along the chain (the row shifts fill 0 past joint 7: the other instance of the row does not leak in)
 	if (roleA) {
-		UNR for (int e = 0; e < 10; e++) {
-			const double up = OCT_ILV ? octl_shl<1>(Ic[e]) : oct_dpp<DPP_ROW_SHL + 1>(Ic[e]);
-			Ic[e] += (OCT_ILV || r + 1 < 8) ? up : 0.0;
-		}
-		UNR for (int e = 0; e < 10; e++) {
-			const double up = OCT_ILV ? octl_shl<2>(Ic[e]) : oct_dpp<DPP_ROW_SHL + 2>(Ic[e]);
-			Ic[e] += (OCT_ILV || r + 2 < 8) ? up : 0.0;
-		}
-		UNR for (int e = 0; e < 10; e++) {
-			const double up = OCT_ILV ? octl_shl<4>(Ic[e]) : oct_dpp<DPP_ROW_SHL + 4>(Ic[e]);
-			Ic[e] += (OCT_ILV || r + 4 < 8) ? up : 0.0;
-		}
+		UNR for (int e = 0; e < 10; e++) Ic[e] += octl_shl<1>(Ic[e]);
+		UNR for (int e = 0; e < 10; e++) Ic[e] += octl_shl<2>(Ic[e]);
+		UNR for (int e = 0; e < 10; e++) Ic[e] += octl_shl<4>(Ic[e]);
 	}
 	jf_sync();
 	// ---------------------------------------------------------------- M(q): row r of the lower triangle, M_ir = S_i . (Ic_r S_r), i <= r
@@ -642,14 +633,13 @@ __global__ void __launch_bounds__(DUO ? 128 : 64) saip_cycle_octjf(const CyclePa
 // two wavefronts per group of eight instances while the launch fits the chip in one round (<= 2 workgroups per CU), as in saip_kernel_oct.hip
 hipError_t launch_cycle_octjf(const CycleParams& P, hipStream_t stream) {
 	const dim3 grid((P.B + 7) / 8);
-	static const bool duo_on = getenv("SAIP_OCT_NO_DUO") == nullptr;
 	static int cus = 0;
 	if (cus == 0) {
 		int dev = 0, n = 0;
 		if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
 		cus = n;
 	}
-	if (duo_on && (int)grid.x <= 2 * cus) hipLaunchKernelGGL(saip_cycle_octjf<true>, grid, dim3(128), 0, stream, P);
+	if ((int)grid.x <= 2 * cus) hipLaunchKernelGGL(saip_cycle_octjf<true>, grid, dim3(128), 0, stream, P);
 	else hipLaunchKernelGGL(saip_cycle_octjf<false>, grid, dim3(64), 0, stream, P);
 	return hipGetLastError();
 }

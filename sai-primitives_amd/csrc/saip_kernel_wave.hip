@@ -79,9 +79,6 @@ __device__ __forceinline__ double wv_dot6(const double* S, const double* F) {  /
 	return fma(S[5], F[2], fma(S[4], F[1], fma(S[3], F[0], fma(S[2], F[5], fma(S[1], F[4], S[0] * F[3])))));
 }
 
-#ifndef SAIP_WAVE_OCC
-#define SAIP_WAVE_OCC 2  // wavefronts per SIMD the register allocation aims at (A/B knob of tools/oct_variant.sh)
-#endif
 // JLA: RobotController::enableJointLimitAvoidance.  A separate instantiation because the wrap needs M^-1 once more AFTER the task loop: without it
 // the stored M^-1 (32 registers) is dead as soon as the last task has used it.
 // GENLAW: some motion-force task runs the general control law (velocity saturation, force / moment spaces, closed-loop force control);
@@ -91,7 +88,7 @@ __device__ __forceinline__ double wv_dot6(const double* S, const double* F) {  /
 // BASELINE config 5 -- which runs neither -- spilled its per-joint state at every turn of the law loop and M^-1 / N_prec at the head of the task
 // loop (656 B of scratch per lane, 343 reloads per wavefront: 42 % of its cycles waiting for memory; round 4).
 template <bool JLA, bool GENLAW, bool GENJT>
-__global__ void __launch_bounds__(64, SAIP_WAVE_OCC) saip_cycle_wave(const CycleParams P) {
+__global__ void __launch_bounds__(64, 2) saip_cycle_wave(const CycleParams P) {
 	__shared__ WaveSmem sm;
 	const int b = saip_xcd_block(blockIdx.x, gridDim.x);  // (one instance per workgroup: the instances of an XCD are contiguous, see saip_oct_common.h)
 	if (b >= P.B) return;

@@ -96,7 +96,7 @@ __global__ void saip_reinit_kernel(const CycleParams P) {
 // ---------------------------------------------------------------- host-callable launchers
 hipError_t launch_cycle_wg_list(const CycleParams& P, hipStream_t stream) {
 	// one workgroup per CU.  An empty list (the usual case) still costs a dependent launch: 4.4 - 4.6 us by rocprofv3 whatever the grid (4, 16, 64
-	// or 256 workgroups measured alike, round 3: tools/ab_listgrid.sh) -- the price is the launch, not the 256 scalar loads
+	// or 256 workgroups measured alike, round 3) -- the price is the launch, not the 256 scalar loads
 	const int grid = P.B < 256 ? P.B : 256;
 	if (P.n <= 8) {
 		hipLaunchKernelGGL((saip_cycle_wg_list<8, 64>), dim3(grid), dim3(64), 0, stream, P);
@@ -110,10 +110,8 @@ hipError_t launch_cycle_wg(const CycleParams& P, hipStream_t stream) {
 		hipLaunchKernelGGL((saip_cycle_wg<8, 64>), dim3(P.B), dim3(64), 0, stream, P);
 	} else {
 		// eight wavefronts per instance (two per SIMD: the LDS block allows one workgroup per CU, so the second wavefront of a SIMD is
-		// the only latency hiding there is): 2.33 ms per 4096-instance launch of config 5 against 2.47 ms with four (SAIP_WG_T256=1)
-		static const bool t256 = getenv("SAIP_WG_T256") != nullptr;
-		if (t256) hipLaunchKernelGGL((saip_cycle_wg<32, 256>), dim3(P.B), dim3(256), 0, stream, P);
-		else hipLaunchKernelGGL((saip_cycle_wg<32, 512>), dim3(P.B), dim3(512), 0, stream, P);
+		// the only latency hiding there is): 2.33 ms per 4096-instance launch of config 5 against 2.47 ms with four
+		hipLaunchKernelGGL((saip_cycle_wg<32, 512>), dim3(P.B), dim3(512), 0, stream, P);
 	}
 	return hipGetLastError();
 }

@@ -19,17 +19,13 @@ __device__ __forceinline__ double saip_ldg(const double* p, const size_t i) {
 // here (pivots of SPD factorisations), without the scaling / fix-up sequences of the IEEE division and the library rsqrt
 __device__ __forceinline__ double oct_rcp(const double x) {
 	double y = __builtin_amdgcn_rcp(x);
-#if !defined(SAIP_OCT_EXP_NEWTON1)
 	y = fma(fma(-x, y, 1.0), y, y);
-#endif
 	return fma(fma(-x, y, 1.0), y, y);
 }
 __device__ __forceinline__ double oct_rsqrt(const double x) {
 	double y = __builtin_amdgcn_rsq(x);
 	const double h = 0.5 * x;
-#if !defined(SAIP_OCT_EXP_NEWTON1)
 	y = fma(y, fma(-h * y, y, 0.5), y);
-#endif
 	return fma(y, fma(-h * y, y, 0.5), y);
 }
 
@@ -41,57 +37,36 @@ __device__ __forceinline__ double oct_dpp(const double x) {
 	const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, true);
 	return __hiloint2double(hi, lo);
 }
-enum { DPP_ROW_SHL = 0x100, DPP_ROW_SHR = 0x110, DPP_QUAD_XOR1 = 0xB1, DPP_QUAD_XOR2 = 0x4E, DPP_HALF_MIRROR = 0x141 };
-// sum / maximum over the eight lanes of an instance, every lane gets the same result: pairs and quads by quad permutes, then the
-// other quad of the 8-lane half-row by row_half_mirror (lane i <-> 7 - i)
-__device__ __forceinline__ double oct_group_sum(double x) {
-	x += oct_dpp<DPP_QUAD_XOR1>(x);
-	x += oct_dpp<DPP_QUAD_XOR2>(x);
-	return x + oct_dpp<DPP_HALF_MIRROR>(x);
-}
-__device__ __forceinline__ double oct_group_max(double x) {
-	x = fmax(x, oct_dpp<DPP_QUAD_XOR1>(x));
-	x = fmax(x, oct_dpp<DPP_QUAD_XOR2>(x));
-	return fmax(x, oct_dpp<DPP_HALF_MIRROR>(x));
-}
+enum { DPP_ROW_SHL = 0x100, DPP_ROW_SHR = 0x110, DPP_QUAD_XOR2 = 0x4E, DPP_ROW_ROR = 0x120 };
 
 // Which block of instances a workgroup takes.  The dispatcher is observed to deal workgroups round-robin over the 8 XCDs (workgroups w and w + 8
 // share one; MI355X_MICROARCH.md "Workgroup dispatch, XCD placement"), each with a private L2.  With block = blockIdx, neighbouring blocks -- which
 // share cache lines of every [row][ld] input array (8 instances x 8 B = half a 128-B line per row for the eight-lane kernels, ONE double per row for
 // the wavefront-per-instance kernel) -- sit on different XCDs, and every line is fetched from HBM once per XCD that touches it (measured, round 3 / 4:
 // 2.15 x the algorithmic bytes on config 2, 8 x on config 5).  This bijective remap gives the workgroups of one XCD a contiguous range of blocks.
-// A speed choice only: any other placement reads the same values.  (SAIP_NO_XCD_REMAP: identity, for A/B builds.)
+// A speed choice only: any other placement reads the same values.
 // Used by the wavefront-per-instance kernel only (config 5, same session: 172.7 -> 170.2 us per launch, HBM traffic 65 -> 11 MB against 7.5 MB
 // algorithmic).  The eight-lane kernels were measured with it as well and run on plain blockIdx: their traffic fell as expected (config 2: 4.6 ->
 // 2.7 MB per launch against 2.2 algorithmic) but every launch got SLOWER (config 2 6.67 -> 6.92 us, config 3 13.53 -> 13.85, config 4's shard 9.61 ->
-// 10.02; tools/ab_remap.sh) -- at 4 % of the HBM peak the bytes are not what these kernels wait for, and neighbouring workgroups that miss on the
+// 10.02) -- at 4 % of the HBM peak the bytes are not what these kernels wait for, and neighbouring workgroups that miss on the
 // same line at the same moment queue behind one another in one L2 instead of missing in parallel in two.
 __device__ __forceinline__ int saip_xcd_block(const unsigned orig, const unsigned nwg) {
-#if defined(SAIP_NO_XCD_REMAP)
-	return (int)orig;
-#else
 	const unsigned q = nwg >> 3, r = nwg & 7u, x = orig & 7u;
 	return (int)((x < r ? x * (q + 1u) : r * (q + 1u) + (x - r) * q) + (orig >> 3));
-#endif
 }
 
 // ---------------------------------------------------------------- lane layout
-// Eight lanes per instance, eight instances per wavefront, two instances per 16-lane DPP row.  INTERLEAVED (default): the two instances of a
-// row take its even and its odd lanes (joint r of instance 2 row + parity sits in lane 16 row + 2 r + parity).  Every boundary of a scan along
-// the chain is then a ROW boundary, which DPP handles by itself (bound_ctrl zero fill, or the untouched `old` operand for an identity) --
-// with the two instances side by side (lanes 0-7 / 8-15, SAIP_OCT_ILV=0) every scan step needed a select per moved register: a third of the
-// instructions of the wavefront's longest phase (doubling them cost 4.5 % of the launch, measured).
-#ifndef SAIP_OCT_ILV
-#define SAIP_OCT_ILV 1
-#endif
-constexpr bool OCT_ILV = SAIP_OCT_ILV != 0;
-__device__ __forceinline__ int octl_r(const int lane) { return OCT_ILV ? ((lane >> 1) & 7) : (lane & 7); }
-__device__ __forceinline__ int octl_grp(const int lane) { return OCT_ILV ? (((lane >> 4) << 1) | (lane & 1)) : (lane >> 3); }
+// Eight lanes per instance, eight instances per wavefront, two instances per 16-lane DPP row, INTERLEAVED: the two instances of a row take its
+// even and its odd lanes (joint r of instance 2 row + parity sits in lane 16 row + 2 r + parity).  Every boundary of a scan along the chain is
+// then a ROW boundary, which DPP handles by itself (bound_ctrl zero fill, or the untouched `old` operand for an identity) -- with the two
+// instances side by side (lanes 0-7 / 8-15) every scan step needed a select per moved register: a third of the instructions of the
+// wavefront's longest phase (doubling them cost 4.5 % of the launch, measured).
+__device__ __forceinline__ int octl_r(const int lane) { return (lane >> 1) & 7; }
+__device__ __forceinline__ int octl_grp(const int lane) { return ((lane >> 4) << 1) | (lane & 1); }
 // the lane that holds joint j of this lane's instance
-__device__ __forceinline__ int octl_src(const int lane, const int j) { return OCT_ILV ? ((lane & 0x31) | (j << 1)) : ((lane & ~7) | j); }
+__device__ __forceinline__ int octl_src(const int lane, const int j) { return (lane & 0x31) | (j << 1); }
 // the votes of the eight lanes of this lane's instance, bit r = joint r
 __device__ __forceinline__ unsigned octl_votes(const unsigned long long ballot, const int lane) {
-	if (!OCT_ILV) return (unsigned)((ballot >> ((lane >> 3) * 8)) & 0xffull);
 	unsigned x = (unsigned)((ballot >> (16 * (lane >> 4))) & 0xffffull) >> (lane & 1);  // the row's votes, this instance's on the even bits
 	x &= 0x5555u;
 	x = (x | (x >> 1)) & 0x3333u;
@@ -99,25 +74,20 @@ __device__ __forceinline__ unsigned octl_votes(const unsigned long long ballot, 
 	x = (x | (x >> 4)) & 0x00ffu;
 	return x;
 }
-enum { DPP_ROW_ROR = 0x120 };
 // sum / maximum over the eight lanes of an instance, every lane gets the result (rotations by 4 and 8 inside the row keep the parity)
 __device__ __forceinline__ double octl_sum(double x) {
-	if (!OCT_ILV) return oct_group_sum(x);
 	x += oct_dpp<DPP_QUAD_XOR2>(x);
 	x += oct_dpp<DPP_ROW_ROR + 4>(x);
 	return x + oct_dpp<DPP_ROW_ROR + 8>(x);
 }
 __device__ __forceinline__ double octl_max(double x) {
-	if (!OCT_ILV) return oct_group_max(x);
 	x = fmax(x, oct_dpp<DPP_QUAD_XOR2>(x));
 	x = fmax(x, oct_dpp<DPP_ROW_ROR + 4>(x));
 	return fmax(x, oct_dpp<DPP_ROW_ROR + 8>(x));
 }
 // the three exchange steps of a butterfly over the eight lanes of an instance (arg-max with its index, ...)
-constexpr int OCT_BFLY0 = OCT_ILV ? (int)DPP_QUAD_XOR2 : (int)DPP_QUAD_XOR1, OCT_BFLY1 = OCT_ILV ? DPP_ROW_ROR + 4 : (int)DPP_QUAD_XOR2,
-			  OCT_BFLY2 = OCT_ILV ? DPP_ROW_ROR + 8 : (int)DPP_HALF_MIRROR;
-// value of joint r - D (shr) / r + D (shl) of the same instance; lanes without such a joint get `fill` (0 or 1: the identity's diagonal).
-// Interleaved layout only (the side-by-side layout masks by selects at the call sites).
+constexpr int OCT_BFLY0 = DPP_QUAD_XOR2, OCT_BFLY1 = DPP_ROW_ROR + 4, OCT_BFLY2 = DPP_ROW_ROR + 8;
+// value of joint r - D (shr) / r + D (shl) of the same instance; lanes without such a joint get `fill` (0 or 1: the identity's diagonal)
 template <int D, bool ONE>
 __device__ __forceinline__ double octl_shr(const double x) {
 	const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), DPP_ROW_SHR + 2 * D, 0xF, 0xF, true);
@@ -131,21 +101,17 @@ __device__ __forceinline__ double octl_shl(const double x) {
 	const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), DPP_ROW_SHL + 2 * D, 0xF, 0xF, true);
 	return __hiloint2double(hi, lo);
 }
-// one step of the prefix product of the frames along the chain: T_r <- T_{r-D} o T_r, (Ra,oa) o (Rb,ob) = (Ra Rb, oa + Ra ob)
-#define OCT_FRAME_STEP(D, Tw, r)                                                                                                     \
+// one step of the prefix product of the frames along the chain: T_r <- T_{r-D} o T_r, (Ra,oa) o (Rb,ob) = (Ra Rb, oa + Ra ob); lanes without
+// a predecessor compose with the identity
+#define OCT_FRAME_STEP(D, Tw)                                                                                                        \
 	{                                                                                                                                \
 		double Xa[12], Tn[12];                                                                                                       \
-		if (OCT_ILV) {                                                                                                               \
-			UNR for (int e = 0; e < 12; e++) Xa[e] = (e == 0 || e == 4 || e == 8) ? octl_shr<D, true>(Tw[e]) : octl_shr<D, false>(Tw[e]); \
-		} else {                                                                                                                     \
-			UNR for (int e = 0; e < 12; e++) Xa[e] = oct_dpp<DPP_ROW_SHR + D>(Tw[e]);                                                \
-		}                                                                                                                            \
+		UNR for (int e = 0; e < 12; e++) Xa[e] = (e == 0 || e == 4 || e == 8) ? octl_shr<D, true>(Tw[e]) : octl_shr<D, false>(Tw[e]); \
 		UNR for (int i = 0; i < 3; i++) {                                                                                            \
 			UNR for (int j = 0; j < 3; j++) Tn[3 * i + j] = Xa[3 * i] * Tw[j] + Xa[3 * i + 1] * Tw[3 + j] + Xa[3 * i + 2] * Tw[6 + j];  \
 			Tn[9 + i] = Xa[9 + i] + Xa[3 * i] * Tw[9] + Xa[3 * i + 1] * Tw[10] + Xa[3 * i + 2] * Tw[11];                            \
 		}                                                                                                                            \
-		const bool take = OCT_ILV || r >= D;  /* (interleaved: lanes without a predecessor composed with the identity) */            \
-		UNR for (int e = 0; e < 12; e++) Tw[e] = take ? Tn[e] : Tw[e];                                                               \
+		UNR for (int e = 0; e < 12; e++) Tw[e] = Tn[e];                                                                              \
 	}
 
 

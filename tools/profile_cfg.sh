@@ -5,6 +5,7 @@
 #   2. (pmc = 1) separate rocprofv3 --pmc passes, one counter per run (gpurun refuses PMC together with other tracing)
 #   3. the bench line itself
 # Everything lands under gpurun_out/prof_cfg<C>_<tag>; tools/summarise_cfg.py turns it into the committed profiles/r04_* files.
+# Every GPU step has its own time limit; the first failure (or time-out) ends the script.
 set -e
 CFG=${1:-2}; TAG=${2:-v1}; STEPS=${3:-200}; PMC=${4:-1}
 # counters of the PMC passes (one rocprofv3 run each); override with SAIP_PMC_COUNTERS="A B C"
@@ -14,11 +15,11 @@ BATCH=${SAIP_PROFILE_BATCH:+--batch $SAIP_PROFILE_BATCH}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 WARM=$((STEPS / 10 + 2))
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- python3 bench.py --config $CFG $BATCH --steps $STEPS --warmup $WARM --no-cpu-baseline > $OUT/stats.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- python3 bench.py --config $CFG $BATCH --steps $STEPS --warmup $WARM --no-cpu-baseline > $OUT/stats.log 2>&1
 if [ "$PMC" = "1" ]; then
 	for C in $COUNTERS; do
-		rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_$C -o run -- python3 bench.py --config $CFG $BATCH --steps 20 --warmup 5 --no-cpu-baseline > $OUT/pmc_$C.log 2>&1 || echo "counter $C failed"
+		timeout -k 10 300 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_$C -o run -- python3 bench.py --config $CFG $BATCH --steps 20 --warmup 5 --no-cpu-baseline > $OUT/pmc_$C.log 2>&1
 	done
 fi
-python3 bench.py --config $CFG $BATCH --steps $STEPS --warmup $WARM > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python3 bench.py --config $CFG $BATCH --steps $STEPS --warmup $WARM > $OUT/bench.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.json
