@@ -206,6 +206,50 @@ saip_status saip_batch_rollout_async(saip_batch*, int steps, double sim_dt, int 
 saip_status saip_batch_set_torques_host(saip_batch*, const double* tau);
 /* read the resident state back: q, dq [dof][B] (either may be NULL) */
 saip_status saip_batch_get_state_host(saip_batch*, double* q, double* dq);
+/* ---- robot-model queries: batched SaiModel accessors at the resident state (q, dq as they stand on the device, whoever wrote them:
+ * saip_batch_set_state_host / _device, saip_batch_integrate, saip_batch_rollout_async).  They write their outputs and nothing else: no
+ * task, torque, status, integrator, OTG or singularity-handler state changes.  sai-model is not part of the reference tree; its
+ * semantics below are [RECALLED] unless a reference line is cited.  Call sites: examples/05-using_robot_controller/
+ * 05-using_robot_controller.cpp:69,120-122 (setTRobotBase, positionInWorld, rotationInWorld), examples/03-...cpp:133-134 (position,
+ * rotation), examples/15-...cpp:225-230 (linearVelocityInWorld, angularVelocityInWorld, transformInWorld).
+ * Errors: SAIP_ERR_ORDER before finalize, SAIP_ERR_NO_DEVICE on a configuration-only batch, SAIP_ERR_INVALID_ARGUMENT for a link index
+ * out of range, n_frames outside 1..SAIP_MAX_QUERY_FRAMES, unknown flag bits, a NULL out or links, or dynamics with every output NULL. */
+#define SAIP_MAX_QUERY_FRAMES 8
+enum { SAIP_QUERY_JACOBIAN = 1, SAIP_QUERY_WORLD = 2 };
+/* SaiModel::setTRobotBase / TRobotBase [RECALLED]: T_world_robot of every instance of the batch, R row-major + translation p; identity
+ * by default.  Used ONLY by queries with SAIP_QUERY_WORLD: gravity, g(q), the torques and the integrator stay in the robot base frame
+ * with the model's gravity.  Whether sai-model also rotates gravity by the base cannot be seen in the reference tree; the engine does
+ * not. */
+saip_status saip_batch_set_robot_base(saip_batch*, const double R[9], const double p[3]);
+saip_status saip_batch_get_robot_base(const saip_batch*, double R[9], double p[3]);
+/* rows written per frame by saip_batch_model_frames_*: 18, or 18 + 6 * dof with SAIP_QUERY_JACOBIAN (0 for a NULL batch or bad flags) */
+int saip_batch_model_frame_rows(const saip_batch*, int flags);
+/* Kinematics of n_frames frames (link, point fixed in the link) at the resident state, in the robot base frame:
+ *   rows  0..2   SaiModel::position(link, pos_in_link)           3..11  rotation(link), row-major
+ *   rows 12..14  linearVelocity(link, pos_in_link)               15..17 angularVelocity(link)
+ *   rows 18..    J(link, pos_in_link) = [Jv; Jw], 6 x dof row-major (SAIP_QUERY_JACOBIAN; the [Jv; Jw] order of MotionForceTask.cpp:293-298)
+ * SAIP_QUERY_WORLD maps every row through T_world_robot: the *InWorld accessors (positionInWorld, rotationInWorld, linearVelocityInWorld,
+ * angularVelocityInWorld, JWorldFrame [RECALLED]): positions -> R_wb x + p_wb, rotations -> R_wb R, every other 3-vector -> R_wb v.
+ * links: saip_model_link_index values; links welded to a movable body compose their fixed transform as tasks on them do; a link welded
+ * to the fixed base has a constant pose, zero twist and an all-zero Jacobian.  pos_in_link: [n_frames][3], NULL = all zero.  A frame
+ * equal to a task's control frame (identity compliant rotation) gives rows 0..11 bit-identical to saip_batch_get_current_pose_host.
+ * _host: out = [n_frames][rows][B], synchronous.  _device: out_dev = [n_frames][rows][ld] device memory, asynchronous on the batch stream. */
+saip_status saip_batch_model_frames_host(saip_batch*, int n_frames, const int* links, const double* pos_in_link, int flags, double* out);
+saip_status saip_batch_model_frames_device(saip_batch*, int n_frames, const int* links, const double* pos_in_link, int flags, double* out_dev);
+/* Joint-space dynamics at the resident state; any output may be NULL (that quantity is skipped, not computed):
+ *   M     = SaiModel::M()                [dof*dof] row-major per instance (composite rigid bodies)
+ *   M_inv = SaiModel::MInv()             [dof*dof] (from the Cholesky factor of M)
+ *   g     = SaiModel::jointGravityVector(): what gravity compensation adds to the torques (RobotController.cpp:114-115), model gravity
+ *           in the robot base frame   [dof]
+ *   b     = SaiModel::coriolisForce(): C(q, dq) dq, so that M qdd + b + g = tau (the convention of saip_batch_integrate)   [dof]
+ * _host: [..][B], synchronous.  _device: [..][ld] device pointers, asynchronous on the batch stream. */
+saip_status saip_batch_model_dynamics_host(saip_batch*, double* M, double* M_inv, double* g, double* b);
+saip_status saip_batch_model_dynamics_device(saip_batch*, double* M_dev, double* M_inv_dev, double* g_dev, double* b_dev);
+/* finalize a batch with NO tasks that only mirrors a robot's state for the model queries (SaiModel::updateModel).  Allowed afterwards:
+ * the state setters and getters, saip_batch_synchronize / _wait_for, the robot base, the model queries, saip_batch_ld / _size / _dof /
+ * _stream and saip_batch_device_q / _dq.  Every entry that needs a task or a controller returns SAIP_ERR_ORDER: cycle, step, per-task,
+ * rollout, integrate, timing, gather.  saip_batch_finalize itself still refuses a batch with no tasks. */
+saip_status saip_batch_finalize_model_only(saip_batch*);
 /* getDesiredPosition/Velocity/Acceleration (JointTask.h:185-200; MotionForceTask desired* likewise): [goal_components][B] in the
  * goal layout -- the internal OTG's output of the last cycle when it is enabled, otherwise the goal itself. */
 saip_status saip_batch_get_desired_host(saip_batch*, int task, double* desired);

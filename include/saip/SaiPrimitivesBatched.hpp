@@ -18,6 +18,7 @@
 // Errors: std::invalid_argument where the reference throws it; std::runtime_error for device / unsupported / order errors.
 // Every array is struct-of-arrays, component-major: value of component c for instance b at [c * B + b].
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <functional>
 #include <memory>
@@ -60,7 +61,10 @@ public:
 		_q.assign((size_t)dof() * _batch, 0.0);
 		_dq.assign((size_t)dof() * _batch, 0.0);
 	}
-	~SaiModel() { saip_model_destroy(_model); }
+	~SaiModel() {
+		if (_mq) saip_batch_destroy(_mq);  // the query batch refers to the model: it goes first
+		saip_model_destroy(_model);
+	}
 	SaiModel(const SaiModel&) = delete;
 	SaiModel& operator=(const SaiModel&) = delete;
 
@@ -82,8 +86,56 @@ public:
 	// pushes the state to every batch that mirrors this robot (the RobotController's and the private batches of tasks driven by hand)
 	void updateModel() {
 		for (auto& a : _attached) push(a);
+		_mq_q = _q;
+		_mq_dq = _dq;
+		_mq_version++;
+		if (_mq) pushQueryState();
 	}
 	const saip_model* handle() const { return _model; }
+	int linkIndex(const std::string& link) const {
+		const int i = saip_model_link_index(_model, link.c_str());
+		if (i < 0) throw std::invalid_argument("link " + link + " does not exist in the robot model");
+		return i;
+	}
+
+	// ---- model queries: the sai-model accessors at the state of the last updateModel() (saip_batch_model_frames_host /
+	// saip_batch_model_dynamics_host on a model-only batch of this robot, created at the first query).  Results in the [c*B + b] layout.
+	std::vector<double> position(const std::string& link, const double* pos_in_link = nullptr) { return frameRows(link, pos_in_link, 0, 0, 3); }
+	std::vector<double> rotation(const std::string& link) { return frameRows(link, nullptr, 0, 3, 9); }
+	std::vector<double> transform(const std::string& link, const double* pos_in_link = nullptr) { return toTransform(frameRows(link, pos_in_link, 0, 0, 12)); }
+	std::vector<double> linearVelocity(const std::string& link, const double* pos_in_link = nullptr) { return frameRows(link, pos_in_link, 0, 12, 3); }
+	std::vector<double> angularVelocity(const std::string& link) { return frameRows(link, nullptr, 0, 15, 3); }
+	std::vector<double> J(const std::string& link, const double* pos_in_link = nullptr) { return frameRows(link, pos_in_link, SAIP_QUERY_JACOBIAN, 18, 6 * dof()); }
+	std::vector<double> Jv(const std::string& link, const double* pos_in_link = nullptr) { return frameRows(link, pos_in_link, SAIP_QUERY_JACOBIAN, 18, 3 * dof()); }
+	std::vector<double> Jw(const std::string& link) { return frameRows(link, nullptr, SAIP_QUERY_JACOBIAN, 18 + 3 * dof(), 3 * dof()); }
+	std::vector<double> positionInWorld(const std::string& link, const double* pos_in_link = nullptr) { return frameRows(link, pos_in_link, SAIP_QUERY_WORLD, 0, 3); }
+	std::vector<double> rotationInWorld(const std::string& link) { return frameRows(link, nullptr, SAIP_QUERY_WORLD, 3, 9); }
+	std::vector<double> transformInWorld(const std::string& link, const double* pos_in_link = nullptr) {
+		return toTransform(frameRows(link, pos_in_link, SAIP_QUERY_WORLD, 0, 12));
+	}
+	std::vector<double> linearVelocityInWorld(const std::string& link, const double* pos_in_link = nullptr) {
+		return frameRows(link, pos_in_link, SAIP_QUERY_WORLD, 12, 3);
+	}
+	std::vector<double> angularVelocityInWorld(const std::string& link) { return frameRows(link, nullptr, SAIP_QUERY_WORLD, 15, 3); }
+	std::vector<double> JWorldFrame(const std::string& link, const double* pos_in_link = nullptr) {
+		return frameRows(link, pos_in_link, SAIP_QUERY_JACOBIAN | SAIP_QUERY_WORLD, 18, 6 * dof());
+	}
+	// SaiModel::setTRobotBase: T_world_robot (R row-major, p), the same for every instance; reaches every batch of this robot.  Only the
+	// *InWorld queries use it: gravity and the torques stay in the robot base frame (saip.h)
+	void setTRobotBase(const double R[9], const double p[3]) {
+		for (auto& a : _attached) check(saip_batch_set_robot_base(a.batch, R, p));
+		if (_mq) check(saip_batch_set_robot_base(_mq, R, p));
+		std::copy(R, R + 9, _Rb);
+		std::copy(p, p + 3, _pb);
+	}
+	void TRobotBase(double R[9], double p[3]) const {
+		std::copy(_Rb, _Rb + 9, R);
+		std::copy(_pb, _pb + 3, p);
+	}
+	std::vector<double> M() { return dynamics(0); }
+	std::vector<double> MInv() { return dynamics(1); }
+	std::vector<double> jointGravityVector() { return dynamics(2); }
+	std::vector<double> coriolisForce() { return dynamics(3); }
 
 private:
 	friend class RobotController;
@@ -92,7 +144,65 @@ private:
 		saip_batch* batch;
 		long pushed;
 	};
-	void attach(saip_batch* b) { _attached.push_back({b, -1}); }
+	void attach(saip_batch* b) {
+		_attached.push_back({b, -1});
+		check(saip_batch_set_robot_base(b, _Rb, _pb));
+	}
+	saip_batch* queryBatch() {
+		if (!_mq) {
+			saip_batch* b = nullptr;
+			check(saip_batch_create(_model, _batch, _device, &b));
+			saip_status st = saip_batch_finalize_model_only(b);
+			if (st == SAIP_OK) st = saip_batch_set_robot_base(b, _Rb, _pb);
+			if (st != SAIP_OK) {
+				saip_batch_destroy(b);
+				check(st);
+			}
+			_mq = b;
+		}
+		pushQueryState();
+		return _mq;
+	}
+	void pushQueryState() {
+		if (_device < 0 || _mq_pushed == _mq_version) return;
+		if (_mq_q.empty()) {
+			_mq_q.assign(_q.size(), 0.0);
+			_mq_dq.assign(_dq.size(), 0.0);
+		}
+		check(saip_batch_set_state_host(_mq, _mq_q.data(), _mq_dq.data()));
+		_mq_pushed = _mq_version;
+	}
+	// rows [first, first + count) of one frame
+	std::vector<double> frameRows(const std::string& link, const double* pos_in_link, int flags, int first, int count) {
+		saip_batch* b = queryBatch();
+		const int li = linkIndex(link);
+		const int rows = saip_batch_model_frame_rows(b, flags);
+		std::vector<double> out((size_t)rows * _batch);
+		check(saip_batch_model_frames_host(b, 1, &li, pos_in_link, flags, out.data()));
+		return std::vector<double>(out.begin() + (size_t)first * _batch, out.begin() + (size_t)(first + count) * _batch);
+	}
+	// rows 0..11 (position, rotation) -> [16][B] row-major 4 x 4
+	std::vector<double> toTransform(const std::vector<double>& r) const {
+		std::vector<double> T((size_t)16 * _batch, 0.0);
+		for (int b = 0; b < _batch; b++) {
+			for (int i = 0; i < 3; i++) {
+				for (int j = 0; j < 3; j++) T[(size_t)(4 * i + j) * _batch + b] = r[(size_t)(3 + 3 * i + j) * _batch + b];
+				T[(size_t)(4 * i + 3) * _batch + b] = r[(size_t)i * _batch + b];
+			}
+			T[(size_t)15 * _batch + b] = 1.0;
+		}
+		return T;
+	}
+	// 0 M, 1 M^-1, 2 g, 3 b
+	std::vector<double> dynamics(int which) {
+		saip_batch* b = queryBatch();
+		const size_t n = dof();
+		std::vector<double> out((which < 2 ? n * n : n) * _batch);
+		double* p[4] = {nullptr, nullptr, nullptr, nullptr};
+		p[which] = out.data();
+		check(saip_batch_model_dynamics_host(b, p[0], p[1], p[2], p[3]));
+		return out;
+	}
 	void detach(saip_batch* b) {
 		for (size_t i = 0; i < _attached.size(); i++)
 			if (_attached[i].batch == b) {
@@ -115,6 +225,10 @@ private:
 	std::vector<double> _q, _dq;
 	long _version = 0;
 	std::vector<Attached> _attached;
+	saip_batch* _mq = nullptr;  // model-only batch of the queries
+	std::vector<double> _mq_q, _mq_dq;  // the state of the last updateModel()
+	long _mq_version = 0, _mq_pushed = -1;
+	double _Rb[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, _pb[3] = {0, 0, 0};
 };
 
 // TemplateTask.h:26-124

@@ -6,6 +6,7 @@ reference's task/controller interface in a batched flavour (`SaiModel`, `MotionF
 tasks/MotionForceTask.h, tasks/JointTask.h).  All arithmetic happens in the HIP kernels of csrc/;
 there is no CPU path: without the built library or without a GPU every compute call raises.
 """
-from .capi import lib, build_library, SaipError, SaipUnsupported, SaipNoDevice, device_count  # noqa: F401
+from .capi import (lib, build_library, SaipError, SaipUnsupported, SaipNoDevice, device_count,  # noqa: F401
+                   SAIP_MAX_QUERY_FRAMES, SAIP_QUERY_JACOBIAN, SAIP_QUERY_WORLD)
 from .controller import (SaiModel, MotionForceTask, JointTask, RobotController, TaskType,  # noqa: F401
                          DynamicDecouplingType, PIDGains, load_robot_description)

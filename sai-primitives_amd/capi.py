@@ -7,10 +7,12 @@ import subprocess
 
 _DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_DIR, "libsaip.so")
-SOURCES = ["csrc/saip_engine.cpp", "csrc/saip_comm.cpp", "csrc/saip_kernel_wg.hip", "csrc/saip_kernel_lane.hip", "csrc/saip_kernel_lane_lean.hip", "csrc/saip_kernel_oct.hip", "csrc/saip_kernel_octjf.hip", "csrc/saip_kernel_wave.hip", "csrc/saip_otg.hip", "csrc/saip_dynamics.hip", "csrc/saip_dynamics_oct.hip", "csrc/saip_task_diag.hip"]
-HEADERS = ["csrc/saip_device.h", "csrc/saip_law.h", "csrc/saip_wg_linalg.h", "csrc/saip_wg_cycle.h", "csrc/saip_fk.h", "csrc/saip_oct_common.h", "csrc/saip_wave_prims.h", "csrc/saip_dynamics_oct_body.h", "csrc/saip_otg3.h", "csrc/saip_otg3_step1.h", "csrc/saip_otg3_step2.h", "../include/saip.h"]
+SOURCES = ["csrc/saip_engine.cpp", "csrc/saip_comm.cpp", "csrc/saip_kernel_wg.hip", "csrc/saip_kernel_lane.hip", "csrc/saip_kernel_lane_lean.hip", "csrc/saip_kernel_oct.hip", "csrc/saip_kernel_octjf.hip", "csrc/saip_kernel_wave.hip", "csrc/saip_otg.hip", "csrc/saip_dynamics.hip", "csrc/saip_dynamics_oct.hip", "csrc/saip_task_diag.hip", "csrc/saip_model_query.hip"]
+HEADERS = ["csrc/saip_device.h", "csrc/saip_law.h", "csrc/saip_wg_linalg.h", "csrc/saip_wg_cycle.h", "csrc/saip_fk.h", "csrc/saip_oct_common.h", "csrc/saip_wave_prims.h", "csrc/saip_dynamics_oct_body.h", "csrc/saip_otg3.h", "csrc/saip_otg3_step1.h", "csrc/saip_otg3_step2.h", "csrc/saip_rbd.h", "../include/saip.h"]
 
 SAIP_OK, SAIP_ERR_INVALID_ARGUMENT, SAIP_ERR_UNSUPPORTED, SAIP_ERR_NO_DEVICE, SAIP_ERR_DEVICE, SAIP_ERR_ORDER = range(6)
+SAIP_MAX_QUERY_FRAMES = 8
+SAIP_QUERY_JACOBIAN, SAIP_QUERY_WORLD = 1, 2
 NAME_LEN = 48
 
 
@@ -133,6 +135,14 @@ def lib():
         "saip_batch_get_current_pose_host": (C.c_int, [vp, C.c_int, dp, dp]),
         "saip_batch_get_task_diagnostics_host": (C.c_int, [vp, C.c_int, dp]),
         "saip_batch_task_diagnostics_device": (C.c_int, [vp, C.c_int, vp]),
+        "saip_batch_set_robot_base": (C.c_int, [vp, dp, dp]),
+        "saip_batch_get_robot_base": (C.c_int, [vp, dp, dp]),
+        "saip_batch_model_frame_rows": (C.c_int, [vp, C.c_int]),
+        "saip_batch_model_frames_host": (C.c_int, [vp, C.c_int, ip, dp, C.c_int, dp]),
+        "saip_batch_model_frames_device": (C.c_int, [vp, C.c_int, ip, dp, C.c_int, vp]),
+        "saip_batch_model_dynamics_host": (C.c_int, [vp, dp, dp, dp, dp]),
+        "saip_batch_model_dynamics_device": (C.c_int, [vp, vp, vp, vp, vp]),
+        "saip_batch_finalize_model_only": (C.c_int, [vp]),
         "saip_batch_reset_integrators": (C.c_int, [vp, C.c_int, C.c_int]),
         "saip_batch_set_singularity_gains": (C.c_int, [vp, C.c_int, C.c_double, C.c_double, C.c_double]),
         "saip_batch_set_all_singularities_type1": (C.c_int, [vp, C.c_int, C.c_int]),

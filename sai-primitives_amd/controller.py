@@ -110,8 +110,18 @@ class SaiModel:
         # the robot's state at every updateModel()
         self._controllers = weakref.WeakSet()
         self._state_version = 0
+        # model queries (position(), J(), M(), ...): the state of the last updateModel(), mirrored into a batch of their own (created at
+        # the first query, pushed to at every updateModel(); a setQ() that no updateModel() followed is never seen), and T_world_robot
+        self._model_q, self._model_dq = self._q.copy(), self._dq.copy()
+        self._model_version = 0
+        self._mq = None
+        self._mq_version = -1
+        self._T_base = np.eye(4)
 
     def __del__(self):
+        if getattr(self, "_mq", None):  # the query batch refers to the model: it goes first
+            capi.lib().saip_batch_destroy(self._mq)
+            self._mq = None
         if getattr(self, "_h", None):
             capi.lib().saip_model_destroy(self._h)
             self._h = None
@@ -140,9 +150,14 @@ class SaiModel:
         self._state_version += 1
 
     def updateModel(self):
-        """pushes q/dq to the device; kinematics and dynamics are evaluated inside the cycle kernel"""
+        """pushes q/dq to the device; kinematics and dynamics are evaluated inside the cycle kernel.  The model queries below answer for
+        this state until the next updateModel()."""
         for c in list(self._controllers):
             c._push_state()
+        self._model_q, self._model_dq = self._q.copy(), self._dq.copy()
+        self._model_version += 1
+        if self._mq is not None:
+            self._push_model_state()
 
     def jointLimits(self):
         n = self._n
@@ -152,6 +167,212 @@ class SaiModel:
 
     def linkIndex(self, name: str) -> int:
         return capi.lib().saip_model_link_index(self._h, name.encode())
+
+    # -- model queries: the SaiModel accessors at the state of the last updateModel() (C-ABI saip_batch_model_frames_host /
+    # saip_batch_model_dynamics_host on a model-only batch).  Links by name or by linkIndex() value.
+    def _link(self, link) -> int:
+        if isinstance(link, str):
+            i = self.linkIndex(link)
+            if i < 0:
+                raise ValueError(f"link {link} does not exist in the robot model")
+            return i
+        return int(link)
+
+    def _push_model_state(self):
+        if self.device >= 0 and self._mq_version != self._model_version:
+            q, dq = np.ascontiguousarray(self._model_q.T), np.ascontiguousarray(self._model_dq.T)
+            capi.check(capi.lib().saip_batch_set_state_host(self._mq, _dptr(q), _dptr(dq)))
+            self._mq_version = self._model_version
+
+    def _query_batch(self):
+        if self._mq is None:
+            L = capi.lib()
+            h = C.c_void_p()
+            capi.check(L.saip_batch_create(self._h, self.batch_size, self.device, C.byref(h)))
+            try:
+                capi.check(L.saip_batch_finalize_model_only(h))
+                _set_base(h, self._T_base)
+            except Exception:
+                L.saip_batch_destroy(h)
+                raise
+            self._mq = h
+        self._push_model_state()
+        return self._mq
+
+    def _frames(self, frames, flags):
+        """frames: [(link, pos_in_link)] -> (n_frames, rows, B) as saip_batch_model_frames_host writes it"""
+        return _model_frames(self._query_batch(), self, frames, flags)
+
+    def _frame(self, link, pos, world, jacobian=False):
+        flags = (capi.SAIP_QUERY_WORLD if world else 0) | (capi.SAIP_QUERY_JACOBIAN if jacobian else 0)
+        return self._frames([(link, pos)], flags)[0]
+
+    def position(self, link, pos_in_link=(0.0, 0.0, 0.0)):
+        """(B, 3) SaiModel::position: the point pos_in_link of the link in the robot base frame"""
+        return self._frame(link, pos_in_link, False)[0:3].T.copy()
+
+    def rotation(self, link):
+        """(B, 3, 3) SaiModel::rotation: orientation of the link in the robot base frame"""
+        return self._frame(link, None, False)[3:12].T.reshape(-1, 3, 3).copy()
+
+    def _transform(self, link, pos, world):
+        r = self._frame(link, pos, world)
+        T = np.zeros((self.batch_size, 4, 4))
+        T[:, :3, :3] = r[3:12].T.reshape(-1, 3, 3)
+        T[:, :3, 3] = r[0:3].T
+        T[:, 3, 3] = 1.0
+        return T
+
+    def transform(self, link, pos_in_link=(0.0, 0.0, 0.0)):
+        """(B, 4, 4) SaiModel::transform: pose of the frame (link, pos_in_link) in the robot base frame"""
+        return self._transform(link, pos_in_link, False)
+
+    def linearVelocity(self, link, pos_in_link=(0.0, 0.0, 0.0)):
+        """(B, 3) SaiModel::linearVelocity of the point pos_in_link of the link, robot base frame"""
+        return self._frame(link, pos_in_link, False)[12:15].T.copy()
+
+    def angularVelocity(self, link):
+        """(B, 3) SaiModel::angularVelocity of the link, robot base frame"""
+        return self._frame(link, None, False)[15:18].T.copy()
+
+    def _jac(self, link, pos, world):
+        return self._frame(link, pos, world, jacobian=True)[18:].T.reshape(self.batch_size, 6, self._n).copy()
+
+    def J(self, link, pos_in_link=(0.0, 0.0, 0.0)):
+        """(B, 6, dof) SaiModel::J = [Jv; Jw] of the point pos_in_link of the link, robot base frame"""
+        return self._jac(link, pos_in_link, False)
+
+    def Jv(self, link, pos_in_link=(0.0, 0.0, 0.0)):
+        """(B, 3, dof) SaiModel::Jv"""
+        return self._jac(link, pos_in_link, False)[:, :3].copy()
+
+    def Jw(self, link):
+        """(B, 3, dof) SaiModel::Jw"""
+        return self._jac(link, None, False)[:, 3:].copy()
+
+    def positionInWorld(self, link, pos_in_link=(0.0, 0.0, 0.0)):
+        """(B, 3) SaiModel::positionInWorld: position() mapped through TRobotBase()"""
+        return self._frame(link, pos_in_link, True)[0:3].T.copy()
+
+    def rotationInWorld(self, link):
+        """(B, 3, 3) SaiModel::rotationInWorld"""
+        return self._frame(link, None, True)[3:12].T.reshape(-1, 3, 3).copy()
+
+    def transformInWorld(self, link, pos_in_link=(0.0, 0.0, 0.0)):
+        """(B, 4, 4) SaiModel::transformInWorld"""
+        return self._transform(link, pos_in_link, True)
+
+    def linearVelocityInWorld(self, link, pos_in_link=(0.0, 0.0, 0.0)):
+        """(B, 3) SaiModel::linearVelocityInWorld"""
+        return self._frame(link, pos_in_link, True)[12:15].T.copy()
+
+    def angularVelocityInWorld(self, link):
+        """(B, 3) SaiModel::angularVelocityInWorld"""
+        return self._frame(link, None, True)[15:18].T.copy()
+
+    def JWorldFrame(self, link, pos_in_link=(0.0, 0.0, 0.0)):
+        """(B, 6, dof) SaiModel::JWorldFrame: J() with both blocks rotated into the world frame"""
+        return self._jac(link, pos_in_link, True)
+
+    def JvWorldFrame(self, link, pos_in_link=(0.0, 0.0, 0.0)):
+        """(B, 3, dof) SaiModel::JvWorldFrame"""
+        return self._jac(link, pos_in_link, True)[:, :3].copy()
+
+    def JwWorldFrame(self, link):
+        """(B, 3, dof) SaiModel::JwWorldFrame"""
+        return self._jac(link, None, True)[:, 3:].copy()
+
+    def setTRobotBase(self, T):
+        """SaiModel::setTRobotBase: (4, 4) T_world_robot, the same for every instance.  It reaches the world-frame queries of every batch
+        of this robot; gravity, jointGravityVector() and every torque stay in the robot base frame (include/saip.h)"""
+        T = np.array(T, dtype=float)
+        if T.shape != (4, 4):
+            raise ValueError("setTRobotBase: expected a 4 x 4 homogeneous transform")
+        for h in [self._mq] + [c._h for c in list(self._controllers)]:
+            if h:
+                _set_base(h, T)
+        self._T_base = T
+
+    def TRobotBase(self):
+        """(4, 4) SaiModel::TRobotBase"""
+        return self._T_base.copy()
+
+    def _dynamics(self, which):
+        return _model_dynamics(self._query_batch(), self, which)
+
+    def M(self):
+        """(B, dof, dof) SaiModel::M: joint-space mass matrix"""
+        return self._dynamics(("M",))["M"]
+
+    def MInv(self):
+        """(B, dof, dof) SaiModel::MInv"""
+        return self._dynamics(("M_inv",))["M_inv"]
+
+    def jointGravityVector(self):
+        """(B, dof) SaiModel::jointGravityVector: what gravity compensation adds to the torques (model gravity, robot base frame)"""
+        return self._dynamics(("g",))["g"]
+
+    def coriolisForce(self):
+        """(B, dof) SaiModel::coriolisForce: C(q, dq) dq, so that M qdd + b + g = tau"""
+        return self._dynamics(("b",))["b"]
+
+
+def _set_base(h, T):
+    R = np.ascontiguousarray(T[:3, :3], dtype=float)
+    p = np.ascontiguousarray(T[:3, 3], dtype=float)
+    capi.check(capi.lib().saip_batch_set_robot_base(h, _dptr(R), _dptr(p)))
+
+
+def _frame_args(robot, frames):
+    """[(link, pos_in_link or None)] or [link] -> (n, int32 link array, float64 [n][3] positions)"""
+    frames = [f if isinstance(f, tuple) else (f, None) for f in frames]
+    links = np.array([robot._link(l) for l, _ in frames], dtype=np.int32)
+    pos = np.array([np.zeros(3) if p is None else np.asarray(p, float).reshape(3) for _, p in frames], dtype=float)
+    return len(frames), links, np.ascontiguousarray(pos)
+
+
+def _model_frames(h, robot, frames, flags, out=None):
+    """host: (n_frames, rows, B); device (out = tensor of shape (n_frames, rows, ld) or pointer): enqueued on the batch stream"""
+    L = capi.lib()
+    nf, links, pos = _frame_args(robot, frames)
+    lp = links.ctypes.data_as(C.POINTER(C.c_int))
+    rows = L.saip_batch_model_frame_rows(h, int(flags))
+    if out is None:
+        res = np.empty((nf, max(rows, 1), robot.batch_size))
+        capi.check(L.saip_batch_model_frames_host(h, nf, lp, _dptr(pos), int(flags), _dptr(res)))
+        return res
+    ptr = _device_ptr(out, (nf, rows, L.saip_batch_ld(h)), "getModelFrames")
+    capi.check(L.saip_batch_model_frames_device(h, nf, lp, _dptr(pos), int(flags), C.c_void_p(ptr)))
+    return out
+
+
+_DYN_KEYS = ("M", "M_inv", "g", "b")
+
+
+def _model_dynamics(h, robot, which, out=None):
+    """host: dict of the requested quantities, (B, dof, dof) / (B, dof); device (out = {key: tensor (rows, ld) or pointer}): enqueued"""
+    L = capi.lib()
+    n, B = robot.dof(), robot.batch_size
+    rows = {"M": n * n, "M_inv": n * n, "g": n, "b": n}
+    if out is not None:
+        bad = set(out) - set(_DYN_KEYS)
+        if bad:
+            raise ValueError(f"getModelDynamics: unknown outputs {sorted(bad)} (expected some of {_DYN_KEYS})")
+        ld = L.saip_batch_ld(h)
+        ptrs = [C.c_void_p(_device_ptr(out[k], (rows[k], ld), "getModelDynamics")) if k in out else None for k in _DYN_KEYS]
+        capi.check(L.saip_batch_model_dynamics_device(h, *ptrs))
+        return out
+    host = {k: np.empty((rows[k], B)) for k in which}
+    capi.check(L.saip_batch_model_dynamics_host(h, *[_dptr(host[k]) if k in host else None for k in _DYN_KEYS]))
+    return {k: (v.T.reshape(B, n, n) if rows[k] == n * n else v.T).copy() for k, v in host.items()}
+
+
+def _device_ptr(out, shape, who):
+    if isinstance(out, int):
+        return out
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous() or str(out.dtype) != "torch.float64":
+        raise ValueError(f"{who}: expected a contiguous float64 device tensor of shape {tuple(shape)}")
+    return out.data_ptr()
 
 
 class _Task:
@@ -959,6 +1180,7 @@ class RobotController:
         if not _private:
             robot._controller = self
         robot._controllers.add(self)
+        _set_base(h, robot._T_base)
         self._pushed_version = -1
         self._has_device = robot.device >= 0
 
@@ -1086,6 +1308,20 @@ class RobotController:
         """overwrite the resident torques the next integrate() applies: (B, dof)"""
         a = _soa(np.asarray(tau, float), self.batch_size, self._robot.dof(), "torques")
         self._call("saip_batch_set_torques_host", _dptr(a))
+
+    # -- robot-model queries at the RESIDENT state (what integrate() / rolloutAsync() left on the device, or the state last pushed)
+    def getModelFrames(self, frames, jacobian=False, world=False, out=None):
+        """kinematics of up to 8 frames in one launch: frames = [link or (link, pos_in_link)], links by name or index.  Returns
+        (n_frames, rows, B): rows 0-2 position, 3-11 rotation (row-major), 12-14 linear velocity, 15-17 angular velocity, then with
+        jacobian the 6 x dof [Jv; Jw] row-major; robot base frame, or through TRobotBase() with world.  out: a contiguous float64
+        device tensor of shape (n_frames, rows, ld) or a raw device pointer: written asynchronously on the batch stream"""
+        flags = (capi.SAIP_QUERY_JACOBIAN if jacobian else 0) | (capi.SAIP_QUERY_WORLD if world else 0)
+        return _model_frames(self._h, self._robot, frames, flags, out)
+
+    def getModelDynamics(self, out=None):
+        """M, M_inv (B, dof, dof), g, b (B, dof) at the resident state: dict.  out: {key: device tensor of shape (dof*dof or dof, ld) or
+        pointer} for any of the keys "M", "M_inv", "g", "b" (the others are not computed), written asynchronously on the batch stream"""
+        return _model_dynamics(self._h, self._robot, _DYN_KEYS, out)
 
     def pullState(self):
         """read the resident state back into the SaiModel mirror (after integrate / rolloutAsync); returns (q, dq) (B, dof)"""

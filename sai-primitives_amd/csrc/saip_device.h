@@ -169,6 +169,33 @@ struct SimParams {
 	double* ddq;           // optional [n][ld] joint accelerations of the last substep
 };
 
+// robot-model queries (saip_model_query.hip).  Passed to the kernels by value.
+enum { SAIP_MAXQF = 8 };         // = SAIP_MAX_QUERY_FRAMES
+struct FrameQuery {
+	int B, ld, n, nf;
+	int rows;                    // rows per frame: 18, or 18 + 6n with the Jacobian
+	int jac, world, pad_;
+	int body[SAIP_MAXQF];        // movable body of each frame, ascending (-1: welded to the fixed base)
+	int slot[SAIP_MAXQF];        // output block of each frame (the caller's order)
+	double pos[SAIP_MAXQF][3];   // frame origin in its body frame (the link's fixed transform composed)
+	double rot[SAIP_MAXQF][9];   // frame rotation in its body frame, row-major
+	double Rwb[9], pwb[3];       // T_world_robot (world = 1)
+	const ModelDev* model;
+	const double* q;             // [n][ld]
+	const double* dq;            // [n][ld]
+	double* out;                 // [nf][rows][ld]
+};
+struct DynQuery {
+	int B, ld, n, pad_;
+	const ModelDev* model;
+	const double* q;             // [n][ld]
+	const double* dq;            // [n][ld]
+	double* M;                   // [n*n][ld] or nullptr (skipped)
+	double* Minv;                // [n*n][ld] or nullptr
+	double* g;                   // [n][ld] or nullptr
+	double* h;                   // [n][ld] or nullptr: C(q, dq) dq
+};
+
 // Internal OTG of one joint task (saip_otg.hip).  Passed to the kernel by value.
 enum { OTG_FLAG_GOAL_REACHED = 1, OTG_FLAG_RUCKIG_INIT = 2, OTG_FLAG_STATE_VALID = 4, OTG_FLAG_ERROR = 8, OTG_FLAG_FINISHED_MOVING = 16,
 	   OTG_FLAG_GOAL_ORI_VALID = 32, OTG_FLAG_INVALID_GOAL = 64 };

@@ -39,39 +39,43 @@ __device__ __forceinline__ void fk_mat3_vec(const double* R, const double* v, do
 // whose knife-edge decisions (collinearity within 2^-52) are compared against reference fixtures generated with the same arithmetic.
 // A macro rather than a function so that fk_control_frame, which the general cycle kernel and the OTG inline, compiles to exactly the
 // code it compiled to before the task diagnostics (saip_task_diag.hip) began to share it.
-#define SAIP_FK_WALK(...) \
-	double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};                                                                                   \
-	for (int j = 0; j <= tk.body; j++) {                                                                                                           \
-		double t3[3], Rn[9], Rt[9];                                                                                                                \
-		fk_mat3_vec(R, md.p0[j], t3);                                                                                                              \
-		for (int e = 0; e < 3; e++) o[e] += t3[e];                                                                                                 \
-		for (int r = 0; r < 3; r++)                                                                                                                \
-			for (int c = 0; c < 3; c++) Rt[3 * r + c] = R[3 * r] * md.R0[j][c] + R[3 * r + 1] * md.R0[j][3 + c] + R[3 * r + 2] * md.R0[j][6 + c];  \
-		const double qj = q[(size_t)j * ld + b];                                                                                                   \
-		const double ax = md.axis[j][0], ay = md.axis[j][1], az = md.axis[j][2];                                                                   \
-		__VA_ARGS__                                                                                                                                \
-		if (md.jtype[j] == 1) {                                                                                                                    \
-			double s, c;                                                                                                                           \
-			sincos(qj, &s, &c);  /* library sin/cos on purpose: see above */                                                                       \
-			const double v = 1.0 - c;                                                                                                              \
-			const double Rq[9] = {c + ax * ax * v,      ax * ay * v - az * s, ax * az * v + ay * s,                                                \
-								  ay * ax * v + az * s, c + ay * ay * v,      ay * az * v - ax * s,                                                \
-								  az * ax * v - ay * s, az * ay * v + ax * s, c + az * az * v};                                                    \
-			for (int r = 0; r < 3; r++)                                                                                                            \
-				for (int c2 = 0; c2 < 3; c2++) Rn[3 * r + c2] = Rt[3 * r] * Rq[c2] + Rt[3 * r + 1] * Rq[3 + c2] + Rt[3 * r + 2] * Rq[6 + c2];      \
-		} else {                                                                                                                                   \
-			const double a[3] = {ax, ay, az};                                                                                                      \
-			double d[3];                                                                                                                           \
-			fk_mat3_vec(Rt, a, d);                                                                                                                 \
-			for (int e = 0; e < 3; e++) o[e] += d[e] * qj;                                                                                         \
-			for (int e = 0; e < 9; e++) Rn[e] = Rt[e];                                                                                             \
-		}                                                                                                                                          \
-		for (int e = 0; e < 9; e++) R[e] = Rn[e];                                                                                                  \
-	}                                                                                                                                              \
-	double p[3];                                                                                                                                   \
-	fk_mat3_vec(R, tk.pos, p);                                                                                                                     \
-	for (int e = 0; e < 3; e++) pos[e] = o[e] + p[e];                                                                                              \
-	for (int r = 0; r < 3; r++)                                                                                                                    \
+// SAIP_FK_JOINT_STEP is one joint j of that walk (R, o: rotation and origin of the body walked so last), for walks that emit several
+// frames on the way (saip_model_query.hip).
+#define SAIP_FK_JOINT_STEP(...)                                                                                                                 \
+	double t3[3], Rn[9], Rt[9];                                                                                                                 \
+	fk_mat3_vec(R, md.p0[j], t3);                                                                                                               \
+	for (int e = 0; e < 3; e++) o[e] += t3[e];                                                                                                  \
+	for (int r = 0; r < 3; r++)                                                                                                                 \
+		for (int c = 0; c < 3; c++) Rt[3 * r + c] = R[3 * r] * md.R0[j][c] + R[3 * r + 1] * md.R0[j][3 + c] + R[3 * r + 2] * md.R0[j][6 + c];   \
+	const double qj = q[(size_t)j * ld + b];                                                                                                    \
+	const double ax = md.axis[j][0], ay = md.axis[j][1], az = md.axis[j][2];                                                                    \
+	__VA_ARGS__                                                                                                                                 \
+	if (md.jtype[j] == 1) {                                                                                                                     \
+		double s, c;                                                                                                                            \
+		sincos(qj, &s, &c);  /* library sin/cos on purpose: see above */                                                                        \
+		const double v = 1.0 - c;                                                                                                               \
+		const double Rq[9] = {c + ax * ax * v,      ax * ay * v - az * s, ax * az * v + ay * s,                                                 \
+							  ay * ax * v + az * s, c + ay * ay * v,      ay * az * v - ax * s,                                                 \
+							  az * ax * v - ay * s, az * ay * v + ax * s, c + az * az * v};                                                     \
+		for (int r = 0; r < 3; r++)                                                                                                             \
+			for (int c2 = 0; c2 < 3; c2++) Rn[3 * r + c2] = Rt[3 * r] * Rq[c2] + Rt[3 * r + 1] * Rq[3 + c2] + Rt[3 * r + 2] * Rq[6 + c2];       \
+	} else {                                                                                                                                    \
+		const double a[3] = {ax, ay, az};                                                                                                       \
+		double d[3];                                                                                                                            \
+		fk_mat3_vec(Rt, a, d);                                                                                                                  \
+		for (int e = 0; e < 3; e++) o[e] += d[e] * qj;                                                                                          \
+		for (int e = 0; e < 9; e++) Rn[e] = Rt[e];                                                                                              \
+	}                                                                                                                                           \
+	for (int e = 0; e < 9; e++) R[e] = Rn[e];
+#define SAIP_FK_WALK(...)                                                                                                                       \
+	double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};                                                                                \
+	for (int j = 0; j <= tk.body; j++) {                                                                                                        \
+		SAIP_FK_JOINT_STEP(__VA_ARGS__)                                                                                                         \
+	}                                                                                                                                           \
+	double p[3];                                                                                                                                \
+	fk_mat3_vec(R, tk.pos, p);                                                                                                                  \
+	for (int e = 0; e < 3; e++) pos[e] = o[e] + p[e];                                                                                           \
+	for (int r = 0; r < 3; r++)                                                                                                                 \
 		for (int c = 0; c < 3; c++) Rc[3 * r + c] = R[3 * r] * tk.rot[c] + R[3 * r + 1] * tk.rot[3 + c] + R[3 * r + 2] * tk.rot[6 + c];
 
 // world position of the control point and world rotation of the control frame of motion-force task tk
