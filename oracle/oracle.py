@@ -101,6 +101,9 @@ class Oracle:
                     a1, p1 = _d(dt_)
                     a2, p2 = _d(dr_)
                     tid = L.orc_add_motion_force_task(self._h, li, pp, rp, p1, len(dt_), p2, len(dr_))
+                if tid == -2:
+                    raise ValueError(f"motion force task [{t['name']}] controls more directions than the robot has dof ({self.n}): "
+                                     "undefined in the reference, use a partial task")
                 if tid < 0:
                     raise ValueError("invalid motion force task")
                 g = [_d(_vec3(t[k])) for k in ("kp_pos", "kv_pos", "ki_pos", "kp_ori", "kv_ori", "ki_ori")]

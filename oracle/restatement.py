@@ -350,12 +350,24 @@ def sh_blend_torques(model, t, m, q, dq, F_um, F_f, st):
     return tau_ns + m["alpha"] * tau_s + (1 - m["alpha"]) * tau_js
 
 
+def check_task_sizes(model, tasks):
+    """A motion-force task with more controlled directions than the robot has dof (k > n) is undefined in the reference:
+    SingularityHandler.cpp:78-118 reads k singular values of a thin SVD that has min(k, n).  Refused like the engine refuses it."""
+    for t in tasks:
+        if t["type"] == "motion_force":
+            _, _, pr, orr = mf_projection(t)
+            if pr + orr > model.dof:
+                raise ValueError(f"motion force task [{t['name']}] controls {pr + orr} directions but the robot has {model.dof} dof: "
+                                 "undefined in the reference, use a partial task")
+
+
 def controller_step_single(model, tasks, q, dq, goals, *, state=None, gravity_comp=False,
                            torque_saturation=False, joint_limit_avoidance=False, details=None, info=None):
     """One control cycle for ONE instance, literal reference path (SVDs, explicit inverses).
     goals[t]: flat vector (goal_size).  Returns tau (n,).  Raises Singular when an instance
     leaves the non-singular branch of SingularityHandler (alpha != 1)."""
     n = model.dof
+    check_task_sizes(model, tasks)
     frames = fk(model, q[None])
     M = mass_matrix(model, frames)[0]
     Minv = np.linalg.inv(M)
@@ -569,6 +581,7 @@ def controller_step_single(model, tasks, q, dq, goals, *, state=None, gravity_co
 
 def controller_step(model, tasks, q, dq, goals, **kw):
     """Batched wrapper. q,dq (B,n); goals[t] (B, goal_size). Returns tau (B,n), status (B,) uint8."""
+    check_task_sizes(model, tasks)
     B = q.shape[0]
     tau = np.full((B, model.dof), np.nan)
     status = np.zeros(B, np.uint8)

@@ -1376,6 +1376,9 @@ int orc_add_motion_force_task(orc_ctx* c, int link, const double* pos_in_link, c
 	int co = matrix_range_basis(Po, 3, 3, U, 1e-3);
 	t->ori_range = fro(U, 3 * co) == 0 ? 0 : co;
 	if (t->pos_range + t->ori_range == 0) return -1;
+	/* k > n: SingularityHandler.cpp:78-118 reads k singular values / left singular vectors of a thin SVD that has min(k, n):
+	 * undefined in the reference, refused here (and by the engine) instead of reading past the arrays of sh_update */
+	if (t->pos_range + t->ori_range > c->n) return -2;
 	for (int i = 0; i < 3; i++) { /* MotionForceTask.h:44-49 */
 		t->kp_pos[i] = 100.0; t->kv_pos[i] = 20.0; t->ki_pos[i] = 0.0;
 		t->kp_ori[i] = 200.0; t->kv_ori[i] = 28.3; t->ki_ori[i] = 0.0;

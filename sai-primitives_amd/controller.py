@@ -364,7 +364,7 @@ def _model_dynamics(h, robot, which, out=None):
         return out
     host = {k: np.empty((rows[k], B)) for k in which}
     capi.check(L.saip_batch_model_dynamics_host(h, *[_dptr(host[k]) if k in host else None for k in _DYN_KEYS]))
-    return {k: (v.T.reshape(B, n, n) if rows[k] == n * n else v.T).copy() for k, v in host.items()}
+    return {k: (v.T.reshape(B, n, n) if k in ("M", "M_inv") else v.T).copy() for k, v in host.items()}   # (by name: n * n == n at 1 dof)
 
 
 def _device_ptr(out, shape, who):

@@ -663,6 +663,13 @@ extern "C" saip_status saip_batch_finalize(saip_batch* b) {
 		if (closed)
 			return fail(SAIP_ERR_INVALID_ARGUMENT, "task [%s] cannot be added to the controller because it is in the nullspace of a full joint task", b->tasks[i].name.c_str());
 		if (b->tasks[i].dev.type == saip::TASK_JOINT && b->tasks[i].full_joint) closed = true;
+		// k > n: the reference's thin SVD of the k x n task Jacobian has min(k, n) singular values and SingularityHandler.cpp:78-118
+		// reads k of them (undefined behaviour); the per-task interface goes through this batch too, so it is refused with it
+		if (b->tasks[i].dev.type == saip::TASK_MOTION_FORCE && b->tasks[i].dev.k > b->model->n)
+			return fail(SAIP_ERR_UNSUPPORTED,
+						"MotionForceTask [%s] controls %d directions but the robot has only %d dof: the reference's singularity handler is undefined "
+						"for a task with more directions than joints; use a partial task (controlled_directions_translation / _rotation) of at most %d directions",
+						b->tasks[i].name.c_str(), b->tasks[i].dev.k, b->model->n, b->model->n);
 	}
 	if (has_device(b)) {
 		HIP_TRY(hipSetDevice(b->device));

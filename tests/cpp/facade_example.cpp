@@ -1,6 +1,7 @@
 // Drives the C++ facade the way /root/reference/examples/05-using_robot_controller/05-using_robot_controller.cpp:103-196
 // drives the reference: MotionForceTask + JointTask in a RobotController, one control cycle.
 //   facade_example <robot.txt> cfgonly            host-logic checks without a GPU (device -1)
+//   facade_example <robot.txt> kgtn <device> <link>   a robot of fewer than 6 dof refuses a full motion-force task on <link>
 //   facade_example <robot.txt> run <B> <in.bin> <out.bin>   one cycle on GPU 0: in = q,dq,goal0[24],goal1[21] as [c][B] doubles
 //   facade_example <robot.txt> ex04 <B> <in.bin> <out.bin>  the same tasks WITHOUT a controller, hierarchy built by hand like
 //       /root/reference/examples/04-task_and_redundancy/04-task_and_redundancy.cpp:141-206; out = tau_mf, tau_joint, tau_joint with
@@ -76,6 +77,37 @@ int main(int argc, char** argv) {
 		}
 		ok &= loud;
 		std::cout << (ok ? "FACADE_CFG_OK" : "FACADE_CFG_FAIL") << std::endl;
+		return ok ? 0 : 1;
+	}
+	if (std::string(argv[2]) == "kgtn" && argc == 5) {
+		// a robot of fewer than 6 dof: the full motion-force task (6 directions) on link argv[4] is refused by the controller and by the
+		// per-task interface; a position task (3 directions) is accepted when the robot has at least 3 dof
+		auto robot = std::make_shared<SaiModel>(links, 4, atoi(argv[3]));
+		const int n = robot->dof();
+		auto refused = [](auto f) {
+			try {
+				f();
+			} catch (const std::runtime_error& e) {
+				return std::string(e.what()).find("use a partial task") != std::string::npos;
+			}
+			return false;
+		};
+		int ok = n < 6;
+		auto full = std::make_shared<MotionForceTask>(robot, argv[4], pos_in_link, "full");
+		std::vector<std::shared_ptr<TemplateTask>> tasks = {full, std::make_shared<JointTask>(robot)};
+		ok &= refused([&] { RobotController c(robot, tasks); });
+		auto alone = std::make_shared<MotionForceTask>(robot, argv[4], pos_in_link, "alone");
+		std::vector<double> eye((size_t)n * n, 0.0);
+		for (int i = 0; i < n; i++) eye[(size_t)i * n + i] = 1.0;
+		ok &= refused([&] { alone->updateTaskModel(eye); });
+		if (n >= 3) {
+			auto pos = std::make_shared<MotionForceTask>(robot, argv[4], std::vector<double>{1, 0, 0, 0, 1, 0, 0, 0, 1}, std::vector<double>{},
+														 pos_in_link, "position");
+			std::vector<std::shared_ptr<TemplateTask>> ptasks = {pos, std::make_shared<JointTask>(robot)};
+			RobotController c(robot, ptasks);
+			ok &= c.getTaskNames().size() == 2;
+		}
+		std::cout << (ok ? "FACADE_KGTN_OK" : "FACADE_KGTN_FAIL") << std::endl;
 		return ok ? 0 : 1;
 	}
 	if (std::string(argv[2]) == "run" && argc == 6) {

@@ -465,8 +465,11 @@ def test_six_and_eight_dof_chains(case):
         ctrl.setKernel(kernel)
         ctrl.enableGravityCompensation(opts["gravity_comp"])
         ctrl.enableTorqueSaturation(opts["torque_saturation"])
-        taus = [_cycle(robot, ctrl, q + 0.01 * cyc, dq, goals).copy() for cyc in range(3)]
-        out[kernel] = (np.array(taus), ctrl.status.copy(), ctrl.kernelName())
+        taus, sts = [], []
+        for cyc in range(3):
+            taus.append(_cycle(robot, ctrl, q + 0.01 * cyc, dq, goals).copy())
+            sts.append(ctrl.status.copy())
+        out[kernel] = (np.array(taus), sts[-1], ctrl.kernelName(), np.array(sts))
     assert out[OCT][2] == "saip_cycle_oct" and out[2][2] == "saip_cycle_lane"
     orc = Oracle(model, tasks, **opts)
     for cyc in range(3):
@@ -476,4 +479,12 @@ def test_six_and_eight_dof_chains(case):
         e8, e1 = W.torque_error(out[OCT][0][cyc][plain], ref[plain]), W.torque_error(out[2][0][cyc][plain], ref[plain])
         print(f"{case} cycle {cyc}: eight-lane err {e8:.2e}, lane err {e1:.2e}, plain {int(plain.sum())} of {B}, status set {sorted(set(out[OCT][1]))}")
         assert e8 < TOL and e1 < TOL
+        # the instances inside the handler's region (blended strategies, status 8) against the oracle too: whole status words equal
+        # every cycle, torques of every instance the oracle does not refuse
+        for k in (OCT, 2):
+            assert np.array_equal(out[k][3][cyc], st), (case, k, cyc, np.flatnonzero(out[k][3][cyc] != st)[:8])
+        kept = (st & 1) == 0
+        b8, b1 = W.torque_error(out[OCT][0][cyc][kept], ref[kept]), W.torque_error(out[2][0][cyc][kept], ref[kept])
+        print(f"{case} cycle {cyc}: all {int(kept.sum())} non-refused ({int((st == 8).sum())} blended): eight-lane err {b8:.2e}, lane err {b1:.2e}")
+        assert b8 < TOL and b1 < TOL
     assert np.array_equal(out[OCT][1], out[2][1])
