@@ -22,8 +22,9 @@
  *     fails with SAIP_ERR_NO_DEVICE when no HIP device is usable.
  *
  * Limits (what the reference accepts and this engine does not: every one fails loudly with SAIP_ERR_INVALID_ARGUMENT / _UNSUPPORTED)
- *   - robots are SERIAL CHAINS (link i's parent is link i - 1; sai-model also reads trees) with at most SAIP_MAX_DOF = 32 movable
- *     joints, revolute or prismatic; fixed links are merged into their parents.
+ *   - robots are kinematic trees with a fixed base (saip_model_create_tree; no floating base) and at most SAIP_MAX_DOF = 32 movable
+ *     joints, revolute or prismatic; fixed links are merged into their movable ancestors.  The fast cycle kernels (lane, eight-lane,
+ *     wavefront) cover chains after that merging only; other trees run the general kernel.
  *   - a hierarchy holds at most SAIP_MAX_TASKS = 8 tasks (MotionForceTask / JointTask; RobotController's joint-limit-avoidance task is
  *     the controller option of saip_batch_enable_joint_limit_avoidance, not a ninth task).
  *   - a motion-force task of rank 1 (a single controlled direction) is refused: SingularityHandler's own loop leaves such a task with
@@ -92,7 +93,16 @@ typedef struct saip_link_desc {
 
 /* ---------------------------------------------------------------- robot model (constants only; replaces the
  * SaiModel constructor + URDF parse; the per-cycle SaiModel::updateModel() is part of the GPU cycle) */
-saip_status saip_model_create_serial_chain(const saip_link_desc* links, int n_links, saip_model** out);
+saip_status saip_model_create_serial_chain(const saip_link_desc* links, int n_links, saip_model** out); /* = create_tree(links, NULL, ...) */
+/* Kinematic tree: parent[l] is the index in `links` of link l's parent, -1 for the fixed base; every parent comes before its children
+ * (parent[l] < l), else SAIP_ERR_INVALID_ARGUMENT naming the link.  parent == NULL means parent[l] = l - 1 (a serial chain).  Fixed links
+ * are merged per branch into their movable ancestor (those welded to the base carry no dynamics); a fixed link may have several children.
+ * The dof index of a movable link is its rank among the movable links in the given order.  (sai-model orders the joints of a URDF tree
+ * the way RBDL adds its bodies [RECALLED, not pinned here]: give the links in that order to reproduce its joint vector.)  A model whose
+ * movable bodies form a chain after merging runs exactly as saip_model_create_serial_chain would; any other (forests included) runs the
+ * general cycle kernel only (saip_batch_set_kernel(2|3|4) fails with SAIP_ERR_UNSUPPORTED). */
+saip_status saip_model_create_tree(const saip_link_desc* links, const int* parent, int n_links, saip_model** out);
+int saip_model_joint_parent(const saip_model* model, int joint);          /* movable parent body of joint `joint`; -1 the base, -2 bad index */
 void saip_model_destroy(saip_model* model);
 int saip_model_dof(const saip_model* model);                               /* SaiModel::dof() */
 int saip_model_link_index(const saip_model* model, const char* link_name); /* -1 when absent */

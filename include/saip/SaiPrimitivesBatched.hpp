@@ -61,6 +61,14 @@ public:
 		_q.assign((size_t)dof() * _batch, 0.0);
 		_dq.assign((size_t)dof() * _batch, 0.0);
 	}
+	// kinematic tree: parent[l] = index of link l's parent in `links`, -1 for the fixed base (saip_model_create_tree)
+	SaiModel(const std::vector<saip_link_desc>& links, const std::vector<int>& parent, int batch_size, int device = 0)
+		: _batch(batch_size), _device(device) {
+		if (parent.size() != links.size()) throw std::invalid_argument("SaiModel: one parent index per link expected");
+		check(saip_model_create_tree(links.data(), parent.data(), (int)links.size(), &_model));
+		_q.assign((size_t)dof() * _batch, 0.0);
+		_dq.assign((size_t)dof() * _batch, 0.0);
+	}
 	~SaiModel() {
 		if (_mq) saip_batch_destroy(_mq);  // the query batch refers to the model: it goes first
 		saip_model_destroy(_model);
@@ -92,6 +100,12 @@ public:
 		if (_mq) pushQueryState();
 	}
 	const saip_model* handle() const { return _model; }
+	// movable parent body of joint `joint` (-1: the fixed base)
+	int jointParent(int joint) const {
+		const int p = saip_model_joint_parent(_model, joint);
+		if (p == -2) throw std::invalid_argument("jointParent: joint index out of range");
+		return p;
+	}
 	int linkIndex(const std::string& link) const {
 		const int i = saip_model_link_index(_model, link.c_str());
 		if (i < 0) throw std::invalid_argument("link " + link + " does not exist in the robot model");

@@ -103,6 +103,8 @@ def lib():
     u8p = C.POINTER(C.c_ubyte)
     sig = {
         "saip_model_create_serial_chain": (C.c_int, [C.POINTER(LinkDesc), C.c_int, C.POINTER(vp)]),
+        "saip_model_create_tree": (C.c_int, [C.POINTER(LinkDesc), ip, C.c_int, C.POINTER(vp)]),
+        "saip_model_joint_parent": (C.c_int, [vp, C.c_int]),
         "saip_model_destroy": (None, [vp]),
         "saip_model_dof": (C.c_int, [vp]),
         "saip_model_link_index": (C.c_int, [vp, C.c_char_p]),

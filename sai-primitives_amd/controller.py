@@ -76,6 +76,30 @@ def _soa(a, B, comps, what):
     return np.ascontiguousarray(a.T)
 
 
+def _link_parents(links):
+    """parent link indices of a robot description whose links name their "parent" (a link name, or None for the fixed base; a link
+    without the key hangs off the link listed before it), or None when no link names one (a serial chain, as every description was)"""
+    if not any("parent" in l for l in links):
+        return None
+    index = {}
+    out = []
+    for i, l in enumerate(links):
+        if "parent" not in l:
+            out.append(i - 1)
+        elif l["parent"] is None:
+            out.append(-1)
+        else:
+            if l["parent"] not in index:  # unknown, or listed after its child: the C-ABI reports the latter with the link's name
+                known = {x["name"]: k for k, x in enumerate(links)}
+                if l["parent"] not in known:
+                    raise ValueError(f"link {l['name']}: parent link {l['parent']} is not in the robot description")
+                out.append(known[l["parent"]])
+            else:
+                out.append(index[l["parent"]])
+        index[l["name"]] = i
+    return out
+
+
 class SaiModel:
     """B instances of one robot (batched stand-in for SaiModel::SaiModel: constants + q/dq state)."""
 
@@ -97,7 +121,11 @@ class SaiModel:
             d.velocity_limit, d.effort_limit = l["velocity_limit"], l["effort_limit"]
         L = capi.lib()
         h = C.c_void_p()
-        capi.check(L.saip_model_create_serial_chain(arr, len(links), C.byref(h)))
+        parents = _link_parents(links)
+        if parents is None:
+            capi.check(L.saip_model_create_serial_chain(arr, len(links), C.byref(h)))
+        else:
+            capi.check(L.saip_model_create_tree(arr, (C.c_int * len(links))(*parents), len(links), C.byref(h)))
         self._h = h
         self._n = L.saip_model_dof(h)
         self.batch_size = int(batch_size)
@@ -167,6 +195,13 @@ class SaiModel:
 
     def linkIndex(self, name: str) -> int:
         return capi.lib().saip_model_link_index(self._h, name.encode())
+
+    def jointParent(self, joint: int) -> int:
+        """movable parent body of joint `joint` (-1: the fixed base); the topology of a tree after fixed-link merging"""
+        p = capi.lib().saip_model_joint_parent(self._h, int(joint))
+        if p == -2:
+            raise ValueError(f"jointParent: joint index {joint} out of range [0, {self._n})")
+        return p
 
     # -- model queries: the SaiModel accessors at the state of the last updateModel() (C-ABI saip_batch_model_frames_host /
     # saip_batch_model_dynamics_host on a model-only batch).  Links by name or by linkIndex() value.

@@ -17,7 +17,7 @@ struct alignas(256) JointRec {
 };
 static_assert(sizeof(JointRec) == 256, "JointRec must be exactly four cache lines");
 
-// one movable body of the serial chain (fixed links already merged on the host, engine.cpp: merge_fixed_links)
+// the movable bodies of one robot (fixed links already merged on the host, saip_engine.cpp: saip_model_create_tree)
 struct ModelDev {
 	int n;
 	int all_axis_z;              // every joint axis == (0,0,1) (the usual URDF convention): the eight-lane kernels build R0 Rz(q) from two columns
@@ -35,6 +35,13 @@ struct ModelDev {
 	double gravity[3];
 	double pad_align_[5];
 	JointRec jrec[SAIP_MAXN];    // packed copy of the per-joint constants above (lane kernel FK loop)
+	// Topology, read by the tree instantiations only (the serial ones compile to what they compiled to before these fields existed).
+	// A model whose movable bodies form a chain after fixed-link merging has is_tree = 0 and runs the serial code everywhere.
+	int is_tree;
+	int parent[SAIP_MAXN];       // movable parent body (-1: the fixed base); parent[j] < j
+	uint32_t anc[SAIP_MAXN];     // bit i set: body i is an ancestor of body j or j itself
+	uint32_t desc[SAIP_MAXN];    // bit i set: body i is a descendant of body j or j itself
+	int jump[5][SAIP_MAXN];      // the 2^r-th ancestor of body j (-1: none): pointer jumping of the general kernel's prefix-product FK
 };
 
 enum { TASK_JOINT = 2, TASK_MOTION_FORCE = 3 };

@@ -14,23 +14,23 @@
 #include "saip_device.h"
 
 namespace saip {
-hipError_t launch_cycle_wg(const CycleParams& P, hipStream_t stream);
+hipError_t launch_cycle_wg(const CycleParams& P, bool tree, hipStream_t stream);
 hipError_t launch_cycle_wg_list(const CycleParams& P, hipStream_t stream);
-hipError_t launch_reinit(const CycleParams& P, hipStream_t stream);
+hipError_t launch_reinit(const CycleParams& P, bool tree, hipStream_t stream);
 hipError_t launch_cycle_lane(const CycleParams& P, hipStream_t stream, bool* supported);
 hipError_t launch_cycle_oct(const CycleParams& P, hipStream_t stream);
 hipError_t launch_cycle_wave(const CycleParams& P, hipStream_t stream);
 hipError_t launch_cycle_octjf(const CycleParams& P, hipStream_t stream);
-hipError_t launch_pose(const CycleParams& P, int task, double* out, hipStream_t stream);
-hipError_t launch_task_diag(const CycleParams& P, int task, const double* goal, const double* desired, int gcomps, double* out, hipStream_t stream);
-hipError_t launch_model_frames(const saip::FrameQuery& Q, hipStream_t stream);
-hipError_t launch_model_dynamics(const saip::DynQuery& Q, hipStream_t stream);
+hipError_t launch_pose(const CycleParams& P, int task, double* out, bool tree, hipStream_t stream);
+hipError_t launch_task_diag(const CycleParams& P, int task, const double* goal, const double* desired, int gcomps, double* out, bool tree, hipStream_t stream);
+hipError_t launch_model_frames(const saip::FrameQuery& Q, bool tree, hipStream_t stream);
+hipError_t launch_model_dynamics(const saip::DynQuery& Q, bool tree, hipStream_t stream);
 hipError_t launch_otg_joints(const OtgDev& O, int B, int ld, int mode, hipStream_t stream);
-hipError_t launch_otg_cartesian(const OtgDev& O, int B, int ld, int mode, hipStream_t stream);
+hipError_t launch_otg_cartesian(const OtgDev& O, int B, int ld, int mode, bool tree, hipStream_t stream);
 hipError_t launch_otg_pair(const OtgDev& Oc, const OtgDev& Oj, int B, int ld, hipStream_t stream);
 hipError_t launch_integrate_otg_pair(const SimParams& S, const OtgDev& Oc, const OtgDev& Oj, int B, int ld, hipStream_t stream);
 int otg_state_fields();
-hipError_t launch_integrate(const SimParams& S, hipStream_t stream);
+hipError_t launch_integrate(const SimParams& S, bool tree, hipStream_t stream);
 }  // namespace saip
 
 using saip::CycleParams;
@@ -201,17 +201,39 @@ static void inertial_add(Inertial& a, double m2, const double* c2, const double*
 	memcpy(a.I, I, sizeof(I));
 }
 
+static saip_status model_create(const saip_link_desc* links, const int* parent, int n_links, saip_model** out, const char* fn);
 extern "C" saip_status saip_model_create_serial_chain(const saip_link_desc* links, int n_links, saip_model** out) {
-	if (!links || !out || n_links <= 0) return fail(SAIP_ERR_INVALID_ARGUMENT, "saip_model_create_serial_chain: null or empty link list");
+	return model_create(links, nullptr, n_links, out, "saip_model_create_serial_chain");
+}
+extern "C" saip_status saip_model_create_tree(const saip_link_desc* links, const int* parent, int n_links, saip_model** out) {
+	return model_create(links, parent, n_links, out, "saip_model_create_tree");
+}
+// fn: the entry point called, for the messages
+static saip_status model_create(const saip_link_desc* links, const int* parent, int n_links, saip_model** out, const char* fn) {
+	if (!links || !out || n_links <= 0) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null or empty link list", fn);
+	if (parent)
+		for (int l = 0; l < n_links; l++)
+			if (parent[l] < -1 || parent[l] >= l)
+				return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: link %.*s has parent index %d (a parent must be -1, the fixed base, or a link "
+						   "listed before it)", fn, SAIP_NAME_LEN, links[l].name, parent[l]);
 	auto* M = new saip_model();
 	memset(&M->dev, 0, sizeof(ModelDev));
-	// pending fixed transform between the last movable body frame (or the base) and the current link
-	double Rp[9], pp[3] = {0, 0, 0};
-	m3_eye(Rp);
-	int body = -1;
 	std::vector<Inertial> inertials;
+	std::vector<int> body_parent;  // movable parent body of each movable body (-1: the base)
 	for (int l = 0; l < n_links; l++) {
 		const saip_link_desc& L = links[l];
+		// fixed transform between the parent link's movable body frame (or the base) and this link: the parent link's own (body, R, p)
+		const int pl_idx = parent ? parent[l] : l - 1;
+		double Rp[9], pp[3] = {0, 0, 0};
+		int body = -1;
+		if (pl_idx >= 0) {
+			const LinkInfo& P = M->links[pl_idx];
+			body = P.body;
+			memcpy(Rp, P.R, sizeof(Rp));
+			memcpy(pp, P.p, sizeof(pp));
+		} else {
+			m3_eye(Rp);
+		}
 		double R0[9], Rl[9], pl[3], t[3];
 		rpy_to_R(L.origin_rpy, R0);
 		m3_vec(Rp, L.origin_xyz, t);
@@ -241,6 +263,7 @@ extern "C" saip_status saip_model_create_serial_chain(const saip_link_desc* link
 				return fail(SAIP_ERR_INVALID_ARGUMENT, "joint of link %s has a zero axis", L.name);
 			}
 			int j = M->n++;
+			body_parent.push_back(body);
 			body = j;
 			M->dev.jtype[j] = L.joint_type;
 			memcpy(M->dev.R0[j], Rl, sizeof(Rl));
@@ -307,8 +330,29 @@ extern "C" saip_status saip_model_create_serial_chain(const saip_link_desc* link
 	M->dev.all_axis_z = 1;
 	for (int j = 0; j < M->n; j++)
 		if (!M->dev.axis_is_z[j]) M->dev.all_axis_z = 0;
+	// topology of the movable bodies: a chain after merging (every body's parent is the body before it) keeps is_tree = 0 and the serial kernels
+	M->dev.is_tree = 0;
+	for (int j = 0; j < M->n; j++) {
+		const int pa = body_parent[j];
+		M->dev.parent[j] = pa;
+		if (pa != j - 1) M->dev.is_tree = 1;
+		M->dev.anc[j] = (pa >= 0 ? M->dev.anc[pa] : 0u) | (1u << j);
+		M->dev.desc[j] = 1u << j;
+	}
+	for (int j = M->n - 1; j >= 0; j--)
+		if (M->dev.parent[j] >= 0) M->dev.desc[M->dev.parent[j]] |= M->dev.desc[j];
+	for (int r = 0; r < 5; r++)
+		for (int j = 0; j < SAIP_MAXN; j++) {
+			if (j >= M->n) M->dev.jump[r][j] = -1;
+			else if (r == 0) M->dev.jump[0][j] = M->dev.parent[j];
+			else M->dev.jump[r][j] = M->dev.jump[r - 1][j] < 0 ? -1 : M->dev.jump[r - 1][M->dev.jump[r - 1][j]];
+		}
 	*out = M;
 	return SAIP_OK;
+}
+extern "C" int saip_model_joint_parent(const saip_model* m, int joint) {
+	if (!m || joint < 0 || joint >= m->n) return -2;
+	return m->dev.parent[joint];
 }
 extern "C" void saip_model_destroy(saip_model* m) { delete m; }
 extern "C" int saip_model_dof(const saip_model* m) { return m ? m->n : 0; }
@@ -1290,7 +1334,7 @@ static saip_status run_otg(saip_batch* b, int t, int mode, int mask = 3) {
 		T.otg_limits_dirty = false;
 	}
 	hipError_t e = T.dev.type == saip::TASK_JOINT ? saip::launch_otg_joints(T.otg, b->B, b->ld, mode, b->stream)
-												  : saip::launch_otg_cartesian(T.otg, b->B, b->ld, mode | (mask << 4), b->stream);
+												  : saip::launch_otg_cartesian(T.otg, b->B, b->ld, mode | (mask << 4), b->model->dev.is_tree != 0, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "OTG kernel launch failed: %s", hipGetErrorString(e));
 	if (mode == 1 && mask == 3) T.otg_inited = true;
 	return SAIP_OK;
@@ -1420,7 +1464,7 @@ static saip_status make_params(saip_batch* b, CycleParams& P, bool diag) {
 // the lane-per-instance register kernel covers 6..8 dof, at most two motion-force tasks and one shared BIE threshold
 static bool lane_eligible(const saip_batch* b) {
 	const int n = b->model->n;
-	if (n < 6 || n > 8) return false;
+	if (n < 6 || n > 8 || b->model->dev.is_tree) return false;  // (chains only: the fast kernels scan along the chain)
 	int nmf = 0;
 	double thr = -1.0;
 	for (auto& T : b->tasks) {
@@ -1440,7 +1484,7 @@ static bool lane_eligible(const saip_batch* b) {
 // law itself, so an instance this kernel flags late in the hierarchy would advance it twice when the general kernel recomputes it.
 static bool wave_eligible(const saip_batch* b) {
 	const int n = b->model->n;
-	if (n <= 8 || n > 32) return false;
+	if (n <= 8 || n > 32 || b->model->dev.is_tree) return false;
 	for (auto& T : b->tasks) {
 		if (T.dev.type == saip::TASK_MOTION_FORCE && (T.dev.cl_force || T.dev.cl_moment) && T.dev.popc_enabled) return false;
 		if (T.dev.type == saip::TASK_MOTION_FORCE && (T.dev.k < 2 || T.dev.k > 6)) return false;
@@ -1452,7 +1496,7 @@ static bool wave_eligible(const saip_batch* b) {
 // task of at most four rows (general range basis); default or general control laws, no closed-loop force control.
 static bool oct_eligible(const saip_batch* b, CycleParams& P) {
 	const int n = b->model->n;
-	if (n < 6 || n > 8 || b->tasks.size() != 2) return false;
+	if (n < 6 || n > 8 || b->tasks.size() != 2 || b->model->dev.is_tree) return false;
 	const TaskDev& mf = b->tasks[0].dev;
 	const TaskDev& jt = b->tasks[1].dev;
 	if (mf.type != saip::TASK_MOTION_FORCE || jt.type != saip::TASK_JOINT) return false;
@@ -1500,7 +1544,7 @@ static bool oct_eligible(const saip_batch* b, CycleParams& P) {
 // closed-loop force control keep the stack on the lane kernel.
 static bool octjf_eligible(const saip_batch* b, const CycleParams& P) {
 	const int n = b->model->n;
-	if ((n != 7 && n != 8) || b->tasks.size() != 2 || P.jla) return false;
+	if ((n != 7 && n != 8) || b->tasks.size() != 2 || P.jla || b->model->dev.is_tree) return false;
 	const TaskDev& jt = b->tasks[0].dev;
 	const TaskDev& mf = b->tasks[1].dev;
 	if (jt.type != saip::TASK_JOINT || mf.type != saip::TASK_MOTION_FORCE) return false;
@@ -1663,9 +1707,10 @@ static saip_status launch_cycle(saip_batch* b, bool diag) {
 		if (e2 != hipSuccess) return fail(SAIP_ERR_DEVICE, "slow-path kernel launch failed: %s", hipGetErrorString(e2));
 		return SAIP_OK;
 	}
-	hipError_t e = saip::launch_cycle_wg(P, b->stream);
+	hipError_t e = saip::launch_cycle_wg(P, b->model->dev.is_tree != 0, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
-	b->kernel_name = P.n <= 8 ? "saip_cycle_wg<8,64>" : "saip_cycle_wg<32,512>";
+	if (b->model->dev.is_tree) b->kernel_name = P.n <= 8 ? "saip_cycle_wg_tree<8,64>" : "saip_cycle_wg_tree<32,512>";
+	else b->kernel_name = P.n <= 8 ? "saip_cycle_wg<8,64>" : "saip_cycle_wg<32,512>";
 	return SAIP_OK;
 }
 
@@ -1683,7 +1728,7 @@ static saip_status launch_reinit_masked(saip_batch* b, int task, int mask) {
 	if (st) return st;
 	P.reinit_task = task;
 	P.reinit_mask = mask;
-	hipError_t e = saip::launch_reinit(P, b->stream);
+	hipError_t e = saip::launch_reinit(P, b->model->dev.is_tree != 0, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "reinit launch failed: %s", hipGetErrorString(e));
 	for (size_t t = 0; t < b->tasks.size(); t++) {  // JointTask::reInitializeTask -> _otg->reInitialize (JointTask.cpp:106)
 		TaskHost& T = b->tasks[t];
@@ -1711,7 +1756,7 @@ extern "C" saip_status saip_batch_get_current_pose_host(saip_batch* b, int task,
 	if (!b->pose_dev && (st = dev_alloc(b, &b->pose_dev, (size_t)12 * b->ld))) return st;
 	CycleParams P;
 	if ((st = make_params(b, P, false))) return st;
-	hipError_t e = saip::launch_pose(P, task, b->pose_dev, b->stream);
+	hipError_t e = saip::launch_pose(P, task, b->pose_dev, b->model->dev.is_tree != 0, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "pose kernel launch failed: %s", hipGetErrorString(e));
 	HIP_TRY(hipStreamSynchronize(b->stream));
 	if (pos && (st = copy_d2h(b, pos, b->pose_dev, 3))) return st;
@@ -1728,7 +1773,7 @@ static saip_status launch_task_diagnostics(saip_batch* b, int task, double* out_
 	if ((st = make_params(b, P, false))) return st;
 	TaskHost& T = b->tasks[task];
 	const bool otg = T.otg_enabled && T.otg_alloc && T.otg_inited;  // as saip_batch_get_desired_host
-	hipError_t e = saip::launch_task_diag(P, task, T.goal_dev, otg ? T.desired_dev : T.goal_dev, T.dev.goal_comps, out_dev, b->stream);
+	hipError_t e = saip::launch_task_diag(P, task, T.goal_dev, otg ? T.desired_dev : T.goal_dev, T.dev.goal_comps, out_dev, b->model->dev.is_tree != 0, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "task diagnostics kernel launch failed: %s", hipGetErrorString(e));
 	return SAIP_OK;
 }
@@ -1860,7 +1905,7 @@ static saip_status launch_task(saip_batch* b, int t, int phase, const double* ta
 	P.out_Ntot = phase == 1 ? T.ntot_dev : nullptr;
 	P.tau = tau_out_dev ? tau_out_dev : T.ttau_dev;
 	P.status = T.tstatus_dev;
-	hipError_t e = saip::launch_cycle_wg(P, b->stream);
+	hipError_t e = saip::launch_cycle_wg(P, b->model->dev.is_tree != 0, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "per-task kernel launch failed: %s", hipGetErrorString(e));
 	return SAIP_OK;
 }
@@ -1971,6 +2016,8 @@ extern "C" saip_status saip_batch_wait_for(saip_batch* waiter, saip_batch* produ
 
 extern "C" saip_status saip_batch_set_kernel(saip_batch* b, int which) {
 	if (!b || which < 0 || which > 4) return fail(SAIP_ERR_INVALID_ARGUMENT, "kernel selector must be 0, 1, 2, 3 or 4");
+	if (which >= 2 && b->model->dev.is_tree)
+		return fail(SAIP_ERR_UNSUPPORTED, "saip_batch_set_kernel(%d): this robot is a kinematic tree; only the general kernel (0 or 1) covers trees", which);
 	b->kernel_choice = which;
 	return SAIP_OK;
 }
@@ -1992,12 +2039,13 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 	S.tau = b->tau_bound ? b->tau_bound : b->tau;
 	S.ddq = nullptr;
 	hipError_t e;
-	if (with_next_otg && S.n == 7 && otg_pair_ready(b)) {
+	const bool tree = b->model->dev.is_tree != 0;  // trees: the lane-per-instance tree kernel, whatever the dof (the eight-lane step is chain-only)
+	if (with_next_otg && S.n == 7 && !tree && otg_pair_ready(b)) {
 		// rollouts: this integration and the NEXT period's trajectory generation in one launch (they are independent)
 		e = saip::launch_integrate_otg_pair(S, b->tasks[0].otg, b->tasks[1].otg, b->B, b->ld, b->stream);
 		b->otg_prelaunched = true;
 	} else {
-		e = saip::launch_integrate(S, b->stream);
+		e = saip::launch_integrate(S, tree, b->stream);
 	}
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "integrate launch failed: %s", hipGetErrorString(e));
 	b->models_valid = false;  // the state moved: like after robot->setQ(), updateControllerTaskModels() is due
@@ -2227,7 +2275,7 @@ static saip_status launch_frames(saip_batch* b, int nf, const int* links, const 
 	Q.q = b->q;
 	Q.dq = b->dq;
 	Q.out = out_dev;
-	hipError_t e = saip::launch_model_frames(Q, b->stream);
+	hipError_t e = saip::launch_model_frames(Q, b->model->dev.is_tree != 0, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "model frames kernel launch failed: %s", hipGetErrorString(e));
 	return SAIP_OK;
 }
@@ -2265,7 +2313,7 @@ static saip_status launch_dynamics(saip_batch* b, double* M, double* Minv, doubl
 	Q.Minv = Minv;
 	Q.g = g;
 	Q.h = h;
-	hipError_t e = saip::launch_model_dynamics(Q, b->stream);
+	hipError_t e = saip::launch_model_dynamics(Q, b->model->dev.is_tree != 0, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "model dynamics kernel launch failed: %s", hipGetErrorString(e));
 	return SAIP_OK;
 }

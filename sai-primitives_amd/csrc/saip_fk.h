@@ -1,4 +1,4 @@
-// Serial-chain forward kinematics of one control frame for one instance (straight walk over the chain; used by the
+// Forward kinematics of one control frame for one instance (straight walk over the chain; used by the
 // re-initialisation paths only -- the cycle kernels have their own fused kinematics).
 // SaiModel::positionInWorld / rotationInWorld call sites: MotionForceTask.cpp:212-216, 286-289.
 #pragma once
@@ -81,6 +81,32 @@ __device__ __forceinline__ void fk_mat3_vec(const double* R, const double* v, do
 // world position of the control point and world rotation of the control frame of motion-force task tk
 __device__ inline void fk_control_frame(const ModelDev& md, const TaskDev& tk, const double* q, int ld, int b, double pos[3], double Rc[9]) {
 	SAIP_FK_WALK()
+}
+
+// SAIP_FK_WALK of a kinematic tree: the same steps over the ancestors of the body only, in ascending order (a joint's origin is expressed in
+// its parent body's frame, and every ancestor comes before its descendants)
+#define SAIP_FK_WALK_TREE(...)                                                                                                                  \
+	double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};                                                                                \
+	const uint32_t anc_ = tk.body >= 0 ? md.anc[tk.body] : 0u;                                                                                  \
+	for (int j = 0; j <= tk.body; j++) {                                                                                                        \
+		if (!((anc_ >> j) & 1u)) continue;                                                                                                      \
+		SAIP_FK_JOINT_STEP(__VA_ARGS__)                                                                                                         \
+	}                                                                                                                                           \
+	double p[3];                                                                                                                                \
+	fk_mat3_vec(R, tk.pos, p);                                                                                                                  \
+	for (int e = 0; e < 3; e++) pos[e] = o[e] + p[e];                                                                                           \
+	for (int r = 0; r < 3; r++)                                                                                                                 \
+		for (int c = 0; c < 3; c++) Rc[3 * r + c] = R[3 * r] * tk.rot[c] + R[3 * r + 1] * tk.rot[3 + c] + R[3 * r + 2] * tk.rot[6 + c];
+
+__device__ inline void fk_control_frame_tree(const ModelDev& md, const TaskDev& tk, const double* q, int ld, int b, double pos[3], double Rc[9]) {
+	SAIP_FK_WALK_TREE()
+}
+
+// compile-time choice for the templated kernels (TREE = false is fk_control_frame itself)
+template <bool TREE>
+__device__ __forceinline__ void fk_control_frame_t(const ModelDev& md, const TaskDev& tk, const double* q, int ld, int b, double pos[3], double Rc[9]) {
+	if constexpr (TREE) fk_control_frame_tree(md, tk, q, ld, b, pos, Rc);
+	else fk_control_frame(md, tk, q, ld, b, pos, Rc);
 }
 
 }  // namespace saip

@@ -1,6 +1,7 @@
 // General control-cycle kernel: ONE WORKGROUP PER ROBOT INSTANCE, every matrix of the instance resident in LDS.
 //
-// Covers any serial chain with dof <= NMAX and any task stack (runtime sizes, batch-uniform control flow).
+// Covers any serial chain with dof <= NMAX and any task stack (runtime sizes, batch-uniform control flow); saip_cycle_wg_tree covers kinematic
+// trees (ModelDev::is_tree) with the same body.
 //   NMAX = 8,  T = 64  : one wavefront per instance (Panda-class arms), ~12 KB LDS -> up to 13 instances per CU
 //   NMAX = 32, T = 256 : four wavefronts per instance (humanoid-scale chains), ~125 KB LDS -> 1 instance per CU
 //
@@ -32,6 +33,14 @@ __global__ void __launch_bounds__(T) saip_cycle_wg(const CycleParams P) {
 	if (b >= P.B) return;
 	if (P.only_flagged && (P.status[b] & 1) == 0) return;  // status-driven slow path (diagnostic form; the engine uses the list form below)
 	wg_cycle<NMAX, T>(P, b, sm);
+}
+// kinematic trees: the only cycle kernel they have (the lane / eight-lane / wavefront kernels scan along a chain)
+template <int NMAX, int T>
+__global__ void __launch_bounds__(T) saip_cycle_wg_tree(const CycleParams P) {
+	__shared__ WgSmem<NMAX> sm;
+	const int b = blockIdx.x;
+	if (b >= P.B) return;
+	wg_cycle<NMAX, T, true>(P, b, sm);
 }
 // Device-side slow path behind the lane / eight-lane kernels: a fixed grid strides over the list of instances those kernels could not
 // finish (CycleParams::flag_list).  No host round trip; when the list is empty every workgroup reads the count and leaves.
@@ -92,6 +101,51 @@ __global__ void saip_reinit_kernel(const CycleParams P) {
 		}
 	}
 }
+// kinematic trees
+__global__ void saip_reinit_tree_kernel(const CycleParams P) {
+	const int b = blockIdx.x * blockDim.x + threadIdx.x;
+	if (b >= P.B) return;
+	const ModelDev& md = *P.model;
+	const int n = P.n;
+	const int mask = P.reinit_mask;
+	for (int t = 0; t < P.nt; t++) {
+		if (P.reinit_task >= 0 && t != P.reinit_task) continue;
+		const TaskDev& tk = P.tasks[t];
+		if (tk.type == TASK_MOTION_FORCE) {
+			double pw[3], Rc[9];
+			fk_control_frame_tree(md, tk, P.q, P.ld, b, pw, Rc);
+			if (mask & 1) {  // linear part: goal position := current, velocity/acceleration := 0, integrator := 0
+				for (int e = 0; e < 3; e++) {
+					tk.goal[(size_t)e * P.ld + b] = pw[e];
+					tk.goal[(size_t)(12 + e) * P.ld + b] = 0.0;
+					tk.goal[(size_t)(18 + e) * P.ld + b] = 0.0;
+					tk.integ[(size_t)e * P.ld + b] = 0.0;
+					tk.integ[(size_t)(6 + e) * P.ld + b] = 0.0;  // force integrator (resetIntegratorsLinear)
+				}
+			}
+			if (mask & 2) {  // angular part
+				for (int e = 0; e < 9; e++) tk.goal[(size_t)(3 + e) * P.ld + b] = Rc[e];
+				for (int e = 0; e < 3; e++) {
+					tk.goal[(size_t)(15 + e) * P.ld + b] = 0.0;
+					tk.goal[(size_t)(21 + e) * P.ld + b] = 0.0;
+					tk.integ[(size_t)(3 + e) * P.ld + b] = 0.0;
+					tk.integ[(size_t)(9 + e) * P.ld + b] = 0.0;  // moment integrator (resetIntegratorsAngular)
+				}
+			}
+			if (mask & 4)  // goal force / moment (reInitializeTask, MotionForceTask.cpp:232-237)
+				for (int e = 24; e < 36; e++) tk.goal[(size_t)e * P.ld + b] = 0.0;  // goal and sensed force / moment
+		} else {
+			for (int i = 0; i < tk.m; i++) {
+				double cur = 0.0;
+				for (int j = 0; j < n; j++) cur = fma(tk.S[i * n + j], P.q[(size_t)j * P.ld + b], cur);
+				tk.goal[(size_t)i * P.ld + b] = cur;
+				tk.goal[(size_t)(tk.m + i) * P.ld + b] = 0.0;
+				tk.goal[(size_t)(2 * tk.m + i) * P.ld + b] = 0.0;
+				tk.integ[(size_t)i * P.ld + b] = 0.0;
+			}
+		}
+	}
+}
 
 // ---------------------------------------------------------------- host-callable launchers
 hipError_t launch_cycle_wg_list(const CycleParams& P, hipStream_t stream) {
@@ -105,7 +159,13 @@ hipError_t launch_cycle_wg_list(const CycleParams& P, hipStream_t stream) {
 	}
 	return hipGetLastError();
 }
-hipError_t launch_cycle_wg(const CycleParams& P, hipStream_t stream) {
+hipError_t launch_cycle_wg(const CycleParams& P, bool tree, hipStream_t stream) {
+	if (tree) {
+		// the serial kernel's two sizes and block shapes
+		if (P.n <= 8) hipLaunchKernelGGL((saip_cycle_wg_tree<8, 64>), dim3(P.B), dim3(64), 0, stream, P);
+		else hipLaunchKernelGGL((saip_cycle_wg_tree<32, 512>), dim3(P.B), dim3(512), 0, stream, P);
+		return hipGetLastError();
+	}
 	if (P.n <= 8) {
 		hipLaunchKernelGGL((saip_cycle_wg<8, 64>), dim3(P.B), dim3(64), 0, stream, P);
 	} else {
@@ -117,21 +177,26 @@ hipError_t launch_cycle_wg(const CycleParams& P, hipStream_t stream) {
 }
 // current pose of the control frame of one motion-force task (MotionForceTask::getCurrentPosition / getCurrentOrientation): out = [12][ld],
 // rows 0..2 position, 3..11 rotation (row-major)
-__global__ void saip_pose_kernel(const CycleParams P, const int task, double* out) {
+template <bool TREE>
+__device__ __forceinline__ void pose_body(const CycleParams& P, const int task, double* out) {
 	const int b = blockIdx.x * blockDim.x + threadIdx.x;
 	if (b >= P.B) return;
 	double pw[3], Rc[9];
-	fk_control_frame(*P.model, P.tasks[task], P.q, P.ld, b, pw, Rc);
+	fk_control_frame_t<TREE>(*P.model, P.tasks[task], P.q, P.ld, b, pw, Rc);
 	for (int e = 0; e < 3; e++) out[(size_t)e * P.ld + b] = pw[e];
 	for (int e = 0; e < 9; e++) out[(size_t)(3 + e) * P.ld + b] = Rc[e];
 }
-hipError_t launch_pose(const CycleParams& P, int task, double* out, hipStream_t stream) {
-	hipLaunchKernelGGL(saip_pose_kernel, dim3((P.B + 63) / 64), dim3(64), 0, stream, P, task, out);
+__global__ void saip_pose_kernel(const CycleParams P, const int task, double* out) { pose_body<false>(P, task, out); }
+__global__ void saip_pose_tree_kernel(const CycleParams P, const int task, double* out) { pose_body<true>(P, task, out); }
+hipError_t launch_pose(const CycleParams& P, int task, double* out, bool tree, hipStream_t stream) {
+	if (tree) hipLaunchKernelGGL(saip_pose_tree_kernel, dim3((P.B + 63) / 64), dim3(64), 0, stream, P, task, out);
+	else hipLaunchKernelGGL(saip_pose_kernel, dim3((P.B + 63) / 64), dim3(64), 0, stream, P, task, out);
 	return hipGetLastError();
 }
 
-hipError_t launch_reinit(const CycleParams& P, hipStream_t stream) {
-	hipLaunchKernelGGL(saip_reinit_kernel, dim3((P.B + 63) / 64), dim3(64), 0, stream, P);
+hipError_t launch_reinit(const CycleParams& P, bool tree, hipStream_t stream) {
+	if (tree) hipLaunchKernelGGL(saip_reinit_tree_kernel, dim3((P.B + 63) / 64), dim3(64), 0, stream, P);
+	else hipLaunchKernelGGL(saip_reinit_kernel, dim3((P.B + 63) / 64), dim3(64), 0, stream, P);
 	return hipGetLastError();
 }
 

@@ -1235,7 +1235,8 @@ __device__ __forceinline__ void cart_set_goal_position(const Grp<GS>& g, Lane& L
 
 // mode 0: one control cycle (MotionForceTask.cpp:394-406).  mode 1 | (mask << 4): reInitialize (mask 3), reInitializeLinear
 // (mask 1), reInitializeAngular (mask 2) at the current pose of the control frame (OTG_6dof_cartesian.cpp:46-84).
-template <bool JERK = false>
+// TREE: the robot is a kinematic tree (the re-initialisation walks the ancestors of the task's body only)
+template <bool JERK = false, bool TREE = false>
 __device__ __forceinline__ void otg_cartesian_body(const OtgDev& O, const int B, const int ld, const int mode, const int block) {
 	constexpr int GS = 8;
 	const Grp<GS> g;
@@ -1269,7 +1270,7 @@ __device__ __forceinline__ void otg_cartesian_body(const OtgDev& O, const int B,
 		const int mask = mode >> 4;
 		double pw[3];
 		M3 Rc;
-		fk_control_frame(*O.model, *O.task, O.q, ld, (int)ib, pw, Rc.m);
+		fk_control_frame_t<TREE>(*O.model, *O.task, O.q, ld, (int)ib, pw, Rc.m);
 		if (!(flags & OTG_FLAG_STATE_VALID)) F.ref = Rc;  // constructor: _reference_frame = initial_orientation (:41), _output zero (:39)
 		if (mask & 1) cart_set_goal_position<GS>(g, L, flags, pw, zero3);
 		if (mask & 2) cart_set_goal_orientation<GS>(g, act, L, F, flags, Rc, zero3);
@@ -1387,6 +1388,12 @@ __global__ void __launch_bounds__(256) saip_otg3_joints(const OtgDev O, int B, i
 __global__ void __launch_bounds__(256) saip_otg3_cartesian(const OtgDev O, int B, int ld, int mode) {
 	otg_cartesian_body<true>(O, B, ld, mode, blockIdx.x);
 }
+__global__ void __launch_bounds__(256) saip_otg_cartesian_tree(const OtgDev O, int B, int ld, int mode) {
+	otg_cartesian_body<false, true>(O, B, ld, mode, blockIdx.x);
+}
+__global__ void __launch_bounds__(256) saip_otg3_cartesian_tree(const OtgDev O, int B, int ld, int mode) {
+	otg_cartesian_body<true, true>(O, B, ld, mode, blockIdx.x);
+}
 // One launch for the two OTGs of a { MotionForceTask, JointTask } stack in their cycle mode: they are independent and each is a few
 // latency-bound wavefronts, so the second launch only added its latency.  Workgroups [0, grid_c) run the Cartesian OTG, the rest the
 // joint OTG (8-lane groups).
@@ -1428,9 +1435,14 @@ hipError_t launch_integrate_otg_pair(const SimParams& S, const OtgDev& Oc, const
 	return hipGetLastError();
 }
 
-hipError_t launch_otg_cartesian(const OtgDev& O, int B, int ld, int mode, hipStream_t stream) {
+hipError_t launch_otg_cartesian(const OtgDev& O, int B, int ld, int mode, bool tree, hipStream_t stream) {
 	const int block = 256;
 	const int grid = (int)(((long long)O.lanes + block - 1) / block);
+	if (tree && (mode & 15) == 1) {  // the cycle mode reads no kinematics: trees share the serial kernels there
+		if (O.jerk) hipLaunchKernelGGL(saip_otg3_cartesian_tree, dim3(grid), dim3(block), 0, stream, O, B, ld, mode);
+		else hipLaunchKernelGGL(saip_otg_cartesian_tree, dim3(grid), dim3(block), 0, stream, O, B, ld, mode);
+		return hipGetLastError();
+	}
 	if (O.jerk) hipLaunchKernelGGL(saip_otg3_cartesian, dim3(grid), dim3(block), 0, stream, O, B, ld, mode);
 	else hipLaunchKernelGGL(saip_otg_cartesian, dim3(grid), dim3(block), 0, stream, O, B, ld, mode);
 	return hipGetLastError();

@@ -1,4 +1,4 @@
-// Rigid-body kinematics and dynamics of one serial-chain instance in world coordinates, one lane per instance: forward kinematics,
+// Rigid-body kinematics and dynamics of one robot instance (serial chain; the *_tree variants below for kinematic trees) in world coordinates, one lane per instance: forward kinematics,
 // recursive Newton-Euler and the composite-rigid-body mass matrix.  Shared by the forward-dynamics step (saip_dynamics.hip) and the
 // joint-space model queries (saip_model_query.hip).
 #pragma once
@@ -110,6 +110,92 @@ __device__ void rnea(const ModelDev& md, int n, const Chain<NMAX>& K, const doub
 	}
 }
 
+// kinematic tree: body j starts from its parent's frame (ModelDev::parent, the base when -1)
+template <int NMAX>
+__device__ void chain_fk_tree(const ModelDev& md, int n, const double* q, Chain<NMAX>& K) {
+	for (int j = 0; j < n; j++) {
+		const int pa = md.parent[j];
+		double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+		V3 o = v3(0, 0, 0);
+		if (pa >= 0) {
+			for (int e = 0; e < 9; e++) R[e] = K.R[pa][e];
+			o = K.o[pa];
+		}
+		o = o + mulR(R, v3(md.p0[j][0], md.p0[j][1], md.p0[j][2]));
+		double Rt[9];
+		for (int r = 0; r < 3; r++)
+			for (int c = 0; c < 3; c++) Rt[3 * r + c] = R[3 * r] * md.R0[j][c] + R[3 * r + 1] * md.R0[j][3 + c] + R[3 * r + 2] * md.R0[j][6 + c];
+		const double ax = md.axis[j][0], ay = md.axis[j][1], az = md.axis[j][2];
+		if (md.jtype[j] == 1) {
+			double s, c;
+			sincos(q[j], &s, &c);
+			const double v = 1.0 - c;
+			const double Rq[9] = {c + ax * ax * v,      ax * ay * v - az * s, ax * az * v + ay * s,
+								  ay * ax * v + az * s, c + ay * ay * v,      ay * az * v - ax * s,
+								  az * ax * v - ay * s, az * ay * v + ax * s, c + az * az * v};
+			for (int r = 0; r < 3; r++)
+				for (int c2 = 0; c2 < 3; c2++) R[3 * r + c2] = Rt[3 * r] * Rq[c2] + Rt[3 * r + 1] * Rq[3 + c2] + Rt[3 * r + 2] * Rq[6 + c2];
+		} else {
+			for (int e = 0; e < 9; e++) R[e] = Rt[e];
+			o = o + q[j] * mulR(R, v3(ax, ay, az));
+		}
+		for (int e = 0; e < 9; e++) K.R[j][e] = R[e];
+		K.o[j] = o;
+		K.z[j] = mulR(R, v3(ax, ay, az));
+		K.c[j] = o + mulR(R, v3(md.com[j][0], md.com[j][1], md.com[j][2]));
+	}
+}
+
+// Recursive Newton-Euler on a kinematic tree: the forward pass keeps w, alpha, a (at the joint origin) per body and starts each body from its
+// parent's; the backward pass adds each body's transmitted wrench, shifted from o_j to o_parent, into its parent.
+template <int NMAX>
+__device__ void rnea_tree(const ModelDev& md, int n, const Chain<NMAX>& K, const double* dq, const double* ddq, V3 a0, bool with_velocity, double* tau) {
+	V3 W[NMAX], AL[NMAX], A[NMAX];  // per body: angular velocity, angular acceleration, linear acceleration of the joint origin
+	V3 F[NMAX], N[NMAX];            // force / moment (about o_j) transmitted through joint j
+	for (int j = 0; j < n; j++) {
+		const int pa = md.parent[j];
+		V3 w = v3(0, 0, 0), al = v3(0, 0, 0), a = a0, op = v3(0, 0, 0);
+		if (pa >= 0) {
+			w = W[pa];
+			al = AL[pa];
+			a = A[pa];
+			op = K.o[pa];
+		}
+		const V3 r = K.o[j] - op;  // from the parent's joint origin (rigidly attached to the parent body) to this one
+		a = a + cross(al, r);
+		if (with_velocity) a = a + cross(w, cross(w, r));
+		const V3 z = K.z[j];
+		if (md.jtype[j] == 1) {
+			if (with_velocity) al = al + dq[j] * cross(w, z);
+			al = al + ddq[j] * z;
+			if (with_velocity) w = w + dq[j] * z;
+		} else {
+			if (with_velocity) a = a + 2.0 * dq[j] * cross(w, z);
+			a = a + ddq[j] * z;
+		}
+		W[j] = w;
+		AL[j] = al;
+		A[j] = a;
+		const V3 rc = K.c[j] - K.o[j];
+		V3 ac = a + cross(al, rc);
+		if (with_velocity) ac = ac + cross(w, cross(w, rc));
+		const V3 f = md.mass[j] * ac;
+		V3 nn = inertia_mul(K.R[j], md.inertia[j], al);
+		if (with_velocity) nn = nn + cross(w, inertia_mul(K.R[j], md.inertia[j], w));
+		F[j] = f;
+		N[j] = nn + cross(rc, f);
+	}
+	for (int jj = 0; jj < n; jj++) {
+		const int j = n - 1 - jj;  // every child of j (index > j) has already added its wrench
+		tau[j] = md.jtype[j] == 1 ? dot(K.z[j], N[j]) : dot(K.z[j], F[j]);
+		const int pa = md.parent[j];
+		if (pa >= 0) {
+			F[pa] = F[pa] + F[j];
+			N[pa] = N[pa] + N[j] + cross(K.o[j] - K.o[pa], F[j]);
+		}
+	}
+}
+
 }  // namespace
 
 // Joint-space inertia from composite rigid bodies in world coordinates (serial chain: every later body is a descendant).
@@ -160,6 +246,64 @@ __device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, const int n,
 			const V3 wi = ri ? K.z[i] : v3(0, 0, 0);
 			const V3 vi = ri ? cross(K.o[i], K.z[i]) : K.z[i];
 			const double v = dot(wi, L) + dot(vi, p);
+			M[i][j] = v;
+			M[j][i] = v;
+		}
+	}
+}
+
+// mass_matrix_crb of a kinematic tree: the composite of body j sums its subtree (ModelDev::desc) and M_ij, i < j, is nonzero only for i an
+// ancestor of j (ModelDev::anc)
+template <int NMAX>
+__device__ void mass_matrix_crb_tree(const ModelDev& md, const int n, const Chain<NMAX>& K, double (&M)[NMAX][NMAX]) {
+	double bm[NMAX], bI[NMAX][6];
+	V3 bh[NMAX];
+	for (int j = 0; j < n; j++) {  // spatial inertia of body j about the world origin
+		const double m = md.mass[j];
+		const V3 c = K.c[j];
+		const double* R = K.R[j];
+		const double* I6 = md.inertia[j];
+		double RI[9];
+		for (int r = 0; r < 3; r++) {
+			RI[3 * r + 0] = R[3 * r] * I6[0] + R[3 * r + 1] * I6[3] + R[3 * r + 2] * I6[4];
+			RI[3 * r + 1] = R[3 * r] * I6[3] + R[3 * r + 1] * I6[1] + R[3 * r + 2] * I6[5];
+			RI[3 * r + 2] = R[3 * r] * I6[4] + R[3 * r + 1] * I6[5] + R[3 * r + 2] * I6[2];
+		}
+		const double cc = dot(c, c);
+		bI[j][0] = RI[0] * R[0] + RI[1] * R[1] + RI[2] * R[2] + m * (cc - c.x * c.x);
+		bI[j][1] = RI[3] * R[3] + RI[4] * R[4] + RI[5] * R[5] + m * (cc - c.y * c.y);
+		bI[j][2] = RI[6] * R[6] + RI[7] * R[7] + RI[8] * R[8] + m * (cc - c.z * c.z);
+		bI[j][3] = RI[0] * R[3] + RI[1] * R[4] + RI[2] * R[5] - m * c.x * c.y;
+		bI[j][4] = RI[0] * R[6] + RI[1] * R[7] + RI[2] * R[8] - m * c.x * c.z;
+		bI[j][5] = RI[3] * R[6] + RI[4] * R[7] + RI[5] * R[8] - m * c.y * c.z;
+		bm[j] = m;
+		bh[j] = m * c;
+	}
+	for (int j = 0; j < n; j++) {
+		double cm = 0.0, cI[6] = {0, 0, 0, 0, 0, 0};
+		V3 ch = v3(0, 0, 0);
+		const uint32_t dm = md.desc[j];
+		for (int l = j; l < n; l++) {
+			if (!((dm >> l) & 1u)) continue;
+			cm += bm[l];
+			ch = ch + bh[l];
+			for (int e = 0; e < 6; e++) cI[e] += bI[l][e];
+		}
+		const bool rev = md.jtype[j] == 1;
+		const V3 wj = rev ? K.z[j] : v3(0, 0, 0);
+		const V3 vj = rev ? cross(K.o[j], K.z[j]) : K.z[j];
+		const V3 p = cm * vj + cross(wj, ch);
+		const V3 L = v3(cI[0] * wj.x + cI[3] * wj.y + cI[4] * wj.z, cI[3] * wj.x + cI[1] * wj.y + cI[5] * wj.z, cI[4] * wj.x + cI[5] * wj.y + cI[2] * wj.z) +
+					 cross(ch, vj);
+		const uint32_t am = md.anc[j];
+		for (int i = 0; i <= j; i++) {
+			double v = 0.0;
+			if ((am >> i) & 1u) {
+				const bool ri = md.jtype[i] == 1;
+				const V3 wi = ri ? K.z[i] : v3(0, 0, 0);
+				const V3 vi = ri ? cross(K.o[i], K.z[i]) : K.z[i];
+				v = dot(wi, L) + dot(vi, p);
+			}
 			M[i][j] = v;
 			M[j][i] = v;
 		}

@@ -67,8 +67,10 @@ struct WgSmem {
 	int bieIdx[9];
 };
 
-// one control cycle (or one task's model / torque half, CycleParams::single_task) of instance b by the calling workgroup
-template <int NMAX, int T>
+// one control cycle (or one task's model / torque half, CycleParams::single_task) of instance b by the calling workgroup.
+// TREE: the robot is a kinematic tree (ModelDev::is_tree); the four places that follow the topology read it from the model, the serial
+// instantiation is the chain code.
+template <int NMAX, int T, bool TREE = false>
 __device__ __forceinline__ void wg_cycle(const CycleParams& P, const int b, WgSmem<NMAX>& sm) {
 	using SM = WgSmem<NMAX>;
 	constexpr int LD = SM::LD;
@@ -117,6 +119,38 @@ __device__ __forceinline__ void wg_cycle(const CycleParams& P, const int b, WgSm
 	// log-step prefix product: T_j <- T_{j-d} o T_j,  (Ra,oa) o (Rb,ob) = (Ra Rb, oa + Ra ob)
 	double* fk = sm.fkA;
 	double* fk2 = sm.fkB;
+	if constexpr (TREE) {
+		// pointer jumping: T_j <- T_{jump_r(j)} o T_j with jump_r(j) the 2^r-th ancestor of j (j - 2^r on a chain).  After round r, T_j
+		// composes the 2^(r+1) bodies ending at j, or every body from the base when j is not that deep; depth <= n, so the chain's
+		// rounds suffice
+		int rr = 0;
+		for (int d = 1; d < n; d <<= 1, rr++) {
+			const int* jmp = md.jump[rr];
+			for (int e = tid; e < n * 12; e += T) {
+				int j = e / 12, c = e - 12 * j;
+				const double* Xb = fk + 12 * j;
+				const int a = jmp[j];
+				double val;
+				if (a < 0) {
+					val = Xb[c];
+				} else {
+					const double* Xa = fk + 12 * a;
+					if (c < 9) {
+						int r = c / 3, cc = c - 3 * r;
+						val = Xa[3 * r] * Xb[cc] + Xa[3 * r + 1] * Xb[3 + cc] + Xa[3 * r + 2] * Xb[6 + cc];
+					} else {
+						int r = c - 9;
+						val = Xa[9 + r] + Xa[3 * r] * Xb[9] + Xa[3 * r + 1] * Xb[10] + Xa[3 * r + 2] * Xb[11];
+					}
+				}
+				fk2[e] = val;
+			}
+			SYNC();
+			double* t_ = fk;
+			fk = fk2;
+			fk2 = t_;
+		}
+	} else
 	for (int d = 1; d < n; d <<= 1) {
 		for (int e = tid; e < n * 12; e += T) {
 			int j = e / 12, c = e - 12 * j;
@@ -172,20 +206,34 @@ __device__ __forceinline__ void wg_cycle(const CycleParams& P, const int b, WgSm
 		Bd[9] = Iw[5] - m * c[1] * c[2];
 	}
 	SYNC();
-	// composite inertias: suffix sums (plain sums, everything is expressed about the world origin)
+	// composite inertias: suffix sums (plain sums, everything is expressed about the world origin); on a tree, over the subtree in ascending
+	// order (a chain's subtree of j is j..n-1: the same sum)
 	for (int e = tid; e < n * 10; e += T) {
 		int j = e / 10, c = e - 10 * j;
 		double s = 0.0;
-		for (int l = j; l < n; l++) s += sm.body[10 * l + c];
+		if constexpr (TREE) {
+			const uint32_t dm = md.desc[j];
+			for (int l = j; l < n; l++)
+				if ((dm >> l) & 1u) s += sm.body[10 * l + c];
+		} else {
+			for (int l = j; l < n; l++) s += sm.body[10 * l + c];
+		}
 		sm.comp[e] = s;
 	}
 	SYNC();
-	// ---------------------------------------------------------------- M(q): M_ij = S_i . (Ic_j S_j), i <= j
+	// ---------------------------------------------------------------- M(q): M_ij = S_i . (Ic_j S_j), i <= j (on a tree: i an ancestor of j, else 0)
 	double* Mm = sm.W[0];
 	double* MB = sm.W[1];
 	for (int e = tid; e < n * n; e += T) {
 		int i = divn(e), j = e - i * n;
 		if (i > j) continue;
+		if constexpr (TREE) {
+			if (!((md.anc[j] >> i) & 1u)) {
+				Mm[i * LD + j] = 0.0;
+				Mm[j * LD + i] = 0.0;
+				continue;
+			}
+		}
 		const double* Ic = sm.comp + 10 * j;
 		const double* zj = sm.zax + 3 * j;
 		const double* oj = fk + 12 * j + 9;
@@ -313,7 +361,10 @@ __device__ __forceinline__ void wg_cycle(const CycleParams& P, const int b, WgSm
 			}
 			for (int j = tid; j < n; j += T) {
 				double col[6] = {0, 0, 0, 0, 0, 0};
-				if (j <= bd) {
+				bool on_path;  // joint j moves the control frame: it lies on the path from the base to body bd
+				if constexpr (TREE) on_path = bd >= 0 && ((md.anc[bd] >> j) & 1u);
+				else on_path = j <= bd;
+				if (on_path) {
 					const double* z = sm.zax + 3 * j;
 					if (md.jtype[j] == 1) {
 						const double* o = fk + 12 * j + 9;
@@ -830,7 +881,7 @@ __device__ __forceinline__ void wg_cycle(const CycleParams& P, const int b, WgSm
 			SYNC();
 			if (do_state && tid < 2 * nsg) {
 				double x1[3], R1[9], w6[6] = {0, 0, 0, 0, 0, 0};
-				fk_control_frame(md, tk, qp + tid * n, 1, 0, x1, R1);
+				fk_control_frame_t<TREE>(md, tk, qp + tid * n, 1, 0, x1, R1);
 				for (int e = 0; e < 3; e++) w6[e] = x1[e] - sm.xp[e];
 				for (int col = 0; col < 3; col++) {  // orientation error of R1 with respect to Rc
 					const double a0 = sm.Rc[col], a1 = sm.Rc[3 + col], a2 = sm.Rc[6 + col];
@@ -1154,7 +1205,8 @@ __device__ __forceinline__ void wg_cycle(const CycleParams& P, const int b, WgSm
 	if (tid < n) {
 		double tv = sm.tau[tid];
 		if (P.gravity_comp) {
-			// jointGravityVector: tau_g[j] = -(d c_com / d q_j) . (m g) summed over the subtree = -S_j . (composite gravity wrench)
+			// jointGravityVector: tau_g[j] = -(d c_com / d q_j) . (m g) summed over the subtree = -S_j . (composite gravity wrench); comp is the
+			// subtree's composite on a tree as well
 			const double* Ic = sm.comp + 10 * tid;
 			const double* z = sm.zax + 3 * tid;
 			const double* o = fk + 12 * tid + 9;
