@@ -19,7 +19,9 @@
 
 namespace saip {
 
-template <int NMAX>
+// TREE: kinematic trees (ModelDev::is_tree) -- the same step with the tree traversals of saip_rbd.h; every integrate path of the engine lands
+// here for them, whatever the dof
+template <int NMAX, bool TREE>
 __global__ void __launch_bounds__(64) saip_integrate_kernel(const SimParams S) {
 	const int b = blockIdx.x * blockDim.x + threadIdx.x;
 	if (b >= S.B) return;
@@ -39,84 +41,12 @@ __global__ void __launch_bounds__(64) saip_integrate_kernel(const SimParams S) {
 	const V3 a0 = v3(-S.gravity[0], -S.gravity[1], -S.gravity[2]);
 	Chain<NMAX> K;
 	for (int step = 0; step < S.substeps; step++) {
-		chain_fk<NMAX>(md, n, q, K);
-		rnea<NMAX>(md, n, K, dq, e, a0, true, h);  // b(q, dq) + g(q)
-		mass_matrix_crb<NMAX>(md, n, K, M);
-		// Cholesky M = L L^T (lower, in place), then two triangular solves
-#pragma unroll
-		for (int k = 0; k < n; k++) {
-			double d = M[k][k];
-#pragma unroll
-			for (int l = 0; l < n; l++)
-				if (l < k) d -= M[k][l] * M[k][l];
-			d = sqrt(d);
-			M[k][k] = d;
-			const double rd = 1.0 / d;
-#pragma unroll
-			for (int i = 0; i < n; i++) {
-				if (i <= k) continue;
-				double s = M[i][k];
-#pragma unroll
-				for (int l = 0; l < n; l++)
-					if (l < k) s -= M[i][l] * M[k][l];
-				M[i][k] = s * rd;
-			}
-		}
-#pragma unroll
-		for (int i = 0; i < n; i++) {
-			double s = tau[i] - h[i] - S.damping * dq[i];
-#pragma unroll
-			for (int l = 0; l < n; l++)
-				if (l < i) s -= M[i][l] * ddq[l];
-			ddq[i] = s / M[i][i];
-		}
-#pragma unroll
-		for (int ii = 0; ii < n; ii++) {
-			const int i = n - 1 - ii;
-			double s = ddq[i];
-#pragma unroll
-			for (int l = 0; l < n; l++)
-				if (l > i) s -= M[l][i] * ddq[l];
-			ddq[i] = s / M[i][i];
-		}
-#pragma unroll
-		for (int j = 0; j < n; j++) {
-			dq[j] += S.dt * ddq[j];
-			q[j] += S.dt * dq[j];
-		}
-	}
-#pragma unroll
-	for (int j = 0; j < n; j++) {
-		S.q[(size_t)j * S.ld + b] = q[j];
-		S.dq[(size_t)j * S.ld + b] = dq[j];
-		if (S.ddq) S.ddq[(size_t)j * S.ld + b] = ddq[j];
-	}
-}
-// kinematic trees (ModelDev::is_tree): the step above with the saip_rbd.h *_tree routines; every integrate path of the engine lands here for
-// them, whatever the dof
-template <int NMAX>
-__global__ void __launch_bounds__(64) saip_integrate_tree(const SimParams S) {
-	const int b = blockIdx.x * blockDim.x + threadIdx.x;
-	if (b >= S.B) return;
-	const ModelDev& md = *S.model;
-	const int n = S.n;
-	double q[NMAX], dq[NMAX], tau[NMAX], h[NMAX], ddq[NMAX], e[NMAX];
-	double M[NMAX][NMAX];
-#pragma unroll
-	for (int j = 0; j < n; j++) {
-		q[j] = S.q[(size_t)j * S.ld + b];
-		dq[j] = S.dq[(size_t)j * S.ld + b];
-		tau[j] = S.tau[(size_t)j * S.ld + b];
-		if (!(tau[j] == tau[j])) tau[j] = 0.0;  // flagged instances (NaN torques) coast
-		e[j] = 0.0;
-		ddq[j] = 0.0;
-	}
-	const V3 a0 = v3(-S.gravity[0], -S.gravity[1], -S.gravity[2]);
-	Chain<NMAX> K;
-	for (int step = 0; step < S.substeps; step++) {
-		chain_fk_tree<NMAX>(md, n, q, K);
-		rnea_tree<NMAX>(md, n, K, dq, e, a0, true, h);  // b(q, dq) + g(q)
-		mass_matrix_crb_tree<NMAX>(md, n, K, M);
+		if constexpr (TREE) chain_fk_tree<NMAX>(md, n, q, K);
+		else chain_fk<NMAX>(md, n, q, K);
+		if constexpr (TREE) rnea_tree<NMAX>(md, n, K, dq, e, a0, true, h);  // b(q, dq) + g(q)
+		else rnea<NMAX>(md, n, K, dq, e, a0, true, h);
+		if constexpr (TREE) mass_matrix_crb_tree<NMAX>(md, n, K, M);
+		else mass_matrix_crb<NMAX>(md, n, K, M);
 		// Cholesky M = L L^T (lower, in place), then two triangular solves
 #pragma unroll
 		for (int k = 0; k < n; k++) {
@@ -173,16 +103,16 @@ hipError_t launch_integrate_oct(const SimParams& S, hipStream_t stream);  // sai
 hipError_t launch_integrate(const SimParams& S, bool tree, hipStream_t stream) {
 	if (tree) {
 		const int grid = (S.B + 63) / 64;
-		if (S.n <= 8) hipLaunchKernelGGL((saip_integrate_tree<8>), dim3(grid), dim3(64), 0, stream, S);
-		else hipLaunchKernelGGL((saip_integrate_tree<32>), dim3(grid), dim3(64), 0, stream, S);
+		if (S.n <= 8) hipLaunchKernelGGL((saip_integrate_kernel<8, true>), dim3(grid), dim3(64), 0, stream, S);
+		else hipLaunchKernelGGL((saip_integrate_kernel<32, true>), dim3(grid), dim3(64), 0, stream, S);
 		return hipGetLastError();
 	}
 	// 7-dof chains: the eight-lanes-per-instance kernel is faster at every batch size measured (8.7 vs 33.4 us at 4096, 46.8 vs 81.1 us at
 	// 65 536, 166 vs 218 us at 262 144 per two substeps)
 	if (S.n == 7) return launch_integrate_oct(S, stream);
 	const int grid = (S.B + 63) / 64;
-	if (S.n <= 8) hipLaunchKernelGGL((saip_integrate_kernel<8>), dim3(grid), dim3(64), 0, stream, S);
-	else hipLaunchKernelGGL((saip_integrate_kernel<32>), dim3(grid), dim3(64), 0, stream, S);
+	if (S.n <= 8) hipLaunchKernelGGL((saip_integrate_kernel<8, false>), dim3(grid), dim3(64), 0, stream, S);
+	else hipLaunchKernelGGL((saip_integrate_kernel<32, false>), dim3(grid), dim3(64), 0, stream, S);
 	return hipGetLastError();
 }
 

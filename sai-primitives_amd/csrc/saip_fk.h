@@ -67,9 +67,14 @@ __device__ __forceinline__ void fk_mat3_vec(const double* R, const double* v, do
 		for (int e = 0; e < 9; e++) Rn[e] = Rt[e];                                                                                              \
 	}                                                                                                                                           \
 	for (int e = 0; e < 9; e++) R[e] = Rn[e];
-#define SAIP_FK_WALK(...)                                                                                                                       \
+// TREE (a compile-time bool): a kinematic tree -- the same steps over the ancestors of the body only, in ascending order (a joint's origin is
+// expressed in its parent body's frame, and every ancestor comes before its descendants)
+#define SAIP_FK_WALK(TREE, ...)                                                                                                                 \
 	double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};                                                                                \
+	const uint32_t anc_ = TREE && tk.body >= 0 ? md.anc[tk.body] : 0u;                                                                          \
 	for (int j = 0; j <= tk.body; j++) {                                                                                                        \
+		if constexpr (TREE)                                                                                                                     \
+			if (!((anc_ >> j) & 1u)) continue;                                                                                                  \
 		SAIP_FK_JOINT_STEP(__VA_ARGS__)                                                                                                         \
 	}                                                                                                                                           \
 	double p[3];                                                                                                                                \
@@ -78,35 +83,38 @@ __device__ __forceinline__ void fk_mat3_vec(const double* R, const double* v, do
 	for (int r = 0; r < 3; r++)                                                                                                                 \
 		for (int c = 0; c < 3; c++) Rc[3 * r + c] = R[3 * r] * tk.rot[c] + R[3 * r + 1] * tk.rot[3 + c] + R[3 * r + 2] * tk.rot[6 + c];
 
-// world position of the control point and world rotation of the control frame of motion-force task tk
+// world position of the control point and world rotation of the control frame of motion-force task tk; the two instantiations keep their names
 __device__ inline void fk_control_frame(const ModelDev& md, const TaskDev& tk, const double* q, int ld, int b, double pos[3], double Rc[9]) {
-	SAIP_FK_WALK()
+	SAIP_FK_WALK(false)
 }
-
-// SAIP_FK_WALK of a kinematic tree: the same steps over the ancestors of the body only, in ascending order (a joint's origin is expressed in
-// its parent body's frame, and every ancestor comes before its descendants)
-#define SAIP_FK_WALK_TREE(...)                                                                                                                  \
-	double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};                                                                                \
-	const uint32_t anc_ = tk.body >= 0 ? md.anc[tk.body] : 0u;                                                                                  \
-	for (int j = 0; j <= tk.body; j++) {                                                                                                        \
-		if (!((anc_ >> j) & 1u)) continue;                                                                                                      \
-		SAIP_FK_JOINT_STEP(__VA_ARGS__)                                                                                                         \
-	}                                                                                                                                           \
-	double p[3];                                                                                                                                \
-	fk_mat3_vec(R, tk.pos, p);                                                                                                                  \
-	for (int e = 0; e < 3; e++) pos[e] = o[e] + p[e];                                                                                           \
-	for (int r = 0; r < 3; r++)                                                                                                                 \
-		for (int c = 0; c < 3; c++) Rc[3 * r + c] = R[3 * r] * tk.rot[c] + R[3 * r + 1] * tk.rot[3 + c] + R[3 * r + 2] * tk.rot[6 + c];
-
 __device__ inline void fk_control_frame_tree(const ModelDev& md, const TaskDev& tk, const double* q, int ld, int b, double pos[3], double Rc[9]) {
-	SAIP_FK_WALK_TREE()
+	SAIP_FK_WALK(true)
 }
 
-// compile-time choice for the templated kernels (TREE = false is fk_control_frame itself)
+// compile-time choice for the templated kernels
 template <bool TREE>
 __device__ __forceinline__ void fk_control_frame_t(const ModelDev& md, const TaskDev& tk, const double* q, int ld, int b, double pos[3], double Rc[9]) {
 	if constexpr (TREE) fk_control_frame_tree(md, tk, q, ld, b, pos, Rc);
 	else fk_control_frame(md, tk, q, ld, b, pos, Rc);
 }
+
+// Statement for SAIP_FK_JOINT_STEP / SAIP_FK_WALK that accumulates the unprojected world twist of a point p carried by the body walked to
+// (tv, tw, tc, dq_ and ld, b are names in the caller's scope): with aw = Rt (ax, ay, az) the world axis and o the origin of joint j, a
+// revolute joint (rev) adds aw dq to tw and dq (aw x o) to tc, a prismatic joint adds aw dq to tv; at the end v = tv + tw x p - tc and
+// w = tw, since sum_j dq_j aw_j x (p - o_j) = tw x p - tc.  aw and rev stay in scope for what follows (the Jacobian columns).
+#define SAIP_FK_TWIST_STEP(dq_)                                                                                                                 \
+	const double aj[3] = {ax, ay, az};                                                                                                          \
+	const double dqj = (dq_)[(size_t)j * ld + b];                                                                                               \
+	double aw[3];                                                                                                                               \
+	fk_mat3_vec(Rt, aj, aw);                                                                                                                    \
+	const bool rev = md.jtype[j] == 1;                                                                                                          \
+	if (rev) {                                                                                                                                  \
+		for (int e = 0; e < 3; e++) tw[e] += aw[e] * dqj;                                                                                       \
+		tc[0] += dqj * (aw[1] * o[2] - aw[2] * o[1]);                                                                                           \
+		tc[1] += dqj * (aw[2] * o[0] - aw[0] * o[2]);                                                                                           \
+		tc[2] += dqj * (aw[0] * o[1] - aw[1] * o[0]);                                                                                           \
+	} else {                                                                                                                                    \
+		for (int e = 0; e < 3; e++) tv[e] += aw[e] * dqj;                                                                                       \
+	}
 
 }  // namespace saip

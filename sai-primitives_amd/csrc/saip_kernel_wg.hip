@@ -57,6 +57,7 @@ __global__ void __launch_bounds__(T) saip_cycle_wg_list(const CycleParams P) {
 }
 
 // ---------------------------------------------------------------- reInitializeTask: goal := current pose (one lane per instance)
+template <bool TREE>
 __global__ void saip_reinit_kernel(const CycleParams P) {
 	const int b = blockIdx.x * blockDim.x + threadIdx.x;
 	if (b >= P.B) return;
@@ -68,52 +69,7 @@ __global__ void saip_reinit_kernel(const CycleParams P) {
 		const TaskDev& tk = P.tasks[t];
 		if (tk.type == TASK_MOTION_FORCE) {
 			double pw[3], Rc[9];
-			fk_control_frame(md, tk, P.q, P.ld, b, pw, Rc);
-			if (mask & 1) {  // linear part: goal position := current, velocity/acceleration := 0, integrator := 0
-				for (int e = 0; e < 3; e++) {
-					tk.goal[(size_t)e * P.ld + b] = pw[e];
-					tk.goal[(size_t)(12 + e) * P.ld + b] = 0.0;
-					tk.goal[(size_t)(18 + e) * P.ld + b] = 0.0;
-					tk.integ[(size_t)e * P.ld + b] = 0.0;
-					tk.integ[(size_t)(6 + e) * P.ld + b] = 0.0;  // force integrator (resetIntegratorsLinear)
-				}
-			}
-			if (mask & 2) {  // angular part
-				for (int e = 0; e < 9; e++) tk.goal[(size_t)(3 + e) * P.ld + b] = Rc[e];
-				for (int e = 0; e < 3; e++) {
-					tk.goal[(size_t)(15 + e) * P.ld + b] = 0.0;
-					tk.goal[(size_t)(21 + e) * P.ld + b] = 0.0;
-					tk.integ[(size_t)(3 + e) * P.ld + b] = 0.0;
-					tk.integ[(size_t)(9 + e) * P.ld + b] = 0.0;  // moment integrator (resetIntegratorsAngular)
-				}
-			}
-			if (mask & 4)  // goal force / moment (reInitializeTask, MotionForceTask.cpp:232-237)
-				for (int e = 24; e < 36; e++) tk.goal[(size_t)e * P.ld + b] = 0.0;  // goal and sensed force / moment
-		} else {
-			for (int i = 0; i < tk.m; i++) {
-				double cur = 0.0;
-				for (int j = 0; j < n; j++) cur = fma(tk.S[i * n + j], P.q[(size_t)j * P.ld + b], cur);
-				tk.goal[(size_t)i * P.ld + b] = cur;
-				tk.goal[(size_t)(tk.m + i) * P.ld + b] = 0.0;
-				tk.goal[(size_t)(2 * tk.m + i) * P.ld + b] = 0.0;
-				tk.integ[(size_t)i * P.ld + b] = 0.0;
-			}
-		}
-	}
-}
-// kinematic trees
-__global__ void saip_reinit_tree_kernel(const CycleParams P) {
-	const int b = blockIdx.x * blockDim.x + threadIdx.x;
-	if (b >= P.B) return;
-	const ModelDev& md = *P.model;
-	const int n = P.n;
-	const int mask = P.reinit_mask;
-	for (int t = 0; t < P.nt; t++) {
-		if (P.reinit_task >= 0 && t != P.reinit_task) continue;
-		const TaskDev& tk = P.tasks[t];
-		if (tk.type == TASK_MOTION_FORCE) {
-			double pw[3], Rc[9];
-			fk_control_frame_tree(md, tk, P.q, P.ld, b, pw, Rc);
+			fk_control_frame_t<TREE>(md, tk, P.q, P.ld, b, pw, Rc);
 			if (mask & 1) {  // linear part: goal position := current, velocity/acceleration := 0, integrator := 0
 				for (int e = 0; e < 3; e++) {
 					tk.goal[(size_t)e * P.ld + b] = pw[e];
@@ -195,8 +151,8 @@ hipError_t launch_pose(const CycleParams& P, int task, double* out, bool tree, h
 }
 
 hipError_t launch_reinit(const CycleParams& P, bool tree, hipStream_t stream) {
-	if (tree) hipLaunchKernelGGL(saip_reinit_tree_kernel, dim3((P.B + 63) / 64), dim3(64), 0, stream, P);
-	else hipLaunchKernelGGL(saip_reinit_kernel, dim3((P.B + 63) / 64), dim3(64), 0, stream, P);
+	if (tree) hipLaunchKernelGGL(saip_reinit_kernel<true>, dim3((P.B + 63) / 64), dim3(64), 0, stream, P);
+	else hipLaunchKernelGGL(saip_reinit_kernel<false>, dim3((P.B + 63) / 64), dim3(64), 0, stream, P);
 	return hipGetLastError();
 }
 

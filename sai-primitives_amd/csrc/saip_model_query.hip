@@ -88,11 +88,49 @@ __device__ __forceinline__ void frame_emit(const FrameQuery& Q, const ModelDev& 
 
 }  // namespace
 
+// One joint j of a frames walk, expanded in place: SAIP_FK_JOINT_STEP with the twist accumulators and, with Q.jac, column j of the Jacobian
+// -- Jw = z_j and the partial Jv of frame_emit -- stored to frame g, where FRAMES_ declares g: a loop header or one frame.
+#define MQ_FRAME_JOINT_STEP(FRAMES_)                                                                                    \
+	SAIP_FK_JOINT_STEP({                                                                                                \
+		SAIP_FK_TWIST_STEP(Q.dq)                                                                                        \
+		if (Q.jac) {                                                                                                    \
+			double zs[3], os[3], jv[3], jw[3];                                                                          \
+			if (Q.world) {                                                                                              \
+				fk_mat3_vec(Q.Rwb, aw, zs);                                                                             \
+				fk_mat3_vec(Q.Rwb, o, os);                                                                              \
+			} else {                                                                                                    \
+				for (int e = 0; e < 3; e++) {                                                                           \
+					zs[e] = aw[e];                                                                                      \
+					os[e] = o[e];                                                                                       \
+				}                                                                                                       \
+			}                                                                                                           \
+			if (rev) {                                                                                                  \
+				mq_cross(os, zs, jv);                                                                                   \
+				for (int e = 0; e < 3; e++) jw[e] = zs[e];                                                              \
+			} else {                                                                                                    \
+				for (int e = 0; e < 3; e++) {                                                                           \
+					jv[e] = zs[e];                                                                                      \
+					jw[e] = 0.0;                                                                                        \
+				}                                                                                                       \
+			}                                                                                                           \
+			FRAMES_ {                                                                                                   \
+				double* J = Q.out + (size_t)Q.slot[g] * Q.rows * ld + (size_t)(18 + j) * ld + b;                        \
+				const size_t rs = (size_t)n * ld;                                                                       \
+				for (int e = 0; e < 3; e++) {                                                                           \
+					J[e * rs] = jv[e];                                                                                  \
+					J[(3 + e) * rs] = jw[e];                                                                            \
+				}                                                                                                       \
+			}                                                                                                           \
+		}                                                                                                               \
+	})
+
 // out = [nf][rows][ld]: rows 0..2 position, 3..11 rotation (row-major), 12..14 linear velocity, 15..17 angular velocity, 18.. the 6 x n
-// Jacobian [Jv; Jw] row-major.  One walk over the chain for all frames (sorted by body on the host): each frame is emitted as the walk
-// passes its body.  The pose is the arithmetic of fk_control_frame (SAIP_FK_JOINT_STEP): a frame equal to a task's control frame is
-// bit-identical to the pose readback.  The joint axes and origins of the Jacobian are not kept in a per-lane array (runtime-indexed: it
-// would live in scratch): they go straight to the output columns, coalesced across the instances, and are read back once p is known.
+// Jacobian [Jv; Jw] row-major.  Chain: one walk for all frames (sorted by body on the host): each frame is emitted as the walk passes its
+// body.  TREE: one walk per frame over the ancestors of its body (the bodies of two frames need not lie on one path).  The pose is the
+// arithmetic of fk_control_frame (SAIP_FK_JOINT_STEP): a frame equal to a task's control frame is bit-identical to the pose readback, of a
+// tree as well.  The joint axes and origins of the Jacobian are not kept in a per-lane array (runtime-indexed: it would live in scratch):
+// they go straight to the output columns, coalesced across the instances, and are read back once p is known.
+template <bool TREE>
 __global__ void __launch_bounds__(64) saip_model_frames_kernel(const FrameQuery Q) {
 	const int b = blockIdx.x * blockDim.x + threadIdx.x;
 	if (b >= Q.B) return;
@@ -100,119 +138,27 @@ __global__ void __launch_bounds__(64) saip_model_frames_kernel(const FrameQuery 
 	const double* q = Q.q;
 	const size_t ld = Q.ld;
 	const int n = Q.n;
-	double tv[3] = {0, 0, 0}, tw[3] = {0, 0, 0}, tc[3] = {0, 0, 0};
-	double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};
-	int f = 0;
-	for (; f < Q.nf && Q.body[f] < 0; f++) frame_emit(Q, md, f, b, R, o, tv, tw, tc);  // links welded to the fixed base
-	for (int j = 0; f < Q.nf; j++) {
-		SAIP_FK_JOINT_STEP({
-			const double aj[3] = {ax, ay, az};
-			const double dqj = Q.dq[(size_t)j * ld + b];
-			double aw[3];
-			fk_mat3_vec(Rt, aj, aw);
-			const bool rev = md.jtype[j] == 1;
-			if (rev) {
-				for (int e = 0; e < 3; e++) tw[e] += aw[e] * dqj;
-				tc[0] += dqj * (aw[1] * o[2] - aw[2] * o[1]);
-				tc[1] += dqj * (aw[2] * o[0] - aw[0] * o[2]);
-				tc[2] += dqj * (aw[0] * o[1] - aw[1] * o[0]);
-			} else {
-				for (int e = 0; e < 3; e++) tv[e] += aw[e] * dqj;
+	if constexpr (TREE) {
+		for (int f = 0; f < Q.nf; f++) {
+			const int body = Q.body[f];
+			const uint32_t anc = body >= 0 ? md.anc[body] : 0u;
+			double tv[3] = {0, 0, 0}, tw[3] = {0, 0, 0}, tc[3] = {0, 0, 0};
+			double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};
+			for (int j = 0; j <= body; j++) {
+				if (!((anc >> j) & 1u)) continue;
+				MQ_FRAME_JOINT_STEP(const int g = f;)
 			}
-			if (Q.jac) {
-				double zs[3], os[3], jv[3], jw[3];
-				if (Q.world) {
-					fk_mat3_vec(Q.Rwb, aw, zs);
-					fk_mat3_vec(Q.Rwb, o, os);
-				} else {
-					for (int e = 0; e < 3; e++) {
-						zs[e] = aw[e];
-						os[e] = o[e];
-					}
-				}
-				if (rev) {
-					mq_cross(os, zs, jv);
-					for (int e = 0; e < 3; e++) jw[e] = zs[e];
-				} else {
-					for (int e = 0; e < 3; e++) {
-						jv[e] = zs[e];
-						jw[e] = 0.0;
-					}
-				}
-				for (int g = f; g < Q.nf; g++) {  // every frame not emitted yet lies on body j or beyond
-					double* J = Q.out + (size_t)Q.slot[g] * Q.rows * ld + (size_t)(18 + j) * ld + b;
-					const size_t rs = (size_t)n * ld;
-					for (int e = 0; e < 3; e++) {
-						J[e * rs] = jv[e];
-						J[(3 + e) * rs] = jw[e];
-					}
-				}
-			}
-		})
-		for (; f < Q.nf && Q.body[f] == j; f++) frame_emit(Q, md, f, b, R, o, tv, tw, tc);
-	}
-}
-
-// kinematic trees: one walk per frame over the ancestors of its body (the bodies of two frames need not lie on one path).  Per frame, the
-// arithmetic of fk_control_frame_tree, so a frame equal to a task's control frame is bit-identical to the pose readback of a tree as well.
-__global__ void __launch_bounds__(64) saip_model_frames_tree_kernel(const FrameQuery Q) {
-	const int b = blockIdx.x * blockDim.x + threadIdx.x;
-	if (b >= Q.B) return;
-	const ModelDev& md = *Q.model;
-	const double* q = Q.q;
-	const size_t ld = Q.ld;
-	const int n = Q.n;
-	for (int f = 0; f < Q.nf; f++) {
-		const int body = Q.body[f];
-		const uint32_t anc = body >= 0 ? md.anc[body] : 0u;
+			frame_emit<true>(Q, md, f, b, R, o, tv, tw, tc);
+		}
+	} else {
 		double tv[3] = {0, 0, 0}, tw[3] = {0, 0, 0}, tc[3] = {0, 0, 0};
 		double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {0, 0, 0};
-		for (int j = 0; j <= body; j++) {
-			if (!((anc >> j) & 1u)) continue;
-			SAIP_FK_JOINT_STEP({
-				const double aj[3] = {ax, ay, az};
-				const double dqj = Q.dq[(size_t)j * ld + b];
-				double aw[3];
-				fk_mat3_vec(Rt, aj, aw);
-				const bool rev = md.jtype[j] == 1;
-				if (rev) {
-					for (int e = 0; e < 3; e++) tw[e] += aw[e] * dqj;
-					tc[0] += dqj * (aw[1] * o[2] - aw[2] * o[1]);
-					tc[1] += dqj * (aw[2] * o[0] - aw[0] * o[2]);
-					tc[2] += dqj * (aw[0] * o[1] - aw[1] * o[0]);
-				} else {
-					for (int e = 0; e < 3; e++) tv[e] += aw[e] * dqj;
-				}
-				if (Q.jac) {
-					double zs[3], os[3], jv[3], jw[3];
-					if (Q.world) {
-						fk_mat3_vec(Q.Rwb, aw, zs);
-						fk_mat3_vec(Q.Rwb, o, os);
-					} else {
-						for (int e = 0; e < 3; e++) {
-							zs[e] = aw[e];
-							os[e] = o[e];
-						}
-					}
-					if (rev) {
-						mq_cross(os, zs, jv);
-						for (int e = 0; e < 3; e++) jw[e] = zs[e];
-					} else {
-						for (int e = 0; e < 3; e++) {
-							jv[e] = zs[e];
-							jw[e] = 0.0;
-						}
-					}
-					double* J = Q.out + (size_t)Q.slot[f] * Q.rows * ld + (size_t)(18 + j) * ld + b;
-					const size_t rs = (size_t)n * ld;
-					for (int e = 0; e < 3; e++) {
-						J[e * rs] = jv[e];
-						J[(3 + e) * rs] = jw[e];
-					}
-				}
-			})
+		int f = 0;
+		for (; f < Q.nf && Q.body[f] < 0; f++) frame_emit(Q, md, f, b, R, o, tv, tw, tc);  // links welded to the fixed base
+		for (int j = 0; f < Q.nf; j++) {
+			MQ_FRAME_JOINT_STEP(for (int g = f; g < Q.nf; g++))  // every frame not emitted yet lies on body j or beyond
+			for (; f < Q.nf && Q.body[f] == j; f++) frame_emit(Q, md, f, b, R, o, tv, tw, tc);
 		}
-		frame_emit<true>(Q, md, f, b, R, o, tv, tw, tc);
 	}
 }
 
@@ -220,13 +166,14 @@ __global__ void __launch_bounds__(64) saip_model_frames_tree_kernel(const FrameQ
 // no gravity): the routines of the forward-dynamics step (saip_rbd.h), so M qdd + h + g = tau is the model saip_batch_integrate steps.
 // NMAX = 8 walks a chain padded to eight joints: the padding joints of ModelDev are all zero (no mass, no inertia, a zero rotation), add
 // exact zeros, and every loop runs to the compile-time bound -- every per-lane array is statically indexed and stays in registers.
-template <int NMAX>
+// TREE: kinematic trees -- the same queries with the tree traversals of saip_rbd.h.
+template <int NMAX, bool TREE>
 __global__ void __launch_bounds__(64) saip_model_dynamics_kernel(const DynQuery Q) {
 	const int b = blockIdx.x * blockDim.x + threadIdx.x;
 	if (b >= Q.B) return;
 	const ModelDev& md = *Q.model;
 	const int nn = Q.n;
-	const int n = NMAX <= 8 ? NMAX : nn;
+	const int n = TREE ? nn : (NMAX <= 8 ? NMAX : nn);  // (trees are not padded: padding bodies would hang off body 0)
 	const size_t ld = Q.ld;
 	constexpr int U = NMAX <= 8 ? NMAX : 1;  // the 32 instantiation keeps its loops rolled (its arrays live in scratch either way)
 	double q[NMAX], dq[NMAX], zero[NMAX], t[NMAX];
@@ -237,108 +184,26 @@ __global__ void __launch_bounds__(64) saip_model_dynamics_kernel(const DynQuery 
 		zero[j] = 0.0;
 	}
 	Chain<NMAX> K;
-	chain_fk<NMAX>(md, n, q, K);
+	if constexpr (TREE) chain_fk_tree<NMAX>(md, n, q, K);
+	else chain_fk<NMAX>(md, n, q, K);
 	if (Q.g) {
-		rnea<NMAX>(md, n, K, zero, zero, v3(-md.gravity[0], -md.gravity[1], -md.gravity[2]), false, t);
+		if constexpr (TREE) rnea_tree<NMAX>(md, n, K, zero, zero, v3(-md.gravity[0], -md.gravity[1], -md.gravity[2]), false, t);
+		else rnea<NMAX>(md, n, K, zero, zero, v3(-md.gravity[0], -md.gravity[1], -md.gravity[2]), false, t);
 #pragma unroll U
 		for (int j = 0; j < NMAX; j++)
 			if (j < nn) Q.g[(size_t)j * ld + b] = t[j];
 	}
 	if (Q.h) {
-		rnea<NMAX>(md, n, K, dq, zero, v3(0, 0, 0), true, t);
+		if constexpr (TREE) rnea_tree<NMAX>(md, n, K, dq, zero, v3(0, 0, 0), true, t);
+		else rnea<NMAX>(md, n, K, dq, zero, v3(0, 0, 0), true, t);
 #pragma unroll U
 		for (int j = 0; j < NMAX; j++)
 			if (j < nn) Q.h[(size_t)j * ld + b] = t[j];
 	}
 	if (!Q.M && !Q.Minv) return;
 	double M[NMAX][NMAX];
-	mass_matrix_crb<NMAX>(md, n, K, M);
-	if (Q.M) {
-#pragma unroll U
-		for (int i = 0; i < NMAX; i++)
-#pragma unroll U
-			for (int j = 0; j < NMAX; j++)
-				if (i < nn && j < nn) Q.M[(size_t)(i * nn + j) * ld + b] = M[i][j];
-	}
-	if (!Q.Minv) return;
-	// Cholesky M = L L^T (lower, in place), then M^-1 column by column: L y = e_c, L^T x = y
-#pragma unroll U
-	for (int k = 0; k < NMAX; k++) {
-		if (k >= nn) break;
-		double d = M[k][k];
-#pragma unroll U
-		for (int l = 0; l < k; l++) d -= M[k][l] * M[k][l];
-		d = sqrt(d);
-		M[k][k] = d;
-		const double rd = 1.0 / d;
-#pragma unroll U
-		for (int i = k + 1; i < NMAX; i++) {
-			if (i >= nn) break;
-			double s = M[i][k];
-#pragma unroll U
-			for (int l = 0; l < k; l++) s -= M[i][l] * M[k][l];
-			M[i][k] = s * rd;
-		}
-	}
-#pragma unroll U
-	for (int c = 0; c < NMAX; c++) {
-		if (c >= nn) break;
-		double y[NMAX];
-#pragma unroll U
-		for (int i = 0; i < NMAX; i++) {
-			if (i >= nn) break;
-			double s = i == c ? 1.0 : 0.0;
-#pragma unroll U
-			for (int l = c; l < i; l++) s -= M[i][l] * y[l];
-			y[i] = i < c ? 0.0 : s / M[i][i];
-		}
-#pragma unroll U
-		for (int ii = 0; ii < NMAX; ii++) {
-			const int i = NMAX - 1 - ii;
-			if (i >= nn) continue;
-			double s = y[i];
-#pragma unroll U
-			for (int l = i + 1; l < NMAX; l++)
-				if (l < nn) s -= M[l][i] * y[l];
-			y[i] = s / M[i][i];
-			Q.Minv[(size_t)(i * nn + c) * ld + b] = y[i];
-		}
-	}
-}
-// kinematic trees: the same queries with the saip_rbd.h *_tree routines
-template <int NMAX>
-__global__ void __launch_bounds__(64) saip_model_dynamics_tree_kernel(const DynQuery Q) {
-	const int b = blockIdx.x * blockDim.x + threadIdx.x;
-	if (b >= Q.B) return;
-	const ModelDev& md = *Q.model;
-	const int nn = Q.n;
-	const int n = nn;  // (no padding: padding bodies would hang off body 0)
-	const size_t ld = Q.ld;
-	constexpr int U = NMAX <= 8 ? NMAX : 1;  // the 32 instantiation keeps its loops rolled (its arrays live in scratch either way)
-	double q[NMAX], dq[NMAX], zero[NMAX], t[NMAX];
-#pragma unroll
-	for (int j = 0; j < NMAX; j++) {
-		q[j] = j < nn ? Q.q[(size_t)j * ld + b] : 0.0;
-		dq[j] = j < nn ? Q.dq[(size_t)j * ld + b] : 0.0;
-		zero[j] = 0.0;
-	}
-	Chain<NMAX> K;
-	chain_fk_tree<NMAX>(md, n, q, K);
-	if (Q.g) {
-		rnea_tree<NMAX>(md, n, K, zero, zero, v3(-md.gravity[0], -md.gravity[1], -md.gravity[2]), false, t);
-#pragma unroll U
-		for (int j = 0; j < NMAX; j++)
-			if (j < nn) Q.g[(size_t)j * ld + b] = t[j];
-	}
-	if (Q.h) {
-		rnea_tree<NMAX>(md, n, K, dq, zero, v3(0, 0, 0), true, t);
-#pragma unroll U
-		for (int j = 0; j < NMAX; j++)
-			if (j < nn) Q.h[(size_t)j * ld + b] = t[j];
-	}
-	if (!Q.M && !Q.Minv) return;
-	double M[NMAX][NMAX];
-	mass_matrix_crb_tree<NMAX>(md, n, K, M);
+	if constexpr (TREE) mass_matrix_crb_tree<NMAX>(md, n, K, M);
+	else mass_matrix_crb<NMAX>(md, n, K, M);
 	if (Q.M) {
 #pragma unroll U
 		for (int i = 0; i < NMAX; i++)
@@ -393,20 +258,20 @@ __global__ void __launch_bounds__(64) saip_model_dynamics_tree_kernel(const DynQ
 }
 
 hipError_t launch_model_frames(const FrameQuery& Q, bool tree, hipStream_t stream) {
-	if (tree) hipLaunchKernelGGL(saip_model_frames_tree_kernel, dim3((Q.B + 63) / 64), dim3(64), 0, stream, Q);
-	else hipLaunchKernelGGL(saip_model_frames_kernel, dim3((Q.B + 63) / 64), dim3(64), 0, stream, Q);
+	if (tree) hipLaunchKernelGGL(saip_model_frames_kernel<true>, dim3((Q.B + 63) / 64), dim3(64), 0, stream, Q);
+	else hipLaunchKernelGGL(saip_model_frames_kernel<false>, dim3((Q.B + 63) / 64), dim3(64), 0, stream, Q);
 	return hipGetLastError();
 }
 
 hipError_t launch_model_dynamics(const DynQuery& Q, bool tree, hipStream_t stream) {
 	const int grid = (Q.B + 63) / 64;
 	if (tree) {
-		if (Q.n <= 8) hipLaunchKernelGGL((saip_model_dynamics_tree_kernel<8>), dim3(grid), dim3(64), 0, stream, Q);
-		else hipLaunchKernelGGL((saip_model_dynamics_tree_kernel<32>), dim3(grid), dim3(64), 0, stream, Q);
+		if (Q.n <= 8) hipLaunchKernelGGL((saip_model_dynamics_kernel<8, true>), dim3(grid), dim3(64), 0, stream, Q);
+		else hipLaunchKernelGGL((saip_model_dynamics_kernel<32, true>), dim3(grid), dim3(64), 0, stream, Q);
 		return hipGetLastError();
 	}
-	if (Q.n <= 8) hipLaunchKernelGGL((saip_model_dynamics_kernel<8>), dim3(grid), dim3(64), 0, stream, Q);
-	else hipLaunchKernelGGL((saip_model_dynamics_kernel<32>), dim3(grid), dim3(64), 0, stream, Q);
+	if (Q.n <= 8) hipLaunchKernelGGL((saip_model_dynamics_kernel<8, false>), dim3(grid), dim3(64), 0, stream, Q);
+	else hipLaunchKernelGGL((saip_model_dynamics_kernel<32, false>), dim3(grid), dim3(64), 0, stream, Q);
 	return hipGetLastError();
 }
 

@@ -33,34 +33,41 @@ struct Chain {  // world-frame kinematics of the movable bodies of one instance
 	V3 o[NMAX], z[NMAX], c[NMAX];  // joint origin, joint axis, centre of mass
 };
 
+// One joint j of the forward kinematics, expanded in place in both traversals: R, o come in as the rotation and joint origin of the parent body
+// (the base: identity, zero) and leave as those of body j, which are stored in K with the world axis and the centre of mass.  md, q, j and K
+// are names in the caller's scope.  A macro rather than a function for the reason given at SAIP_FK_JOINT_STEP (saip_fk.h): as a function,
+// force-inlined or not, it changes the schedule of the chain kernels.
+#define RBD_FK_JOINT_STEP \
+	o = o + mulR(R, v3(md.p0[j][0], md.p0[j][1], md.p0[j][2])); \
+	double Rt[9]; \
+	for (int r = 0; r < 3; r++) \
+		for (int c = 0; c < 3; c++) Rt[3 * r + c] = R[3 * r] * md.R0[j][c] + R[3 * r + 1] * md.R0[j][3 + c] + R[3 * r + 2] * md.R0[j][6 + c]; \
+	const double ax = md.axis[j][0], ay = md.axis[j][1], az = md.axis[j][2]; \
+	if (md.jtype[j] == 1) { \
+		double s, c; \
+		sincos(q[j], &s, &c); \
+		const double v = 1.0 - c; \
+		const double Rq[9] = {c + ax * ax * v,      ax * ay * v - az * s, ax * az * v + ay * s, \
+							  ay * ax * v + az * s, c + ay * ay * v,      ay * az * v - ax * s, \
+							  az * ax * v - ay * s, az * ay * v + ax * s, c + az * az * v}; \
+		for (int r = 0; r < 3; r++) \
+			for (int c2 = 0; c2 < 3; c2++) R[3 * r + c2] = Rt[3 * r] * Rq[c2] + Rt[3 * r + 1] * Rq[3 + c2] + Rt[3 * r + 2] * Rq[6 + c2]; \
+	} else { \
+		for (int e = 0; e < 9; e++) R[e] = Rt[e]; \
+		o = o + q[j] * mulR(R, v3(ax, ay, az)); \
+	} \
+	for (int e = 0; e < 9; e++) K.R[j][e] = R[e]; \
+	K.o[j] = o; \
+	K.z[j] = mulR(R, v3(ax, ay, az)); \
+	K.c[j] = o + mulR(R, v3(md.com[j][0], md.com[j][1], md.com[j][2]));
+
 template <int NMAX>
 __device__ void chain_fk(const ModelDev& md, int n, const double* q, Chain<NMAX>& K) {
 	double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 	V3 o = v3(0, 0, 0);
 #pragma unroll
 	for (int j = 0; j < n; j++) {
-		o = o + mulR(R, v3(md.p0[j][0], md.p0[j][1], md.p0[j][2]));
-		double Rt[9];
-		for (int r = 0; r < 3; r++)
-			for (int c = 0; c < 3; c++) Rt[3 * r + c] = R[3 * r] * md.R0[j][c] + R[3 * r + 1] * md.R0[j][3 + c] + R[3 * r + 2] * md.R0[j][6 + c];
-		const double ax = md.axis[j][0], ay = md.axis[j][1], az = md.axis[j][2];
-		if (md.jtype[j] == 1) {
-			double s, c;
-			sincos(q[j], &s, &c);
-			const double v = 1.0 - c;
-			const double Rq[9] = {c + ax * ax * v,      ax * ay * v - az * s, ax * az * v + ay * s,
-								  ay * ax * v + az * s, c + ay * ay * v,      ay * az * v - ax * s,
-								  az * ax * v - ay * s, az * ay * v + ax * s, c + az * az * v};
-			for (int r = 0; r < 3; r++)
-				for (int c2 = 0; c2 < 3; c2++) R[3 * r + c2] = Rt[3 * r] * Rq[c2] + Rt[3 * r + 1] * Rq[3 + c2] + Rt[3 * r + 2] * Rq[6 + c2];
-		} else {
-			for (int e = 0; e < 9; e++) R[e] = Rt[e];
-			o = o + q[j] * mulR(R, v3(ax, ay, az));
-		}
-		for (int e = 0; e < 9; e++) K.R[j][e] = R[e];
-		K.o[j] = o;
-		K.z[j] = mulR(R, v3(ax, ay, az));
-		K.c[j] = o + mulR(R, v3(md.com[j][0], md.com[j][1], md.com[j][2]));
+		RBD_FK_JOINT_STEP
 	}
 }
 
@@ -71,6 +78,31 @@ __device__ __forceinline__ V3 inertia_mul(const double* R, const double* I6, V3 
 	return mulR(R, Il);
 }
 
+// One body j of the forward pass of recursive Newton-Euler, in two statements (macros for the same reason as RBD_FK_JOINT_STEP).
+// RBD_RNEA_MOTION_STEP: w, al, a (angular velocity, angular acceleration, linear acceleration of the joint origin) come in as the parent
+// body's, with op its joint origin, and leave as body j's.  RBD_RNEA_FORCE_STEP: f_ = net force on body j, nn_ = net moment about its centre
+// of mass rc.
+#define RBD_RNEA_MOTION_STEP \
+	const V3 r = K.o[j] - op; \
+	a = a + cross(al, r); \
+	if (with_velocity) a = a + cross(w, cross(w, r)); \
+	const V3 z = K.z[j]; \
+	if (md.jtype[j] == 1) { \
+		if (with_velocity) al = al + dq[j] * cross(w, z); \
+		al = al + ddq[j] * z; \
+		if (with_velocity) w = w + dq[j] * z; \
+	} else { \
+		if (with_velocity) a = a + 2.0 * dq[j] * cross(w, z); \
+		a = a + ddq[j] * z; \
+	}
+#define RBD_RNEA_FORCE_STEP(f_, nn_) \
+	const V3 rc = K.c[j] - K.o[j]; \
+	V3 ac = a + cross(al, rc); \
+	if (with_velocity) ac = ac + cross(w, cross(w, rc)); \
+	f_ = md.mass[j] * ac; \
+	nn_ = inertia_mul(K.R[j], md.inertia[j], al); \
+	if (with_velocity) nn_ = nn_ + cross(w, inertia_mul(K.R[j], md.inertia[j], w));
+
 // Recursive Newton-Euler in world coordinates: joint torques for (dq, ddq) with base acceleration a0 (= -gravity).
 // with_velocity = false drops every velocity-product term (used for the columns of M).
 template <int NMAX>
@@ -79,24 +111,8 @@ __device__ void rnea(const ModelDev& md, int n, const Chain<NMAX>& K, const doub
 	V3 w = v3(0, 0, 0), al = v3(0, 0, 0), a = a0, op = v3(0, 0, 0);
 #pragma unroll
 	for (int j = 0; j < n; j++) {
-		const V3 r = K.o[j] - op;  // from the previous joint origin (rigidly attached to body j-1) to this one
-		a = a + cross(al, r);
-		if (with_velocity) a = a + cross(w, cross(w, r));
-		const V3 z = K.z[j];
-		if (md.jtype[j] == 1) {
-			if (with_velocity) al = al + dq[j] * cross(w, z);
-			al = al + ddq[j] * z;
-			if (with_velocity) w = w + dq[j] * z;
-		} else {
-			if (with_velocity) a = a + 2.0 * dq[j] * cross(w, z);
-			a = a + ddq[j] * z;
-		}
-		const V3 rc = K.c[j] - K.o[j];
-		V3 ac = a + cross(al, rc);
-		if (with_velocity) ac = ac + cross(w, cross(w, rc));
-		f[j] = md.mass[j] * ac;
-		nn[j] = inertia_mul(K.R[j], md.inertia[j], al);
-		if (with_velocity) nn[j] = nn[j] + cross(w, inertia_mul(K.R[j], md.inertia[j], w));
+		RBD_RNEA_MOTION_STEP
+		RBD_RNEA_FORCE_STEP(f[j], nn[j])
 		op = K.o[j];
 	}
 	V3 F = v3(0, 0, 0), N = v3(0, 0, 0);  // force / moment (about o_j) transmitted through joint j
@@ -121,28 +137,7 @@ __device__ void chain_fk_tree(const ModelDev& md, int n, const double* q, Chain<
 			for (int e = 0; e < 9; e++) R[e] = K.R[pa][e];
 			o = K.o[pa];
 		}
-		o = o + mulR(R, v3(md.p0[j][0], md.p0[j][1], md.p0[j][2]));
-		double Rt[9];
-		for (int r = 0; r < 3; r++)
-			for (int c = 0; c < 3; c++) Rt[3 * r + c] = R[3 * r] * md.R0[j][c] + R[3 * r + 1] * md.R0[j][3 + c] + R[3 * r + 2] * md.R0[j][6 + c];
-		const double ax = md.axis[j][0], ay = md.axis[j][1], az = md.axis[j][2];
-		if (md.jtype[j] == 1) {
-			double s, c;
-			sincos(q[j], &s, &c);
-			const double v = 1.0 - c;
-			const double Rq[9] = {c + ax * ax * v,      ax * ay * v - az * s, ax * az * v + ay * s,
-								  ay * ax * v + az * s, c + ay * ay * v,      ay * az * v - ax * s,
-								  az * ax * v - ay * s, az * ay * v + ax * s, c + az * az * v};
-			for (int r = 0; r < 3; r++)
-				for (int c2 = 0; c2 < 3; c2++) R[3 * r + c2] = Rt[3 * r] * Rq[c2] + Rt[3 * r + 1] * Rq[3 + c2] + Rt[3 * r + 2] * Rq[6 + c2];
-		} else {
-			for (int e = 0; e < 9; e++) R[e] = Rt[e];
-			o = o + q[j] * mulR(R, v3(ax, ay, az));
-		}
-		for (int e = 0; e < 9; e++) K.R[j][e] = R[e];
-		K.o[j] = o;
-		K.z[j] = mulR(R, v3(ax, ay, az));
-		K.c[j] = o + mulR(R, v3(md.com[j][0], md.com[j][1], md.com[j][2]));
+		RBD_FK_JOINT_STEP
 	}
 }
 
@@ -161,27 +156,12 @@ __device__ void rnea_tree(const ModelDev& md, int n, const Chain<NMAX>& K, const
 			a = A[pa];
 			op = K.o[pa];
 		}
-		const V3 r = K.o[j] - op;  // from the parent's joint origin (rigidly attached to the parent body) to this one
-		a = a + cross(al, r);
-		if (with_velocity) a = a + cross(w, cross(w, r));
-		const V3 z = K.z[j];
-		if (md.jtype[j] == 1) {
-			if (with_velocity) al = al + dq[j] * cross(w, z);
-			al = al + ddq[j] * z;
-			if (with_velocity) w = w + dq[j] * z;
-		} else {
-			if (with_velocity) a = a + 2.0 * dq[j] * cross(w, z);
-			a = a + ddq[j] * z;
-		}
+		RBD_RNEA_MOTION_STEP
 		W[j] = w;
 		AL[j] = al;
 		A[j] = a;
-		const V3 rc = K.c[j] - K.o[j];
-		V3 ac = a + cross(al, rc);
-		if (with_velocity) ac = ac + cross(w, cross(w, rc));
-		const V3 f = md.mass[j] * ac;
-		V3 nn = inertia_mul(K.R[j], md.inertia[j], al);
-		if (with_velocity) nn = nn + cross(w, inertia_mul(K.R[j], md.inertia[j], w));
+		V3 f, nn;
+		RBD_RNEA_FORCE_STEP(f, nn)
 		F[j] = f;
 		N[j] = nn + cross(rc, f);
 	}
