@@ -12,6 +12,7 @@
 
 #include "../../include/saip.h"
 #include "saip_device.h"
+#include "saip_cycle_plan.h"
 
 namespace saip {
 hipError_t launch_cycle_wg(const CycleParams& P, bool tree, hipStream_t stream);
@@ -87,6 +88,11 @@ static void m3_T(const double* A, double* B) {
 static void m3_eye(double* A) {
 	memset(A, 0, 9 * sizeof(double));
 	A[0] = A[4] = A[8] = 1.0;
+}
+static bool m3_is_eye(const double* A) {
+	for (int i = 0; i < 9; i++)
+		if (A[i] != ((i % 4 == 0) ? 1.0 : 0.0)) return false;
+	return true;
 }
 static void rpy_to_R(const double* rpy, double* R) {  // URDF fixed-axis rpy: R = Rz(yaw) Ry(pitch) Rx(roll)
 	double cr = cos(rpy[0]), sr = sin(rpy[0]), cp = cos(rpy[1]), sp = sin(rpy[1]), cy = cos(rpy[2]), sy = sin(rpy[2]);
@@ -405,7 +411,7 @@ struct saip_batch {
 	int B = 0, ld = 0, device = -1;
 	bool finalized = false, models_valid = false, config_dirty = true, state_pushed = false;
 	bool gravity_comp = false, torque_sat = false, integ_always = false, jla = false;
-	int kernel_choice = 0;
+	KernelChoice kernel_choice = KernelChoice::Auto;
 	std::string kernel_name = "none";
 	std::vector<TaskHost> tasks;
 	hipStream_t stream = nullptr;
@@ -427,13 +433,8 @@ struct saip_batch {
 	hipEvent_t time_ev[2] = {nullptr, nullptr};  // saip_batch_time_steps (created once: event creation is not part of a timed region)
 	bool flag_nan = false;                   // saip_batch_set_flagged_torque_policy
 	bool flagged_on_list = false;            // saip_batch_set_flagged_recompute: eight-lane kernels hand flagged instances to the list launch instead of their slow tail
-	int* flag_buf = nullptr;                 // [2 * (32 + ld)]: two { count, list } pairs of the device-side slow path, used alternately (CycleParams::flag_*)
-	unsigned flag_parity = 0;                // advanced only by a launch that hands the pair to a kernel
-	bool flag_clean[2] = {true, true};       // whether each pair's count is known to be zero (the buffer is zeroed at allocation)
+	FlagList flags;                          // the device-side work list of the slow path
 	bool otg_prelaunched = false;            // rollouts: the paired OTG step of the coming cycle already ran, fused with the previous integrate
-	int sim_want = 0;                        // rollouts: substeps the next cycle launch should integrate itself if it can (0 = no) ...
-	double sim_dt = 0, sim_damping = 0, sim_gravity[3] = {0, 0, 0};
-	bool sim_done = false;                   // ... and whether it did (eight-lane kernel, headline-type stack, no slow path behind)
 };
 
 static bool has_device(const saip_batch* b) { return b->device >= 0; }
@@ -722,7 +723,7 @@ extern "C" saip_status saip_batch_finalize(saip_batch* b) {
 		saip_status st;
 		if ((st = dev_alloc(b, &b->q, n * ld)) || (st = dev_alloc(b, &b->dq, n * ld)) || (st = dev_alloc(b, &b->tau, n * ld)) ||
 			(st = dev_alloc(b, &b->status, ld)) || (st = dev_alloc(b, &b->model_dev, 1)) || (st = dev_alloc(b, &b->tasks_dev, b->tasks.size())) ||
-			(st = dev_alloc(b, &b->flag_buf, 2 * (ld + 32))))
+			(st = dev_alloc(b, &b->flags.buf, 2 * (ld + 32))))
 			return st;
 		for (auto& T : b->tasks) {
 			if ((st = dev_alloc(b, &T.goal_dev, (size_t)T.dev.goal_comps * ld)) || (st = dev_alloc(b, &T.integ_dev, (size_t)T.integ_rows * ld)) ||
@@ -1340,6 +1341,12 @@ static saip_status run_otg(saip_batch* b, int t, int mode, int mask = 3) {
 	return SAIP_OK;
 }
 
+// a motion-force task that controls all of its space in motion: identity projections and, where the short control law is used, identity
+// sigma matrices as well
+static bool mf_full_identity(const TaskDev& d, bool with_sigma) {
+	return m3_is_eye(d.Ppos) && m3_is_eye(d.Pori) && (!with_sigma || (m3_is_eye(d.sig_p) && m3_is_eye(d.sig_o)));
+}
+
 static saip_status make_params(saip_batch* b, CycleParams& P, bool diag) {
 	for (auto& T : b->tasks) {
 		if (T.otg_enabled) {
@@ -1365,12 +1372,8 @@ static saip_status make_params(saip_batch* b, CycleParams& P, bool diag) {
 			if (T.otg_enabled) d.goal = T.desired_dev;  // the law tracks the OTG output (JointTask.cpp:317-319, MotionForceTask.cpp:394-406)
 			d.law_identity = 0;
 			if (d.type == saip::TASK_MOTION_FORCE && d.k == 6 && !d.general_law) {
-				bool id = true;
+				bool id = mf_full_identity(d, true);
 				for (int i = 0; i < 36 && id; i++) id = d.Bm[i] == ((i % 7 == 0) ? 1.0 : 0.0);
-				for (int i = 0; i < 9 && id; i++) {
-					const double e = (i % 4 == 0) ? 1.0 : 0.0;
-					id = d.Ppos[i] == e && d.Pori[i] == e && d.sig_p[i] == e && d.sig_o[i] == e;
-				}
 				d.law_identity = id ? 1 : 0;
 			}
 			tmp.push_back(d);
@@ -1442,14 +1445,10 @@ static saip_status make_params(saip_batch* b, CycleParams& P, bool diag) {
 	P.out_Ntot = nullptr;
 	for (int t = 0; t < SAIP_MAXT; t++) P.task_cycle[t] = t < (int)b->tasks.size() ? b->tasks[t].sh_cycle : 0;
 	P.flag_nan = b->flag_nan ? 1 : 0;
-	P.flag_count = nullptr;  // set by launch_cycle when a device-side slow path follows the lane / eight-lane kernel
-	P.flag_count_next = nullptr;
-	P.flag_list = nullptr;
-	P.slow_tail = 0;
+	// neutral: no work list, no slow tail, the lean eight-lane instantiation.  launch_cycle alone overwrites these, from its CyclePlan
+	P.flag_count = P.flag_count_next = P.flag_list = nullptr;
+	P.slow_tail = P.oct_general_joint = P.oct_partial_mf = P.oct_truncate = 0;
 	P.lane_general = 0;
-	P.oct_general_joint = 0;
-	P.oct_partial_mf = 0;
-	P.oct_truncate = 0;
 	for (auto& T : b->tasks)
 		if (T.dev.general_law) P.lane_general = 1;
 	P.wave_general_joint = 0;
@@ -1494,57 +1493,44 @@ static bool wave_eligible(const saip_batch* b) {
 // eight-lanes-per-instance kernel (saip_kernel_oct.hip): 7-dof chain, { MotionForceTask, JointTask }.  Either the headline stack
 // (full 6-dof motion-force task + full joint task: the joint task has rank <= 1) or any motion-force task of rank >= 2 with a joint
 // task of at most four rows (general range basis); default or general control laws, no closed-loop force control.
-static bool oct_eligible(const saip_batch* b, CycleParams& P) {
+static OctFit oct_eligible(const saip_batch* b) {  // (on top of lane_eligible)
+	OctFit fit;
 	const int n = b->model->n;
-	if (n < 6 || n > 8 || b->tasks.size() != 2 || b->model->dev.is_tree) return false;
+	if (n < 6 || n > 8 || b->tasks.size() != 2 || b->model->dev.is_tree) return fit;
 	const TaskDev& mf = b->tasks[0].dev;
 	const TaskDev& jt = b->tasks[1].dev;
-	if (mf.type != saip::TASK_MOTION_FORCE || jt.type != saip::TASK_JOINT) return false;
-	if (mf.cl_force || mf.cl_moment || mf.k < 2) return false;
+	if (mf.type != saip::TASK_MOTION_FORCE || jt.type != saip::TASK_JOINT) return fit;
+	if (mf.cl_force || mf.cl_moment || mf.k < 2) return fit;
 	const bool full_mf = mf.k == 6 && mf.bm_identity;
 	const bool full_jt = jt.m == n && jt.s_identity;
+	if (!full_mf && mf.general_law) return fit;  // the general laws are wired for the full task only
+	// full task: the projections are identities; the short control law also relies on identity sigma matrices
+	if (full_mf && !mf_full_identity(mf, !mf.general_law)) return fit;
 	if (n != 7) {
 		// 6- and 8-dof chains: the general instantiation only -- full joint task behind a motion-force task, Jp = N_1 of rank n - k (<= 5) by the
 		// multi-pivot Gram-Schmidt path; singularity handling on (a reduced task would need the 7-dof bookkeeping), no joint limit avoidance
-		if (!full_jt || n - mf.k > 5 || n - mf.k < 0 || !mf.sing_handling || P.jla) return false;
-		if (!full_mf && mf.general_law) return false;
-		if (full_mf)
-			for (int i = 0; i < 9; i++) {
-				const double id = (i % 4 == 0) ? 1.0 : 0.0;
-				if (mf.Ppos[i] != id || mf.Pori[i] != id) return false;
-				if (!mf.general_law && (mf.sig_p[i] != id || mf.sig_o[i] != id)) return false;
-			}
-		if (!lane_eligible(b)) return false;
-		P.oct_general_joint = 2;
-		P.oct_partial_mf = full_mf ? 0 : 1;
-		return true;
-	}
-	if (!full_mf && mf.general_law) return false;  // the general laws are wired for the full task only
-	if (full_mf) {
-		for (int i = 0; i < 9; i++) {  // full task: the projections are identities; the short control law also relies on identity sigma matrices
-			const double id = (i % 4 == 0) ? 1.0 : 0.0;
-			if (mf.Ppos[i] != id || mf.Pori[i] != id) return false;
-			if (!mf.general_law && (mf.sig_p[i] != id || mf.sig_o[i] != id)) return false;
+		if (!full_jt || n - mf.k > 5 || n - mf.k < 0 || !mf.sing_handling || b->jla) return fit;
+		fit.general_joint = 2;
+	} else {
+		const bool full_behind_partial = full_jt && !full_mf && mf.k <= 5;  // Jp = N_1 has rank 7 - k: multi-pivot Gram-Schmidt path
+		if (!(full_mf && full_jt) && !full_behind_partial && jt.m > 4) return fit;
+		fit.general_joint = (full_mf && full_jt) ? 0 : (full_behind_partial ? 2 : 1);
+		if (full_mf && full_jt && !mf.sing_handling && !mf.general_law) {  // disableSingularityHandling(): reduced tasks need the multi-pivot joint-task path
+			fit.general_joint = 2;
+			fit.truncate = 1;
 		}
 	}
-	const bool full_behind_partial = full_jt && !full_mf && mf.k <= 5;  // Jp = N_1 has rank 7 - k: multi-pivot Gram-Schmidt path
-	if (!(full_mf && full_jt) && !full_behind_partial && jt.m > 4) return false;
-	if (!lane_eligible(b)) return false;
-	P.oct_general_joint = (full_mf && full_jt) ? 0 : (full_behind_partial ? 2 : 1);
-	if (full_mf && full_jt && !mf.sing_handling && !mf.general_law) {  // disableSingularityHandling(): reduced tasks need the multi-pivot joint-task path
-		P.oct_general_joint = 2;
-		P.oct_truncate = 1;
-	}
-	P.oct_partial_mf = full_mf ? 0 : 1;
-	return true;
+	fit.partial_mf = full_mf ? 0 : 1;
+	fit.ok = true;
+	return fit;
 }
 // eight-lanes-per-instance kernel for hierarchies that START with a joint task (saip_kernel_octjf.hip): 7- or 8-dof chain,
 // { JointTask of <= 4 rows, each selecting one joint; full 6-dof MotionForceTask in its nullspace } -- the stack of examples/06.
 // Default or general (open-loop) control laws, any decoupling type, gravity compensation, torque saturation; joint limit avoidance and
 // closed-loop force control keep the stack on the lane kernel.
-static bool octjf_eligible(const saip_batch* b, const CycleParams& P) {
+static bool octjf_eligible(const saip_batch* b) {  // (on top of lane_eligible)
 	const int n = b->model->n;
-	if ((n != 7 && n != 8) || b->tasks.size() != 2 || P.jla || b->model->dev.is_tree) return false;
+	if ((n != 7 && n != 8) || b->tasks.size() != 2 || b->jla || b->model->dev.is_tree) return false;
 	const TaskDev& jt = b->tasks[0].dev;
 	const TaskDev& mf = b->tasks[1].dev;
 	if (jt.type != saip::TASK_JOINT || mf.type != saip::TASK_MOTION_FORCE) return false;
@@ -1561,11 +1547,7 @@ static bool octjf_eligible(const saip_batch* b, const CycleParams& P) {
 		seen |= 1u << hit;
 	}
 	if (mf.k != 6 || !mf.bm_identity || mf.cl_force || mf.cl_moment) return false;  // (goal rows 30..35, the sensed force and moment, are only read by the closed-loop laws)
-	for (int i = 0; i < 9; i++) {
-		const double id = (i % 4 == 0) ? 1.0 : 0.0;
-		if (mf.Ppos[i] != id || mf.Pori[i] != id) return false;
-	}
-	return lane_eligible(b);
+	return mf_full_identity(mf, false);
 }
 // both OTGs of a { MotionForceTask, JointTask } stack on, initialised and with clean limits: their cycle-mode steps share one launch
 static bool otg_pair_ready(saip_batch* b) {
@@ -1583,7 +1565,66 @@ static bool otg_pair_ready(saip_batch* b) {
 	return true;
 }
 
-static saip_status launch_cycle(saip_batch* b, bool diag) {
+// ---- which cycle kernel a launch takes, who recomputes the instances it flags, and whether it integrates the state as well: decided
+// here and nowhere else.  A pure function of the batch and the parameter block; launch_cycle carries the plan out.
+static CyclePlan plan_cycle(const saip_batch* b, const CycleParams& P, bool diag, bool wants_sim) {
+	CyclePlan plan;
+	const KernelChoice choice = b->kernel_choice;
+	auto refuse = [&plan](const char* why) {
+		plan.refused = SAIP_ERR_UNSUPPORTED;
+		plan.why = why;
+		return plan;
+	};
+	if (diag || choice == KernelChoice::Wg) return plan;  // diagnostic launches always take the general kernel
+	const bool lane = lane_eligible(b);
+	if (lane) plan.oct = oct_eligible(b);
+	const bool octjf_ok = lane && !plan.oct.ok && octjf_eligible(b);
+	if (choice == KernelChoice::Oct && !plan.oct.ok && !octjf_ok) return refuse(kOctRefusal);
+	if (lane) {
+		// small batches of the headline stack: eight lanes per instance (the lane kernel would leave most of the chip idle)
+		// Up to which batch: 1024 wavefronts (8192 instances) are resident at once, larger launches run in rounds.  Measured against the lane
+		// kernel (round 3): the lean instantiation (config 2's stack) stays ahead up to 24 576 instances (26.8 against
+		// 31.1 us) and is level at 32 768; every other instantiation -- partial tasks, reduced tasks, joint task first, 6 / 8 dof -- is ahead
+		// at every size (config 3: 109 against 195 us at 65 536, 384 against 627 at 262 144; config 6: 102 against 190 at 65 536), and
+		// stacks whose instances leave the non-singular branch are not a contest (the lane kernel hands those to the general kernel).
+		const bool oct_lean = plan.oct.ok && plan.oct.general_joint == 0 && !(P.jla || P.lane_general || plan.oct.partial_mf);
+		const bool oct_size = !oct_lean || b->B <= 24576;
+		const bool eight = choice == KernelChoice::Oct || (choice == KernelChoice::Auto && oct_size);
+		plan.kernel = (eight && plan.oct.ok) ? CycleKernel::Oct : ((eight && octjf_ok) ? CycleKernel::OctJf : CycleKernel::Lane);
+		// slow path: instances the lane / eight-lane kernel flags (outside the fully non-singular branch) are recomputed by the general kernel
+		// when a task can handle them there (blended strategies -- the reference default -- or singularity handling disabled: the task is
+		// reduced to its non-singular subspace).  Flagged instances are appended to a list on the device; the general kernel launched
+		// behind strides over it with a small fixed grid, no host round trip, and leaves at once when the list is empty.
+		bool handled = false;
+		for (auto& T : b->tasks)
+			if (T.dev.type == saip::TASK_MOTION_FORCE && (!T.dev.sing_handling || T.dev.sing_strategies)) handled = true;
+		const bool headline = plan.kernel == CycleKernel::Oct && plan.oct.general_joint == 0;
+		if (!handled) plan.recompute = Recompute::None;
+		// the eight-lane kernel runs the blended singularity strategies of the headline stack itself (and passes a fully singular task
+		// through): with the handling enforced nothing is left for a slow path, and what it still refuses the general kernel would too
+		else if (headline && b->tasks[0].dev.sing_handling) plan.recompute = Recompute::None;
+		// every other eight-lane stack: the wavefront that flags an instance recomputes it itself behind its epilogue (the general kernel's body on
+		// its own LDS block) -- no list and no second launch behind the kernel (round 4)
+		else if (plan.kernel != CycleKernel::Lane && !headline && !b->flagged_on_list) plan.recompute = Recompute::Tail;
+		else plan.recompute = Recompute::List;
+		plan.fuse_sim = wants_sim && headline && plan.recompute == Recompute::None;  // nothing recomputes torques behind this launch: it can integrate as well
+		return plan;
+	}
+	if (choice == KernelChoice::Lane) return refuse(kLaneRefusal);
+	const bool wave = wave_eligible(b);
+	if (choice == KernelChoice::Wave && !wave) return refuse(kWaveRefusal);
+	if (wave) {  // (the choice is Auto or Wave here)
+		// chains of 9..32 dof: one wavefront per instance, matrices in MFMA operand form (saip_kernel_wave.hip).  What it cannot certify
+		// (a task outside the non-singular branch, an ambiguous rank gap, ...) it leaves untouched on the device-side work list; the
+		// general kernel behind recomputes those instances -- an empty list costs that launch one scalar load per workgroup
+		plan.kernel = CycleKernel::Wave;
+		plan.recompute = Recompute::List;
+	}
+	return plan;
+}
+
+// sim: the integration a rollout would like this launch to do as well; *integrated tells whether it did
+static saip_status launch_cycle(saip_batch* b, bool diag, const SimRequest* sim = nullptr, bool* integrated = nullptr) {
 	CycleParams P;
 	if (!diag)
 		for (auto& T : b->tasks) T.sh_cycle++;  // updateControllerTaskModels: every task's model is updated once per cycle
@@ -1609,108 +1650,59 @@ static saip_status launch_cycle(saip_batch* b, bool diag) {
 		if (!T.otg_enabled) continue;
 		if (!diag && (st = run_otg(b, (int)t, 0))) return st;  // a diagnostic re-launch must not advance the trajectory
 	}
-	bool lane_ok = false;
-	if (!diag && b->kernel_choice == 3 && !oct_eligible(b, P) && !octjf_eligible(b, P)) return fail(SAIP_ERR_UNSUPPORTED, "the eight-lanes-per-instance kernel does not cover this robot/task stack");
-	if (!diag && b->kernel_choice != 1 && lane_eligible(b)) {
-		// slow path: instances the lane / eight-lane kernel flags (outside the fully non-singular branch) are recomputed by the general kernel
-		// when a task can handle them there (blended strategies -- the reference default -- or singularity handling disabled: the task is
-		// reduced to its non-singular subspace).  Flagged instances are appended to a list on the device; the general kernel launched
-		// behind strides over it with a small fixed grid, no host round trip, and leaves at once when the list is empty.
-		bool slow = false;
-		for (auto& T : b->tasks)
-			if (T.dev.type == saip::TASK_MOTION_FORCE && (!T.dev.sing_handling || T.dev.sing_strategies)) slow = true;
-		if (slow) {
-			int* cur = b->flag_buf + (size_t)(b->flag_parity & 1u) * (b->ld + 32);
-			int* nxt = b->flag_buf + (size_t)((b->flag_parity + 1u) & 1u) * (b->ld + 32);
-			P.flag_count = cur;
-			P.flag_list = cur + 32;
-			P.flag_count_next = nxt;
-		}
-		// small batches of the headline stack: eight lanes per instance (the lane kernel would leave most of the chip idle)
-		// Up to which batch: 1024 wavefronts (8192 instances) are resident at once, larger launches run in rounds.  Measured against the lane
-		// kernel (round 3): the lean instantiation (config 2's stack) stays ahead up to 24 576 instances (26.8 against
-		// 31.1 us) and is level at 32 768; every other instantiation -- partial tasks, reduced tasks, joint task first, 6 / 8 dof -- is ahead
-		// at every size (config 3: 109 against 195 us at 65 536, 384 against 627 at 262 144; config 6: 102 against 190 at 65 536), and
-		// stacks whose instances leave the non-singular branch are not a contest (the lane kernel hands those to the general kernel).
-		const bool oct_ok = oct_eligible(b, P);
-		const bool oct_lean = oct_ok && P.oct_general_joint == 0 && !(P.jla || P.lane_general || P.oct_partial_mf);
-		const bool oct_size = !oct_lean || b->B <= 24576;
-		const bool oct = oct_ok && (b->kernel_choice == 3 || (b->kernel_choice == 0 && oct_size));
-		const bool octjf = !oct && octjf_eligible(b, P) && (b->kernel_choice == 3 || (b->kernel_choice == 0 && oct_size));
-		// the eight-lane kernel runs the blended singularity strategies of the headline stack itself (and passes a fully singular task
-		// through): with the handling enforced nothing is left for a slow path, and what it still refuses the general kernel would too
-		if (oct && P.oct_general_joint == 0 && b->tasks[0].dev.sing_handling) {
-			slow = false;
-			P.flag_count = P.flag_count_next = P.flag_list = nullptr;
-		}
-		// every other eight-lane stack: the wavefront that flags an instance recomputes it itself behind its epilogue (the general kernel's body on
-		// its own LDS block) -- no list and no second launch behind the kernel (round 4)
-		P.slow_tail = 0;
-		if (slow && !b->flagged_on_list && ((oct && P.oct_general_joint != 0) || octjf)) {
-			slow = false;
-			P.slow_tail = 1;
-			P.flag_count = P.flag_count_next = P.flag_list = nullptr;
-		}
-		b->sim_done = false;
-		if (b->sim_want > 0 && oct && !slow && P.oct_general_joint == 0) {  // nothing recomputes torques behind this launch: it can integrate as well
-			P.sim_substeps = b->sim_want;
-			P.sim_dt = b->sim_dt;
-			P.sim_damping = b->sim_damping;
-			for (int i = 0; i < 3; i++) P.sim_gravity[i] = b->sim_gravity[i];
-			b->sim_done = true;
-		}
-		if (slow && !b->flag_clean[b->flag_parity & 1u]) {
-			// the pair this launch appends to was not zeroed by the cycle before (a cycle without a slow path, another kernel choice, or a
-			// failed launch came in between): zero its count here, or stale entries would be recomputed a second time
-			HIP_TRY(hipMemsetAsync(P.flag_count, 0, sizeof(int), b->stream));
-			b->flag_clean[b->flag_parity & 1u] = true;
-		}
-		hipError_t e = oct ? saip::launch_cycle_oct(P, b->stream) : (octjf ? saip::launch_cycle_octjf(P, b->stream) : saip::launch_cycle_lane(P, b->stream, &lane_ok));
-		if (oct || octjf) lane_ok = true;
-		if (slow && lane_ok && e == hipSuccess) {  // the kernel appends to the current pair and zeroes the other one
-			b->flag_clean[b->flag_parity & 1u] = false;
-			b->flag_clean[(b->flag_parity + 1u) & 1u] = true;
-			b->flag_parity++;
-		}
-		if (lane_ok) {
-			if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "lane kernel launch failed: %s", hipGetErrorString(e));
-			b->kernel_name = oct ? "saip_cycle_oct" : (octjf ? "saip_cycle_octjf" : "saip_cycle_lane");
-			if (slow) {
-				hipError_t e2 = saip::launch_cycle_wg_list(P, b->stream);
-				if (e2 != hipSuccess) return fail(SAIP_ERR_DEVICE, "slow-path kernel launch failed: %s", hipGetErrorString(e2));
-			}
-			return SAIP_OK;
-		}
+	const CyclePlan plan = plan_cycle(b, P, diag, sim != nullptr);
+	if (plan.refused) return fail(plan.refused, "%s", plan.why);
+	P.oct_general_joint = plan.oct.general_joint;
+	P.oct_partial_mf = plan.oct.partial_mf;
+	P.oct_truncate = plan.oct.truncate;
+	P.slow_tail = plan.recompute == Recompute::Tail ? 1 : 0;
+	if (plan.fuse_sim) {
+		P.sim_substeps = sim->substeps;
+		P.sim_dt = sim->dt;
+		P.sim_damping = sim->damping;
+		for (int i = 0; i < 3; i++) P.sim_gravity[i] = sim->gravity[i];
 	}
-	if (!diag && b->kernel_choice == 2) return fail(SAIP_ERR_UNSUPPORTED, "the lane-per-instance kernel does not cover this robot/task stack");
-	if (!diag && b->kernel_choice == 4 && !wave_eligible(b)) return fail(SAIP_ERR_UNSUPPORTED, "the wavefront-per-instance kernel covers chains of 9 to 32 dof without a passivity controller");
-	if (!diag && (b->kernel_choice == 0 || b->kernel_choice == 4) && wave_eligible(b)) {
-		// chains of 9..32 dof: one wavefront per instance, matrices in MFMA operand form (saip_kernel_wave.hip).  What it cannot certify
-		// (a task outside the non-singular branch, an ambiguous rank gap, ...) it leaves untouched on the device-side work list; the
-		// general kernel behind recomputes those instances -- an empty list costs that launch one scalar load per workgroup
-		int* cur = b->flag_buf + (size_t)(b->flag_parity & 1u) * (b->ld + 32);
-		int* nxt = b->flag_buf + (size_t)((b->flag_parity + 1u) & 1u) * (b->ld + 32);
-		P.flag_count = cur;
-		P.flag_list = cur + 32;
-		P.flag_count_next = nxt;
-		if (!b->flag_clean[b->flag_parity & 1u]) {
-			HIP_TRY(hipMemsetAsync(P.flag_count, 0, sizeof(int), b->stream));
-			b->flag_clean[b->flag_parity & 1u] = true;
-		}
-		hipError_t e = saip::launch_cycle_wave(P, b->stream);
-		if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "wavefront-per-instance kernel launch failed: %s", hipGetErrorString(e));
-		b->flag_clean[b->flag_parity & 1u] = false;
-		b->flag_clean[(b->flag_parity + 1u) & 1u] = true;
-		b->flag_parity++;
-		b->kernel_name = "saip_cycle_wave";
+	bool list = plan.recompute == Recompute::List;
+	if (list) {
+		b->flags.bind(P, b->ld);
+		HIP_TRY(b->flags.zero_current(P, b->stream));
+	}
+	CycleKernel kernel = plan.kernel;
+	hipError_t e;
+	bool took = true;
+	switch (kernel) {
+		case CycleKernel::Oct: e = saip::launch_cycle_oct(P, b->stream); break;
+		case CycleKernel::OctJf: e = saip::launch_cycle_octjf(P, b->stream); break;
+		case CycleKernel::Lane: e = saip::launch_cycle_lane(P, b->stream, &took); break;
+		case CycleKernel::Wave: e = saip::launch_cycle_wave(P, b->stream); break;
+		default: e = saip::launch_cycle_wg(P, b->model->dev.is_tree != 0, b->stream);
+	}
+	if (!took) {  // the lane kernel has no instantiation for this stack (there is none such at 6..8 dof): as if the stack were not eligible
+		if (b->kernel_choice == KernelChoice::Lane) return fail(SAIP_ERR_UNSUPPORTED, "%s", kLaneRefusal);
+		if (b->kernel_choice == KernelChoice::Wave) return fail(SAIP_ERR_UNSUPPORTED, "%s", kWaveRefusal);
+		kernel = CycleKernel::Wg;
+		list = false;
+		e = saip::launch_cycle_wg(P, b->model->dev.is_tree != 0, b->stream);
+	}
+	if (e != hipSuccess) {
+		const char* what = kernel == CycleKernel::Wg ? "kernel" : (kernel == CycleKernel::Wave ? "wavefront-per-instance kernel" : "lane kernel");
+		return fail(SAIP_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
+	}
+	if (list) b->flags.handed_over();
+	switch (kernel) {
+		case CycleKernel::Oct: b->kernel_name = "saip_cycle_oct"; break;
+		case CycleKernel::OctJf: b->kernel_name = "saip_cycle_octjf"; break;
+		case CycleKernel::Lane: b->kernel_name = "saip_cycle_lane"; break;
+		case CycleKernel::Wave: b->kernel_name = "saip_cycle_wave"; break;
+		default:
+			if (b->model->dev.is_tree) b->kernel_name = P.n <= 8 ? "saip_cycle_wg_tree<8,64>" : "saip_cycle_wg_tree<32,512>";
+			else b->kernel_name = P.n <= 8 ? "saip_cycle_wg<8,64>" : "saip_cycle_wg<32,512>";
+	}
+	if (list) {
 		hipError_t e2 = saip::launch_cycle_wg_list(P, b->stream);
 		if (e2 != hipSuccess) return fail(SAIP_ERR_DEVICE, "slow-path kernel launch failed: %s", hipGetErrorString(e2));
-		return SAIP_OK;
 	}
-	hipError_t e = saip::launch_cycle_wg(P, b->model->dev.is_tree != 0, b->stream);
-	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
-	if (b->model->dev.is_tree) b->kernel_name = P.n <= 8 ? "saip_cycle_wg_tree<8,64>" : "saip_cycle_wg_tree<32,512>";
-	else b->kernel_name = P.n <= 8 ? "saip_cycle_wg<8,64>" : "saip_cycle_wg<32,512>";
+	if (integrated) *integrated = plan.fuse_sim;
 	return SAIP_OK;
 }
 
@@ -2018,7 +2010,7 @@ extern "C" saip_status saip_batch_set_kernel(saip_batch* b, int which) {
 	if (!b || which < 0 || which > 4) return fail(SAIP_ERR_INVALID_ARGUMENT, "kernel selector must be 0, 1, 2, 3 or 4");
 	if (which >= 2 && b->model->dev.is_tree)
 		return fail(SAIP_ERR_UNSUPPORTED, "saip_batch_set_kernel(%d): this robot is a kinematic tree; only the general kernel (0 or 1) covers trees", which);
-	b->kernel_choice = which;
+	b->kernel_choice = (KernelChoice)which;
 	return SAIP_OK;
 }
 extern "C" const char* saip_batch_kernel_name(saip_batch* b) { return b ? b->kernel_name.c_str() : ""; }
@@ -2068,21 +2060,17 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 	if (steps < 1 || !(sim_dt > 0) || substeps < 1 || damping < 0) return fail(SAIP_ERR_INVALID_ARGUMENT, "saip_batch_rollout_async: bad arguments");
 	bool any_otg = false;
 	for (auto& T : b->tasks) any_otg = any_otg || T.otg_enabled;
+	SimRequest sim = {substeps, sim_dt, damping, {0, 0, 0}};
+	for (int i = 0; i < 3; i++) sim.gravity[i] = gravity ? gravity[i] : b->model->dev.gravity[i];
 	auto period = [&](const bool more = false) -> saip_status {  // more: another period follows inside this call
 		// no internal OTG in the stack: the cycle launch integrates the state itself when it can (eight-lane kernel, no slow path behind)
-		b->sim_want = (!any_otg && b->model->n == 7) ? substeps : 0;
-		b->sim_dt = sim_dt;
-		b->sim_damping = damping;
-		for (int i = 0; i < 3; i++) b->sim_gravity[i] = gravity ? gravity[i] : b->model->dev.gravity[i];
-		b->sim_done = false;
-		saip_status s2 = launch_cycle(b, false);
-		b->sim_want = 0;
+		bool integrated = false;
+		saip_status s2 = launch_cycle(b, false, (!any_otg && b->model->n == 7) ? &sim : nullptr, &integrated);
 		if (s2) {
 			b->otg_prelaunched = false;  // a failed period must not leave the next standalone cycle believing its OTG step has already run
 			return s2;
 		}
-		if (b->sim_done) {  // the bookkeeping of enqueue_integrate
-			b->sim_done = false;
+		if (integrated) {  // the bookkeeping of enqueue_integrate
 			b->models_valid = false;
 			b->state_epoch++;
 			return SAIP_OK;
