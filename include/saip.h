@@ -211,6 +211,44 @@ saip_status saip_batch_integrate(saip_batch*, double dt, int substeps, const dou
 /* `steps` closed-loop control periods { internal OTGs -> control cycle -> integrate(sim_dt, substeps) } enqueued back to back on the
  * engine stream without host synchronisation (follow with saip_batch_synchronize); goals stay as they are on the device. */
 saip_status saip_batch_rollout_async(saip_batch*, int steps, double sim_dt, int substeps, const double gravity[3], double damping);
+/* ---- rollout recorder: a per-period trajectory log and running summaries of saip_batch_rollout_async, kept on the device (the
+ * reference's example loops print or log the same quantities every period: state, torques, position / orientation error).  A recorder
+ * is attached to a finalized batch and stays attached across rollout calls until detached.  It observes rollout periods only
+ * (saip_batch_step_async, saip_batch_integrate and saip_batch_compute_control_torques called directly are not recorded), each one AFTER
+ * its integration: the torques that were applied during the period (the array saip_batch_integrate reads), the status byte of the
+ * period's cycle, q and dq as the integration left them, and the task quantities of one motion-force task at that state against its
+ * user goal as it stands.  A period counter p starts at 1 with the first recorded period and continues across rollout calls.
+ *   log: every stride-th period (p % stride == 0) goes to slot (p / stride - 1) % capacity of a ring that keeps the last `capacity`
+ *        samples: log[slot][row][ld] doubles and status[slot][ld] bytes (ld = saip_batch_ld; columns B..ld-1 are never written).  The
+ *        rows of a sample are the channels selected by `channels`, in this order:
+ *          SAIP_RECORD_Q     q    [dof]
+ *          SAIP_RECORD_DQ    dq   [dof]
+ *          SAIP_RECORD_TAU   tau  [dof], NaN kept as NaN
+ *          SAIP_RECORD_POSE  position [3], rotation [9] row-major of the task's control frame (as saip_batch_get_current_pose_host)
+ *          SAIP_RECORD_ERROR rows 0..5 of saip_batch_get_task_diagnostics_host: selection-projected position and orientation error
+ *        With an empty mask nothing is sampled.
+ *   summaries (summaries != 0), advanced on EVERY period whatever the stride; [8][ld], T = sim_dt * substeps of the rollout call:
+ *          0 sum T tau.tau (NaN entries count as 0, the way the integrator coasts)    1 sum T |e_pos|^2    2 sum T |e_ori|^2
+ *          3 max |e_pos|    4 max |e_ori|    5 max_j |tau_j|    6 max_j |dq_j|    7 number of periods with status != 0
+ *        e_pos, e_ori are the error rows above; rows 1..4 stay 0 without a task.  The maxima skip NaN entries.
+ *   task: one motion-force task, or -1 (then the pose and error channels are SAIP_ERR_INVALID_ARGUMENT).
+ * The log is allocated and zeroed by _attach, never inside a rollout; _detach waits for the stream and frees it; _reset (on the stream)
+ * sets p back to 0, empties the log and zeroes the summaries.  Without a recorder a rollout enqueues exactly what it did before; with
+ * one, one small launch per observed period (per sampled period when summaries are off).  SAIP_ERR_ORDER: before saip_batch_finalize,
+ * on a model-only batch, a second _attach without _detach, and every other entry without a recorder. */
+enum { SAIP_RECORD_Q = 1, SAIP_RECORD_DQ = 2, SAIP_RECORD_TAU = 4, SAIP_RECORD_POSE = 8, SAIP_RECORD_ERROR = 16 };
+#define SAIP_RECORD_SUMMARY_ROWS 8
+saip_status saip_batch_rollout_recorder_attach(saip_batch*, int capacity, int stride, unsigned channels, int task, int summaries);
+saip_status saip_batch_rollout_recorder_detach(saip_batch*);
+saip_status saip_batch_rollout_recorder_reset(saip_batch*);
+/* samples in the log, rows per sample, period number of the oldest sample (0 when empty), stride; any pointer may be NULL */
+saip_status saip_batch_rollout_log_info(saip_batch*, int* n_samples, int* rows, int* first_period, int* stride);
+/* the log in chronological order: out [n_samples][rows][B], status [n_samples][B] (either may be NULL); synchronous */
+saip_status saip_batch_rollout_log_host(saip_batch*, double* out, uint8_t* status);
+/* the summaries: out [8][B]; synchronous.  SAIP_ERR_ORDER when the recorder was attached without summaries */
+saip_status saip_batch_rollout_summary_host(saip_batch*, double* out);
+double* saip_batch_rollout_log_device(saip_batch*);      /* [capacity][rows][ld], ring order; NULL when detached or nothing is sampled */
+double* saip_batch_rollout_summary_device(saip_batch*);  /* [8][ld]; NULL when detached or without summaries */
 /* overwrite the resident torque array ([dof][B]) that saip_batch_integrate applies -- sim->setJointTorques(name, control_torques +
  * ui_torques) in the examples (05-...cpp:226-228) when the applied torque is not just the last cycle's output */
 saip_status saip_batch_set_torques_host(saip_batch*, const double* tau);

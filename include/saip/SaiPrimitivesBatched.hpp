@@ -780,6 +780,68 @@ public:
 	saip_batch* handle() { return _batch; }
 	void pushState() { _robot->pushTo(_batch); }
 
+	// ---- the resident pipeline (engine extras): control cycles and forward dynamics on the device, no host in the loop
+	// one control cycle enqueued on the engine stream (torques: getTorques() after synchronize())
+	void stepAsync() { check(saip_batch_step_async(_batch)); }
+	// semi-implicit Euler steps of the resident state under the torques of the last cycle; gravity nullptr = the model's
+	void integrate(double dt, int substeps = 1, const double* gravity = nullptr, double damping = 0.0) {
+		pushState();
+		check(saip_batch_integrate(_batch, dt, substeps, gravity, damping));
+	}
+	// `steps` closed-loop periods {internal OTGs, control cycle, integrate} enqueued without host synchronisation
+	void rolloutAsync(int steps, double sim_dt, int substeps = 1, const double* gravity = nullptr, double damping = 0.0) {
+		pushState();
+		check(saip_batch_rollout_async(_batch, steps, sim_dt, substeps, gravity, damping));
+	}
+	void synchronize() { check(saip_batch_synchronize(_batch)); }
+	// [dof][B] torques of the last cycle; status() is refreshed
+	std::vector<double> getTorques() {
+		std::vector<double> tau((size_t)_robot->dof() * _robot->batchSize());
+		_status.assign(_robot->batchSize(), 0);
+		check(saip_batch_get_torques_host(_batch, tau.data(), _status.data()));
+		return tau;
+	}
+	// read the resident state back into the SaiModel mirror (after integrate / rolloutAsync): robot->q(), robot->dq()
+	void pullState() {
+		std::vector<double> q(_robot->_q.size()), dq(_robot->_dq.size());
+		check(saip_batch_get_state_host(_batch, q.data(), dq.data()));
+		_robot->_q = std::move(q);
+		_robot->_dq = std::move(dq);
+		_robot->_version++;
+		for (auto& a : _robot->_attached)
+			if (a.batch == _batch) a.pushed = _robot->_version;  // the device already holds this state
+	}
+
+	// ---- rollout recorder: per-period trajectory log and running summaries of rolloutAsync, kept on the device (saip.h)
+	struct RolloutLog {
+		int samples = 0, rows = 0, first_period = 0, stride = 1;
+		std::vector<double> data;     // [samples][rows][B], chronological; rows: the recorded channels in the order of their bits
+		std::vector<uint8_t> status;  // [samples][B]
+	};
+	// channels: SAIP_RECORD_* bits; task: the motion-force task of the pose / error channels and of the error summaries, or nullptr
+	void recordRollouts(int capacity, int stride = 1, unsigned channels = SAIP_RECORD_Q | SAIP_RECORD_DQ | SAIP_RECORD_TAU,
+						const std::shared_ptr<MotionForceTask>& task = nullptr, bool summaries = false) {
+		const TemplateTask* t = task.get();
+		if (t && t->_batch != _batch) throw std::invalid_argument("recordRollouts: the task does not belong to this controller");
+		check(saip_batch_rollout_recorder_attach(_batch, capacity, stride, channels, t ? t->_id : -1, summaries ? 1 : 0));
+	}
+	void stopRecordingRollouts() { check(saip_batch_rollout_recorder_detach(_batch)); }
+	void resetRolloutRecorder() { check(saip_batch_rollout_recorder_reset(_batch)); }
+	RolloutLog rolloutLog() {
+		RolloutLog log;
+		check(saip_batch_rollout_log_info(_batch, &log.samples, &log.rows, &log.first_period, &log.stride));
+		log.data.resize((size_t)log.samples * log.rows * _robot->batchSize());
+		log.status.resize((size_t)log.samples * _robot->batchSize());
+		if (log.samples) check(saip_batch_rollout_log_host(_batch, log.data.data(), log.status.data()));
+		return log;
+	}
+	// [8][B] (saip.h)
+	std::vector<double> rolloutSummary() {
+		std::vector<double> out((size_t)SAIP_RECORD_SUMMARY_ROWS * _robot->batchSize());
+		check(saip_batch_rollout_summary_host(_batch, out.data()));
+		return out;
+	}
+
 private:
 	template <typename T>
 	std::shared_ptr<T> byName(const std::string& name, TaskType type, const char* what) {

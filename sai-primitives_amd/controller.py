@@ -1218,6 +1218,7 @@ class RobotController:
         _set_base(h, robot._T_base)
         self._pushed_version = -1
         self._has_device = robot.device >= 0
+        self._rec_mask = 0  # channels of the attached rollout recorder
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -1338,6 +1339,71 @@ class RobotController:
         self._push_state()
         g, gp = self._grav(gravity)
         self._call("saip_batch_rollout_async", int(steps), float(sim_dt), int(substeps), gp, float(damping))
+
+    # -- rollout recorder: per-period trajectory log and running summaries of rolloutAsync, kept on the device (saip.h)
+    _REC_CHANNELS = {"q": capi.SAIP_RECORD_Q, "dq": capi.SAIP_RECORD_DQ, "tau": capi.SAIP_RECORD_TAU, "pose": capi.SAIP_RECORD_POSE,
+                     "error": capi.SAIP_RECORD_ERROR}
+
+    def recordRollouts(self, capacity: int, stride: int = 1, channels=("q", "dq", "tau"), task=None, summaries: bool = False):
+        """attach a recorder to the rollouts of this controller: every stride-th period is sampled into a ring of the last `capacity`
+        samples.  channels: any of "q", "dq", "tau", "pose", "error" (the last two of `task`, a MotionForceTask of this controller or
+        its name).  summaries: running per-instance summaries over every period (rolloutSummary)."""
+        mask = 0
+        for c in channels:
+            if c not in self._REC_CHANNELS:
+                raise ValueError(f"recordRollouts: unknown channel {c!r} (one of {sorted(self._REC_CHANNELS)})")
+            mask |= self._REC_CHANNELS[c]
+        if isinstance(task, str):
+            task = self.getMotionForceTaskByName(task)
+        if task is not None and task not in self._tasks:
+            raise ValueError("recordRollouts: the task does not belong to this controller")
+        self._call("saip_batch_rollout_recorder_attach", int(capacity), int(stride), mask, -1 if task is None else task._id, int(bool(summaries)))
+        self._rec_mask = mask
+
+    def stopRecordingRollouts(self):
+        self._call("saip_batch_rollout_recorder_detach")
+        self._rec_mask = 0
+
+    def resetRolloutRecorder(self):
+        """period counter back to 0, log emptied, summaries zeroed"""
+        self._call("saip_batch_rollout_recorder_reset")
+
+    def rolloutLog(self):
+        """the samples in chronological order: dict of (n, B, dof) arrays "q", "dq", "tau", (n, B, 3) "position", (n, B, 3, 3) "orientation",
+        (n, B, 3) "position_error" and "orientation_error" for the recorded channels, plus "status" (n, B) and "period" (n,)"""
+        L = capi.lib()
+        n, rows, first, stride = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._call("saip_batch_rollout_log_info", C.byref(n), C.byref(rows), C.byref(first), C.byref(stride))
+        n, rows, B, dof = n.value, rows.value, self.batch_size, self._robot.dof()
+        out, st = np.zeros((n, rows, B)), np.zeros((n, B), np.uint8)
+        if n:
+            self._call("saip_batch_rollout_log_host", _dptr(out), st.ctypes.data_as(C.POINTER(C.c_ubyte)))
+        # the rows of a sample: the recorded channels in the order of their bits
+        log = {"status": st, "period": first.value + stride.value * np.arange(n)}
+        at = 0
+        widths = {"q": dof, "dq": dof, "tau": dof, "pose": 12, "error": 6}
+        for name in ("q", "dq", "tau", "pose", "error"):
+            if not (self._rec_mask & self._REC_CHANNELS[name]):
+                continue
+            blk = out[:, at:at + widths[name]].transpose(0, 2, 1)
+            at += widths[name]
+            if name == "pose":
+                log["position"] = blk[:, :, :3].copy()
+                log["orientation"] = blk[:, :, 3:].reshape(n, B, 3, 3).copy()
+            elif name == "error":
+                log["position_error"] = blk[:, :, :3].copy()
+                log["orientation_error"] = blk[:, :, 3:].copy()
+            else:
+                log[name] = blk.copy()
+        assert at == rows
+        return log
+
+    def rolloutSummary(self):
+        """(B, 8): sum T tau.tau, sum T |e_pos|^2, sum T |e_ori|^2, max |e_pos|, max |e_ori|, max |tau_j|, max |dq_j|, periods with
+        status != 0 (saip.h)"""
+        out = np.empty((capi.SAIP_RECORD_SUMMARY_ROWS, self.batch_size))
+        self._call("saip_batch_rollout_summary_host", _dptr(out))
+        return out.T.copy()
 
     def setTorques(self, tau):
         """overwrite the resident torques the next integrate() applies: (B, dof)"""

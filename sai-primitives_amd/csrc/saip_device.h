@@ -176,6 +176,28 @@ struct SimParams {
 	double* ddq;           // optional [n][ld] joint accelerations of the last substep
 };
 
+// one observed rollout period (saip_rollout_record.hip).  Passed to the kernel by value.
+enum { REC_Q = 1, REC_DQ = 2, REC_TAU = 4, REC_POSE = 8, REC_ERROR = 16, REC_ALL = 31, REC_SUMMARY_ROWS = 8 };
+struct RecordParams {
+	int B, ld, n;
+	int slot;                    // log slot of this period's sample, -1: not a sampled period (summaries only)
+	unsigned channels;           // REC_* bits: the rows of a sample, in that order
+	int rows;                    // rows of one sample = what `channels` adds up to
+	int task;                    // motion-force task of the pose / error rows and of summary rows 1..4, -1: none
+	int pad_;
+	double T;                    // length of the period (sim_dt * substeps): weight of the summary integrals
+	const ModelDev* model;
+	const TaskDev* tasks;
+	const double* q;             // [n][ld] the state as the period's integration left it
+	const double* dq;            // [n][ld]
+	const double* tau;           // [n][ld] the torques applied during the period
+	const uint8_t* status;       // [ld] status of the period's cycle
+	const double* goal;          // [goal_comps][ld] user goal block of `task`
+	double* log;                 // [capacity][rows][ld]
+	uint8_t* status_log;         // [capacity][ld]
+	double* summary;             // [REC_SUMMARY_ROWS][ld] running summaries, nullptr: off
+};
+
 // robot-model queries (saip_model_query.hip).  Passed to the kernels by value.
 enum { SAIP_MAXQF = 8 };         // = SAIP_MAX_QUERY_FRAMES
 struct FrameQuery {

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <utility>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -32,6 +33,7 @@ hipError_t launch_otg_pair(const OtgDev& Oc, const OtgDev& Oj, int B, int ld, hi
 hipError_t launch_integrate_otg_pair(const SimParams& S, const OtgDev& Oc, const OtgDev& Oj, int B, int ld, hipStream_t stream);
 int otg_state_fields();
 hipError_t launch_integrate(const SimParams& S, bool tree, hipStream_t stream);
+hipError_t launch_rollout_record(const RecordParams& P, bool tree, hipStream_t stream);
 }  // namespace saip
 
 using saip::CycleParams;
@@ -435,6 +437,17 @@ struct saip_batch {
 	bool flagged_on_list = false;            // saip_batch_set_flagged_recompute: eight-lane kernels hand flagged instances to the list launch instead of their slow tail
 	FlagList flags;                          // the device-side work list of the slow path
 	bool otg_prelaunched = false;            // rollouts: the paired OTG step of the coming cycle already ran, fused with the previous integrate
+	// saip_batch_rollout_recorder_attach: the observer of the rollout periods (saip_rollout_record.hip).  Its arrays are its own (freed by
+	// _detach), not part of `allocs`.
+	struct Recorder {
+		bool attached = false;
+		int capacity = 0, stride = 1, task = -1, rows = 0;
+		unsigned channels = 0;
+		long long period = 0;                // recorded periods so far: the global period counter p
+		double* log = nullptr;               // [capacity][rows][ld], a ring over the samples (nullptr: empty channel mask)
+		uint8_t* status_log = nullptr;       // [capacity][ld]
+		double* summary = nullptr;           // [8][ld] (nullptr: summaries off)
+	} rec;
 };
 
 static bool has_device(const saip_batch* b) { return b->device >= 0; }
@@ -480,6 +493,8 @@ extern "C" void saip_batch_destroy(saip_batch* b) {
 		for (hipEvent_t e : b->time_ev)
 			if (e) (void)hipEventDestroy(e);
 		for (void* p : b->allocs) (void)hipFree(p);
+		for (void* p : {(void*)b->rec.log, (void*)b->rec.status_log, (void*)b->rec.summary})
+			if (p) (void)hipFree(p);
 		if (b->stream) (void)hipStreamDestroy(b->stream);
 	}
 	delete b;
@@ -2050,6 +2065,170 @@ extern "C" saip_status saip_batch_integrate(saip_batch* b, double dt, int subste
 	if (!(dt > 0) || substeps < 1 || damping < 0) return fail(SAIP_ERR_INVALID_ARGUMENT, "saip_batch_integrate: dt > 0, substeps >= 1, damping >= 0 required");
 	return enqueue_integrate(b, dt, substeps, gravity, damping);
 }
+// ---- rollout recorder (saip_rollout_record.hip): per-period trajectory log and running summaries of saip_batch_rollout_async
+static int record_rows(unsigned channels, int n) {
+	return ((channels & saip::REC_Q) ? n : 0) + ((channels & saip::REC_DQ) ? n : 0) + ((channels & saip::REC_TAU) ? n : 0) +
+		   ((channels & saip::REC_POSE) ? 12 : 0) + ((channels & saip::REC_ERROR) ? 6 : 0);
+}
+static void record_free(saip_batch* b) {
+	auto& R = b->rec;
+	for (void* p : {(void*)R.log, (void*)R.status_log, (void*)R.summary})
+		if (p) (void)hipFree(p);
+	R = saip_batch::Recorder();
+}
+// the observation of the period that has just been integrated: the sample slot is computed here, at enqueue time (no device-side counter)
+static saip_status record_period(saip_batch* b, double T) {
+	auto& R = b->rec;
+	const long long p = ++R.period;
+	const bool sample = R.channels && p % R.stride == 0;
+	if (!sample && !R.summary) return SAIP_OK;
+	saip::RecordParams P;
+	P.B = b->B;
+	P.ld = b->ld;
+	P.n = b->model->n;
+	P.slot = sample ? (int)((p / R.stride - 1) % R.capacity) : -1;
+	P.channels = R.channels;
+	P.rows = R.rows;
+	P.task = R.task;
+	P.pad_ = 0;
+	P.T = T;
+	P.model = b->model_dev;
+	P.tasks = b->tasks_dev;
+	P.q = b->q;
+	P.dq = b->dq;
+	P.tau = b->tau_bound ? b->tau_bound : b->tau;
+	P.status = b->status;
+	P.goal = R.task >= 0 ? b->tasks[R.task].goal_dev : nullptr;
+	P.log = R.log;
+	P.status_log = R.status_log;
+	P.summary = R.summary;
+	hipError_t e = saip::launch_rollout_record(P, b->model->dev.is_tree != 0, b->stream);
+	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "rollout recorder launch failed: %s", hipGetErrorString(e));
+	return SAIP_OK;
+}
+// finalized as a controller (no device needed yet: argument errors come first, as in the model queries)
+static saip_status need_controller(const saip_batch* b, const char* fn) {
+	if (!b) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null batch", fn);
+	if (!b->finalized) return fail(SAIP_ERR_ORDER, "%s: call saip_batch_finalize first", fn);
+	if (b->model_only) return fail(SAIP_ERR_ORDER, "%s: the batch was finalized for model queries only (no tasks)", fn);
+	return SAIP_OK;
+}
+static saip_status need_recorder(const saip_batch* b, const char* fn) {
+	saip_status st = need_controller(b, fn);
+	if (st) return st;
+	if (!b->rec.attached) return fail(SAIP_ERR_ORDER, "%s: no rollout recorder is attached (saip_batch_rollout_recorder_attach)", fn);
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_rollout_recorder_attach(saip_batch* b, int capacity, int stride, unsigned channels, int task, int summaries) {
+	const char* fn = "saip_batch_rollout_recorder_attach";
+	saip_status st = need_controller(b, fn);
+	if (st) return st;
+	if (b->rec.attached) return fail(SAIP_ERR_ORDER, "%s: a recorder is already attached (saip_batch_rollout_recorder_detach first)", fn);
+	if (capacity < 1 || stride < 1) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: capacity >= 1 and stride >= 1 required", fn);
+	if (channels & ~(unsigned)saip::REC_ALL) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: unknown channel bits 0x%x", fn, channels & ~(unsigned)saip::REC_ALL);
+	if (!channels && !summaries) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: nothing to record (empty channel mask and no summaries)", fn);
+	if (task < -1 || task >= (int)b->tasks.size()) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: task id %d out of range", fn, task);
+	if (task >= 0 && b->tasks[task].dev.type != saip::TASK_MOTION_FORCE) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: task %d is not a motion-force task", fn, task);
+	if ((channels & (saip::REC_POSE | saip::REC_ERROR)) && task < 0) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the pose and error channels need a motion-force task", fn);
+	const int rows = record_rows(channels, b->model->n);
+	// [capacity][rows][ld] doubles: the byte count must fit a size_t
+	const size_t slot_bytes = (size_t)(rows > 0 ? rows : 1) * b->ld * sizeof(double);
+	if ((size_t)capacity > SIZE_MAX / slot_bytes) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a log of %d samples of %d rows is too large", fn, capacity, rows);
+	if ((st = need_ready(b, fn))) return st;
+	auto& R = b->rec;
+	auto alloc_zero = [&](void** p, size_t bytes) -> saip_status {
+		HIP_TRY(hipMalloc(p, bytes));
+		HIP_TRY(hipMemset(*p, 0, bytes));
+		return SAIP_OK;
+	};
+	if (channels) {
+		if ((st = alloc_zero((void**)&R.log, (size_t)capacity * slot_bytes)) || (st = alloc_zero((void**)&R.status_log, (size_t)capacity * b->ld))) {
+			record_free(b);
+			return st;
+		}
+	}
+	if (summaries && (st = alloc_zero((void**)&R.summary, (size_t)saip::REC_SUMMARY_ROWS * b->ld * sizeof(double)))) {
+		record_free(b);
+		return st;
+	}
+	R.attached = true;
+	R.capacity = capacity;
+	R.stride = stride;
+	R.channels = channels;
+	R.task = task;
+	R.rows = rows;
+	R.period = 0;
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_rollout_recorder_detach(saip_batch* b) {
+	saip_status st = need_recorder(b, "saip_batch_rollout_recorder_detach");
+	if (st) return st;
+	if ((st = need_ready(b, "saip_batch_rollout_recorder_detach"))) return st;
+	HIP_TRY(hipStreamSynchronize(b->stream));  // a recorded period may still be in flight
+	record_free(b);
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_rollout_recorder_reset(saip_batch* b) {
+	saip_status st = need_recorder(b, "saip_batch_rollout_recorder_reset");
+	if (st) return st;
+	if ((st = need_ready(b, "saip_batch_rollout_recorder_reset"))) return st;
+	auto& R = b->rec;
+	if (R.log) HIP_TRY(hipMemsetAsync(R.log, 0, (size_t)R.capacity * R.rows * b->ld * sizeof(double), b->stream));
+	if (R.status_log) HIP_TRY(hipMemsetAsync(R.status_log, 0, (size_t)R.capacity * b->ld, b->stream));
+	if (R.summary) HIP_TRY(hipMemsetAsync(R.summary, 0, (size_t)saip::REC_SUMMARY_ROWS * b->ld * sizeof(double), b->stream));
+	R.period = 0;
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_rollout_log_info(saip_batch* b, int* n_samples, int* rows, int* first_period, int* stride) {
+	saip_status st = need_recorder(b, "saip_batch_rollout_log_info");
+	if (st) return st;
+	const auto& R = b->rec;
+	const long long taken = R.channels ? R.period / R.stride : 0;  // samples written so far; the ring keeps the last `capacity`
+	const long long n = taken < R.capacity ? taken : R.capacity;
+	if (n_samples) *n_samples = (int)n;
+	if (rows) *rows = R.rows;
+	if (first_period) *first_period = n ? (int)((taken - n + 1) * R.stride) : 0;
+	if (stride) *stride = R.stride;
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_rollout_log_host(saip_batch* b, double* out, uint8_t* status) {
+	const char* fn = "saip_batch_rollout_log_host";
+	saip_status st = need_recorder(b, fn);
+	if (st) return st;
+	if ((st = need_ready(b, fn))) return st;
+	const auto& R = b->rec;
+	const long long taken = R.channels ? R.period / R.stride : 0;
+	const long long n = taken < R.capacity ? taken : R.capacity;
+	// chronological order: the ring from the oldest sample's slot to its end, then from slot 0 (rows of consecutive slots are consecutive
+	// [ld] arrays, so each piece is one 2-D copy)
+	const long long first = (taken - n) % R.capacity;
+	const long long piece[2][2] = {{first, first + n <= R.capacity ? n : R.capacity - first}, {0, first + n <= R.capacity ? 0 : first + n - R.capacity}};
+	long long done = 0;
+	for (const auto& pc : piece) {
+		if (pc[1] == 0) continue;
+		if (out)
+			HIP_TRY(hipMemcpy2DAsync(out + (size_t)done * R.rows * b->B, (size_t)b->B * sizeof(double), R.log + (size_t)pc[0] * R.rows * b->ld,
+									 (size_t)b->ld * sizeof(double), (size_t)b->B * sizeof(double), (size_t)pc[1] * R.rows, hipMemcpyDeviceToHost, b->stream));
+		if (status)
+			HIP_TRY(hipMemcpy2DAsync(status + (size_t)done * b->B, (size_t)b->B, R.status_log + (size_t)pc[0] * b->ld, (size_t)b->ld, (size_t)b->B,
+									 (size_t)pc[1], hipMemcpyDeviceToHost, b->stream));
+		done += pc[1];
+	}
+	HIP_TRY(hipStreamSynchronize(b->stream));
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_rollout_summary_host(saip_batch* b, double* out) {
+	const char* fn = "saip_batch_rollout_summary_host";
+	saip_status st = need_recorder(b, fn);
+	if (st) return st;
+	if (!b->rec.summary) return fail(SAIP_ERR_ORDER, "%s: the recorder was attached without summaries", fn);
+	if (!out) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null output", fn);
+	if ((st = need_ready(b, fn))) return st;
+	return copy_d2h(b, out, b->rec.summary, saip::REC_SUMMARY_ROWS);
+}
+extern "C" double* saip_batch_rollout_log_device(saip_batch* b) { return b ? b->rec.log : nullptr; }
+extern "C" double* saip_batch_rollout_summary_device(saip_batch* b) { return b ? b->rec.summary : nullptr; }
+
 // steps x { internal OTGs, control cycle, integrate } on the engine stream, no host synchronisation.  One period is 3-5 small
 // launches.  Plain back-to-back stream launches are the default: they were measured FASTER than replaying a hipGraph of the period
 // (68.6 vs 74.2 us per period at B = 4096, 65.7 vs 70.4 us at B = 256, tools/rollout_bench.py) -- the host enqueues far ahead of the
@@ -2073,11 +2252,11 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 		if (integrated) {  // the bookkeeping of enqueue_integrate
 			b->models_valid = false;
 			b->state_epoch++;
-			return SAIP_OK;
+		} else if ((s2 = enqueue_integrate(b, sim_dt, substeps, gravity, damping, more))) {
+			b->otg_prelaunched = false;
+			return s2;
 		}
-		s2 = enqueue_integrate(b, sim_dt, substeps, gravity, damping, more);
-		if (s2) b->otg_prelaunched = false;
-		return s2;
+		return b->rec.attached ? record_period(b, sim_dt * substeps) : SAIP_OK;
 	};
 	for (int done = 0; done < steps; done++)
 		if ((st = period(done + 1 < steps))) return st;
