@@ -209,8 +209,43 @@ saip_status saip_batch_set_otg_jerk_limited(saip_batch*, int task, const double*
  * saip_batch_compute_control_torques, exactly like after robot->setQ(). */
 saip_status saip_batch_integrate(saip_batch*, double dt, int substeps, const double gravity[3], double damping);
 /* `steps` closed-loop control periods { internal OTGs -> control cycle -> integrate(sim_dt, substeps) } enqueued back to back on the
- * engine stream without host synchronisation (follow with saip_batch_synchronize); goals stay as they are on the device. */
+ * engine stream without host synchronisation (follow with saip_batch_synchronize); goals stay as they are on the device unless a goal
+ * schedule is attached (below). */
 saip_status saip_batch_rollout_async(saip_batch*, int steps, double sim_dt, int substeps, const double gravity[3], double damping);
+/* ---- goal schedules: time-varying task goals inside rollouts (the reference's example loops call setGoalPosition / setGoalOrientation /
+ * setGoalLinearVelocity every cycle as a function of time: examples 02, 03, 06, 09, 10).  A schedule is a list of keyframes for ONE
+ * contiguous range [first_component, first_component + n_components) of one task's goal block, in the component numbering of
+ * saip_batch_set_goal_field_host / saip_batch_goal_components (36 rows for a motion-force task, sensed force and moment included; 3m for
+ * a joint task).  At most one schedule per task; it stays attached across rollout calls until detached.
+ *   keyframes: host [n_keyframes][n_components][B] with per_instance = 1, [n_keyframes][n_components] (the same for every instance)
+ *        with per_instance = 0; copied to the device by _attach ([K][count][ld] or [K][count]), never inside a rollout.
+ *        saip_batch_goal_schedule_device returns the resident copy, to be rewritten in place between rollouts (a sampler on the device).
+ *   timing: a period counter c, shared by every schedule of the batch, starts at 0 at _attach and _rewind and advances with every period
+ *        of saip_batch_rollout_async.  Period c uses keyframe i = c / stride and the fraction s = (c % stride) / (double)stride; from
+ *        c = (n_keyframes - 1) * stride on, the last keyframe is held.  i and s are computed at enqueue time and passed as launch arguments.
+ *   SAIP_SCHEDULE_HOLD   the rows of keyframe i.
+ *   SAIP_SCHEDULE_LINEAR a + s * (b - a) per component between keyframes i and i + 1, difference, product and sum each rounded once in
+ *        double precision (no fused multiply-add), so a host restatement gives the same bits; at s == 0 the rows of keyframe i exactly.
+ *        Rows 3..11 of a motion-force task (the goal rotation, row-major) are interpolated on SO(3) instead:
+ *        R(s) = R0 Exp(s Log(R0^T R1)); the range must then cover all nine rows (or none), every keyframe must be a rotation
+ *        (max |R^T R - I| <= 1e-6) and consecutive keyframes at most pi - 1e-3 rad apart.  HOLD validates nothing, like
+ *        saip_batch_set_goal_field_host.
+ * A period with a schedule attached enqueues one small launch that writes the scheduled goal rows of every scheduled task (columns
+ * 0..B-1 only), then the usual OTG step, cycle, integration and recorder observation: the OTG step sees the period's goal as it does
+ * after a host setGoal...(), and the recorder's error rows are taken against it.  The integration is then never fused with the next
+ * period's OTG step.  Without a schedule a rollout enqueues exactly what it did before.  saip_batch_step_async, saip_batch_integrate
+ * and saip_batch_compute_control_torques called directly apply no schedule and do not advance c.  After a rollout the goal rows hold
+ * the values applied last (saip_batch_get_goal_host).  _detach waits for the stream and frees the keyframes; task = -1 detaches all.
+ * SAIP_ERR_ORDER: before saip_batch_finalize, on a model-only batch, a second _attach on a task without _detach, _detach / _info of a
+ * task without a schedule.  Argument and order errors are reported before the device is needed. */
+enum { SAIP_SCHEDULE_HOLD = 0, SAIP_SCHEDULE_LINEAR = 1 };
+saip_status saip_batch_goal_schedule_attach(saip_batch*, int task, int first_component, int n_components, const double* keyframes,
+                                            int n_keyframes, int stride, int mode, int per_instance);
+saip_status saip_batch_goal_schedule_detach(saip_batch*, int task);
+saip_status saip_batch_goal_schedule_rewind(saip_batch*);
+/* any pointer may be NULL; period: the counter c */
+saip_status saip_batch_goal_schedule_info(saip_batch*, int task, int* first, int* count, int* n_keyframes, int* stride, int* mode, long long* period);
+double* saip_batch_goal_schedule_device(saip_batch*, int task);  /* NULL when the task has no schedule */
 /* ---- rollout recorder: a per-period trajectory log and running summaries of saip_batch_rollout_async, kept on the device (the
  * reference's example loops print or log the same quantities every period: state, torques, position / orientation error).  A recorder
  * is attached to a finalized batch and stays attached across rollout calls until detached.  It observes rollout periods only

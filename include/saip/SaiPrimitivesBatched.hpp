@@ -333,6 +333,35 @@ public:
 		return r;
 	}
 	void disableVelocitySaturation() { cfg([](saip_batch* b, int id) { return saip_batch_set_velocity_saturation(b, id, 0); }); }
+	// ---- goal schedules: time-varying goals inside RobotController::rolloutAsync from keyframes resident on the device (saip.h).
+	// Goal components [first, first + count) of this task; keyframes [n_keyframes][count] (the same for every instance) or
+	// [n_keyframes][count][B] (per instance); mode SAIP_SCHEDULE_HOLD or SAIP_SCHEDULE_LINEAR
+	void setGoalSchedule(int first, int count, const std::vector<double>& keyframes, int n_keyframes, int stride = 1, int mode = SAIP_SCHEDULE_HOLD) {
+		need();
+		const size_t per_frame = (size_t)(count > 0 ? count : 0), B = _robot->batchSize();
+		const size_t K = (size_t)(n_keyframes > 0 ? n_keyframes : 0);
+		if (K == 0 || per_frame == 0 || (keyframes.size() != K * per_frame && keyframes.size() != K * per_frame * B))
+			throw std::invalid_argument("setGoalSchedule: expected [n_keyframes][count] or [n_keyframes][count][B] keyframes");
+		const int per_instance = keyframes.size() == K * per_frame ? 0 : 1;  // (B == 1: the two layouts coincide)
+		check(saip_batch_goal_schedule_attach(_batch, _id, first, count, keyframes.data(), n_keyframes, stride, mode, per_instance));
+	}
+	// field: the name of a goal setter's field ("position", "orientation", "linear_velocity", ... / joint task: "position", "velocity",
+	// "acceleration")
+	void setGoalSchedule(const std::string& field, const std::vector<double>& keyframes, int n_keyframes, int stride = 1, int mode = SAIP_SCHEDULE_HOLD) {
+		int first = 0, count = 0;
+		if (!scheduleField(field, &first, &count)) throw std::invalid_argument("setGoalSchedule: task [" + _task_name + "] has no goal field " + field);
+		setGoalSchedule(first, count, keyframes, n_keyframes, stride, mode);
+	}
+	// detach this task's schedule; its goal keeps the values applied last
+	void clearGoalSchedule() {
+		need();
+		check(saip_batch_goal_schedule_detach(_batch, _id));
+	}
+	// the resident keyframes ([n_keyframes][count][ld] per instance, else [n_keyframes][count]), to be rewritten in place; nullptr without a schedule
+	double* goalScheduleDevice() {
+		need();
+		return saip_batch_goal_schedule_device(_batch, _id);
+	}
 	// (B x dof x dof as [dof*dof][B]) nullspace projector of this task for the current state, TemplateTask.h:71-77
 	std::vector<double> getTaskNullspace() {
 		need();
@@ -448,6 +477,7 @@ protected:
 		check(saip_batch_set_goal_field_host(_batch, _id, first, comps, v.data()));
 	}
 	virtual saip_status add(saip_batch* b, int* id) = 0;
+	virtual bool scheduleField(const std::string& field, int* first, int* count) const = 0;
 
 	std::shared_ptr<SaiModel> _robot;
 	std::string _task_name;
@@ -634,6 +664,21 @@ protected:
 		for (size_t b = 0; b < B; b++) r[b] = std::sqrt(e[b] * e[b] + e[B + b] * e[B + b] + e[2 * B + b] * e[2 * B + b]) < tolerance;
 		return r;
 	}
+	bool scheduleField(const std::string& field, int* first, int* count) const override {
+		static const struct {
+			const char* name;
+			int first, count;
+		} fields[] = {{"position", 0, 3},          {"orientation", 3, 9},           {"linear_velocity", 12, 3}, {"angular_velocity", 15, 3},
+					  {"linear_acceleration", 18, 3}, {"angular_acceleration", 21, 3}, {"force", 24, 3},           {"moment", 27, 3},
+					  {"sensed_force", 30, 3},     {"sensed_moment", 33, 3}};
+		for (const auto& f : fields)
+			if (field == f.name) {
+				*first = f.first;
+				*count = f.count;
+				return true;
+			}
+		return false;
+	}
 	saip_status add(saip_batch* b, int* id) override {
 		return saip_batch_add_motion_force_task(b, _task_name.c_str(), _link.c_str(), _pos, nullptr, _dt.empty() ? nullptr : _dt.data(),
 												_partial ? (int)_dt.size() / 3 : -1, _dr.empty() ? nullptr : _dr.data(),
@@ -695,6 +740,12 @@ public:
 	}
 
 protected:
+	bool scheduleField(const std::string& field, int* first, int* count) const override {
+		const int m = getTaskDof();
+		*count = m;
+		*first = field == "position" ? 0 : field == "velocity" ? m : 2 * m;
+		return field == "position" || field == "velocity" || field == "acceleration";
+	}
 	saip_status add(saip_batch* b, int* id) override {
 		return saip_batch_add_joint_task(b, _task_name.c_str(), _rows > 0 ? _S.data() : nullptr, _rows, _loop_timestep, id);
 	}
@@ -811,6 +862,9 @@ public:
 		for (auto& a : _robot->_attached)
 			if (a.batch == _batch) a.pushed = _robot->_version;  // the device already holds this state
 	}
+
+	// the period counter of the tasks' goal schedules (TemplateTask::setGoalSchedule) back to 0
+	void rewindGoalSchedules() { check(saip_batch_goal_schedule_rewind(_batch)); }
 
 	// ---- rollout recorder: per-period trajectory log and running summaries of rolloutAsync, kept on the device (saip.h)
 	struct RolloutLog {

@@ -588,6 +588,59 @@ class _Task:
         capi.check(capi.lib().saip_batch_get_goal_host(ctrl._h, self._id, _dptr(out)))
         return out.T.copy()
 
+    # -- goal schedules: time-varying goals inside rolloutAsync, from keyframes resident on the device (saip.h)
+    _SCHED_MODES = {"hold": capi.SAIP_SCHEDULE_HOLD, "linear": capi.SAIP_SCHEDULE_LINEAR}
+
+    def _schedule_fields(self):
+        """field name -> (first component, components) of this task's goal block"""
+        return {}
+
+    def setGoalSchedule(self, field, keyframes, stride=1, mode="hold"):
+        """attach a goal schedule to this task: period c of the controller's rollouts uses keyframe c // stride ("hold") or goes from it
+        towards the next one by the fraction (c % stride) / stride ("linear": component-wise, orientations on SO(3)); the last keyframe
+        is held.  field: a name of the goal setters ("position", "orientation", "linear_velocity", ... / joint task: "position",
+        "velocity", "acceleration") or (first, count) goal components.  keyframes: (K, count) for every instance or (K, B, count) per
+        instance; orientations also as (K, 3, 3) / (K, B, 3, 3)."""
+        ctrl = self._need_ctrl()
+        B = ctrl.batch_size
+        if isinstance(field, str):
+            fields = self._schedule_fields()
+            if field not in fields:
+                raise ValueError(f"setGoalSchedule: unknown field {field!r} (one of {sorted(fields)})")
+            first, count = fields[field]
+        else:
+            first, count = (int(v) for v in field)
+        if mode not in self._SCHED_MODES:
+            raise ValueError(f"setGoalSchedule: unknown mode {mode!r} (one of {sorted(self._SCHED_MODES)})")
+        k = np.asarray(keyframes, float)
+        if count == 9 and k.shape[-2:] == (3, 3):
+            k = k.reshape(k.shape[:-2] + (9,))
+        if k.ndim == 2 and k.shape[1] == count:
+            a, per_instance = np.ascontiguousarray(k), 0
+        elif k.ndim == 3 and k.shape[1:] == (B, count):
+            a, per_instance = np.ascontiguousarray(k.transpose(0, 2, 1)), 1
+        else:
+            raise ValueError(f"setGoalSchedule: keyframes of shape (K, {count}) or (K, {B}, {count}) expected, got {k.shape}")
+        ctrl._call("saip_batch_goal_schedule_attach", self._id, first, count, _dptr(a), a.shape[0], int(stride), self._SCHED_MODES[mode], per_instance)
+
+    def clearGoalSchedule(self):
+        """detach this task's schedule; its goal keeps the values applied last"""
+        self._need_ctrl()._call("saip_batch_goal_schedule_detach", self._id)
+
+    def goalScheduleInfo(self):
+        """dict first, count, n_keyframes, stride, mode, period (the period counter every schedule of the controller shares)"""
+        v = [C.c_int(0) for _ in range(5)]
+        period = C.c_longlong(0)
+        self._need_ctrl()._call("saip_batch_goal_schedule_info", self._id, *(C.byref(x) for x in v), C.byref(period))
+        mode = {m: name for name, m in self._SCHED_MODES.items()}[v[4].value]
+        return dict(first=v[0].value, count=v[1].value, n_keyframes=v[2].value, stride=v[3].value, mode=mode, period=period.value)
+
+    def goalScheduleDevice(self):
+        """device pointer of the resident keyframes, (K, count, ld) per instance or (K, count): rewrite them in place on the controller's
+        stream (or behind synchronize()) and the next rollout follows the new ones.  None without a schedule."""
+        ctrl = self._need_ctrl()
+        return capi.lib().saip_batch_goal_schedule_device(ctrl._h, self._id)
+
     def getTaskNullspace(self, device=False):
         """(B, dof, dof) nullspace projector N of this task for the current state (TemplateTask.h:71-77)"""
         if self._manual:
@@ -660,6 +713,11 @@ class MotionForceTask(_Task):
             _dptr(self.dt_) if len(self.dt_) else None, len(self.dt_) if self.partial else -1,
             _dptr(self.dr_) if len(self.dr_) else None, len(self.dr_) if self.partial else -1, self._dt, C.byref(tid)))
         return tid.value
+
+    def _schedule_fields(self):
+        return {"position": (0, 3), "orientation": (3, 9), "linear_velocity": (12, 3), "angular_velocity": (15, 3),
+                "linear_acceleration": (18, 3), "angular_acceleration": (21, 3), "force": (24, 3), "moment": (27, 3),
+                "sensed_force": (30, 3), "sensed_moment": (33, 3)}
 
     # goals, MotionForceTask.h:211-247
     def setGoalPosition(self, x):
@@ -1044,6 +1102,10 @@ class JointTask(_Task):
     def isFullJointTask(self):
         return self.getTaskDof() == self._robot.dof()
 
+    def _schedule_fields(self):
+        m = self.getTaskDof()
+        return {"position": (0, m), "velocity": (m, m), "acceleration": (2 * m, m)}
+
     # goals, JointTask.h:140-175
     def setGoalPosition(self, q):
         self._set_field(0, self.getTaskDof(), q, "goal position vector size not consistent with task dof in JointTask::setGoalPosition")
@@ -1339,6 +1401,10 @@ class RobotController:
         self._push_state()
         g, gp = self._grav(gravity)
         self._call("saip_batch_rollout_async", int(steps), float(sim_dt), int(substeps), gp, float(damping))
+
+    def rewindGoalSchedules(self):
+        """the period counter of the tasks' goal schedules (task.setGoalSchedule) back to 0: the next rollout starts at the first keyframe"""
+        self._call("saip_batch_goal_schedule_rewind")
 
     # -- rollout recorder: per-period trajectory log and running summaries of rolloutAsync, kept on the device (saip.h)
     _REC_CHANNELS = {"q": capi.SAIP_RECORD_Q, "dq": capi.SAIP_RECORD_DQ, "tau": capi.SAIP_RECORD_TAU, "pose": capi.SAIP_RECORD_POSE,

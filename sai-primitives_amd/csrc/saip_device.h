@@ -198,6 +198,25 @@ struct RecordParams {
 	double* summary;             // [REC_SUMMARY_ROWS][ld] running summaries, nullptr: off
 };
 
+// the goal schedules of one rollout period (saip_goal_schedule.hip): one entry per scheduled task.  Passed to the kernel by value.
+enum { SCHED_HOLD = 0, SCHED_LINEAR = 1 };
+struct ScheduleEntry {
+	double* goal;                // [goal_comps][ld] user goal block of the task
+	const double* key;           // the resident keyframes: [K][count][ld] (per_instance) or [K][count] (batch-uniform)
+	int first, count;            // the scheduled goal rows [first, first + count)
+	int K;                       // keyframes
+	int i;                       // keyframe of this period, already clamped to K - 1 on the host
+	int mode;                    // SCHED_*
+	int per_instance;
+	int rot;                     // SCHED_LINEAR over rows 3..11 of a motion-force task: those nine rows are interpolated on SO(3)
+	int pad_;
+	double s;                    // fraction towards keyframe i + 1, in [0, 1); 0 on a keyframe period and past the last keyframe
+};
+struct ScheduleParams {
+	int B, ld, n, pad_;          // n: entries in use
+	ScheduleEntry e[SAIP_MAXT];
+};
+
 // robot-model queries (saip_model_query.hip).  Passed to the kernels by value.
 enum { SAIP_MAXQF = 8 };         // = SAIP_MAX_QUERY_FRAMES
 struct FrameQuery {

@@ -34,6 +34,7 @@ hipError_t launch_integrate_otg_pair(const SimParams& S, const OtgDev& Oc, const
 int otg_state_fields();
 hipError_t launch_integrate(const SimParams& S, bool tree, hipStream_t stream);
 hipError_t launch_rollout_record(const RecordParams& P, bool tree, hipStream_t stream);
+hipError_t launch_goal_schedule(const ScheduleParams& P, hipStream_t stream);
 }  // namespace saip
 
 using saip::CycleParams;
@@ -448,6 +449,16 @@ struct saip_batch {
 		uint8_t* status_log = nullptr;       // [capacity][ld]
 		double* summary = nullptr;           // [8][ld] (nullptr: summaries off)
 	} rec;
+	// saip_batch_goal_schedule_attach: time-varying goals of the rollout periods (saip_goal_schedule.hip), at most one per task.  The
+	// keyframes are the schedule's own allocation (freed by _detach), not part of `allocs`.
+	struct Schedule {
+		bool attached = false;
+		int first = 0, count = 0, K = 0, stride = 1, mode = 0, per_instance = 0, rot = 0;
+		double* key = nullptr;               // [K][count][ld] (per instance) or [K][count] (batch-uniform)
+	};
+	std::vector<Schedule> sched;             // one slot per task once a schedule has been attached
+	int n_sched = 0;                         // attached schedules
+	long long sched_period = 0;              // rollout periods since the last attach / rewind: the counter c every schedule shares
 };
 
 static bool has_device(const saip_batch* b) { return b->device >= 0; }
@@ -495,6 +506,8 @@ extern "C" void saip_batch_destroy(saip_batch* b) {
 		for (void* p : b->allocs) (void)hipFree(p);
 		for (void* p : {(void*)b->rec.log, (void*)b->rec.status_log, (void*)b->rec.summary})
 			if (p) (void)hipFree(p);
+		for (auto& S : b->sched)
+			if (S.key) (void)hipFree(S.key);
 		if (b->stream) (void)hipStreamDestroy(b->stream);
 	}
 	delete b;
@@ -2229,6 +2242,175 @@ extern "C" saip_status saip_batch_rollout_summary_host(saip_batch* b, double* ou
 extern "C" double* saip_batch_rollout_log_device(saip_batch* b) { return b ? b->rec.log : nullptr; }
 extern "C" double* saip_batch_rollout_summary_device(saip_batch* b) { return b ? b->rec.summary : nullptr; }
 
+// ---- goal schedules (saip_goal_schedule.hip): the user goals of every rollout period from keyframes resident on the device
+static double sched_max_abs(const double* a, int n) {
+	double m = 0;
+	for (int i = 0; i < n; i++) m = std::fmax(m, std::fabs(a[i]));
+	return m;
+}
+// LINEAR over the rotation rows: every keyframe orthonormal to 1e-6, consecutive keyframes less than pi - 1e-3 apart.  `at(k, r)`: row r
+// (3..11 of the goal block) of keyframe k for the instance under test
+template <typename At>
+static const char* sched_check_rotations(int K, At at) {
+	double prev[9];
+	for (int k = 0; k < K; k++) {
+		double R[9], G[9];
+		for (int e = 0; e < 9; e++) R[e] = at(k, e);
+		for (int i = 0; i < 3; i++)
+			for (int j = 0; j < 3; j++) G[3 * i + j] = R[i] * R[j] + R[3 + i] * R[3 + j] + R[6 + i] * R[6 + j] - (i == j ? 1.0 : 0.0);
+		if (!(sched_max_abs(G, 9) <= 1e-6)) return "a rotation keyframe is not orthonormal (max |R^T R - I| > 1e-6)";
+		if (k > 0) {
+			double M[9];
+			for (int i = 0; i < 3; i++)
+				for (int j = 0; j < 3; j++) M[3 * i + j] = prev[i] * R[j] + prev[3 + i] * R[3 + j] + prev[6 + i] * R[6 + j];
+			const double w[3] = {0.5 * (M[7] - M[5]), 0.5 * (M[2] - M[6]), 0.5 * (M[3] - M[1])};
+			const double angle = std::atan2(std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), 0.5 * (M[0] + M[4] + M[8] - 1.0));
+			if (!(angle <= M_PI - 1e-3)) return "two consecutive rotation keyframes are more than pi - 1e-3 rad apart (the geodesic is ill-defined)";
+		}
+		for (int e = 0; e < 9; e++) prev[e] = R[e];
+	}
+	return nullptr;
+}
+static saip_status need_schedule(const saip_batch* b, int task, const char* fn) {
+	saip_status st = need_controller(b, fn);
+	if (st) return st;
+	if (task < 0 || task >= (int)b->tasks.size()) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: task id %d out of range", fn, task);
+	if (task >= (int)b->sched.size() || !b->sched[task].attached)
+		return fail(SAIP_ERR_ORDER, "%s: task %d has no goal schedule (saip_batch_goal_schedule_attach)", fn, task);
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_goal_schedule_attach(saip_batch* b, int task, int first, int count, const double* keyframes, int n_keyframes,
+													   int stride, int mode, int per_instance) {
+	const char* fn = "saip_batch_goal_schedule_attach";
+	saip_status st = need_controller(b, fn);
+	if (st) return st;
+	if (task < 0 || task >= (int)b->tasks.size()) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: task id %d out of range", fn, task);
+	if (task < (int)b->sched.size() && b->sched[task].attached)
+		return fail(SAIP_ERR_ORDER, "%s: task %d already has a goal schedule (saip_batch_goal_schedule_detach first)", fn, task);
+	if (!keyframes) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null keyframes", fn);
+	const auto& T = b->tasks[task];
+	if (first < 0 || count <= 0 || count > T.dev.goal_comps || first > T.dev.goal_comps - count)
+		return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: components [%d, %d + %d) outside the %d goal components of task %d", fn, first, first, count, T.dev.goal_comps, task);
+	if (n_keyframes < 1 || stride < 1) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: n_keyframes >= 1 and stride >= 1 required", fn);
+	if (mode != saip::SCHED_HOLD && mode != saip::SCHED_LINEAR) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: unknown mode %d", fn, mode);
+	per_instance = per_instance ? 1 : 0;
+	// [K][count][ld] (or [K][count]) doubles: the byte count must fit a size_t
+	const size_t frame_bytes = (size_t)count * (per_instance ? (size_t)b->ld : 1) * sizeof(double);
+	if ((size_t)n_keyframes > SIZE_MAX / frame_bytes) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %d keyframes of %d components are too large", fn, n_keyframes, count);
+	int rot = 0;
+	if (mode == saip::SCHED_LINEAR && T.dev.type == saip::TASK_MOTION_FORCE && first < 12 && first + count > 3) {
+		if (first > 3 || first + count < 12)
+			return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a linear schedule must cover all or none of the rotation rows 3..11 (got [%d, %d))", fn, first, first + count);
+		rot = 1;
+		const size_t B = b->B, r0 = 3 - first;
+		const char* bad = nullptr;
+		for (size_t i = 0; i < (per_instance ? B : 1) && !bad; i++)
+			bad = sched_check_rotations(n_keyframes, [&](int k, int e) {
+				const size_t row = (size_t)k * count + r0 + e;
+				return per_instance ? keyframes[row * B + i] : keyframes[row];
+			});
+		if (bad) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, bad);
+	}
+	if ((st = need_ready(b, fn))) return st;
+	double* key = nullptr;
+	const size_t bytes = (size_t)n_keyframes * frame_bytes;
+	HIP_TRY(hipMalloc((void**)&key, bytes));
+	hipError_t e;
+	if (per_instance) {
+		e = hipMemsetAsync(key, 0, bytes, b->stream);
+		if (e == hipSuccess)
+			e = hipMemcpy2DAsync(key, (size_t)b->ld * sizeof(double), keyframes, (size_t)b->B * sizeof(double), (size_t)b->B * sizeof(double),
+								 (size_t)n_keyframes * count, hipMemcpyHostToDevice, b->stream);
+	} else {
+		e = hipMemcpyAsync(key, keyframes, bytes, hipMemcpyHostToDevice, b->stream);
+	}
+	if (e == hipSuccess) e = hipStreamSynchronize(b->stream);  // the host buffer may be reused by the caller right away
+	if (e != hipSuccess) {
+		(void)hipFree(key);
+		return fail(SAIP_ERR_DEVICE, "%s: keyframe upload failed: %s", fn, hipGetErrorString(e));
+	}
+	if (b->sched.size() < b->tasks.size()) b->sched.resize(b->tasks.size());
+	auto& S = b->sched[task];
+	S.attached = true;
+	S.first = first;
+	S.count = count;
+	S.K = n_keyframes;
+	S.stride = stride;
+	S.mode = mode;
+	S.per_instance = per_instance;
+	S.rot = rot;
+	S.key = key;
+	b->n_sched++;
+	b->sched_period = 0;
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_goal_schedule_detach(saip_batch* b, int task) {
+	const char* fn = "saip_batch_goal_schedule_detach";
+	saip_status st = task == -1 ? need_controller(b, fn) : need_schedule(b, task, fn);
+	if (st) return st;
+	if (task == -1 && b->n_sched == 0) return SAIP_OK;
+	if ((st = need_ready(b, fn))) return st;
+	HIP_TRY(hipStreamSynchronize(b->stream));  // a scheduled period may still be in flight
+	for (int t = 0; t < (int)b->sched.size(); t++) {
+		auto& S = b->sched[t];
+		if (!S.attached || (task != -1 && t != task)) continue;
+		(void)hipFree(S.key);
+		S = saip_batch::Schedule();
+		b->n_sched--;
+	}
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_goal_schedule_rewind(saip_batch* b) {
+	saip_status st = need_controller(b, "saip_batch_goal_schedule_rewind");
+	if (st) return st;
+	b->sched_period = 0;
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_goal_schedule_info(saip_batch* b, int task, int* first, int* count, int* n_keyframes, int* stride, int* mode,
+													 long long* period) {
+	saip_status st = need_schedule(b, task, "saip_batch_goal_schedule_info");
+	if (st) return st;
+	const auto& S = b->sched[task];
+	if (first) *first = S.first;
+	if (count) *count = S.count;
+	if (n_keyframes) *n_keyframes = S.K;
+	if (stride) *stride = S.stride;
+	if (mode) *mode = S.mode;
+	if (period) *period = b->sched_period;
+	return SAIP_OK;
+}
+extern "C" double* saip_batch_goal_schedule_device(saip_batch* b, int task) {
+	return (b && task >= 0 && task < (int)b->sched.size()) ? b->sched[task].key : nullptr;
+}
+// the goals of rollout period c = sched_period, written in front of the period's OTG step and cycle: one launch for every schedule; the
+// keyframe index and the fraction are computed here, at enqueue time (no device-side counter)
+static saip_status apply_schedules(saip_batch* b) {
+	saip::ScheduleParams P;
+	memset(&P, 0, sizeof(P));
+	P.B = b->B;
+	P.ld = b->ld;
+	const long long c = b->sched_period++;
+	for (int t = 0; t < (int)b->sched.size(); t++) {
+		const auto& S = b->sched[t];
+		if (!S.attached) continue;
+		auto& E = P.e[P.n++];
+		E.goal = b->tasks[t].goal_dev;
+		E.key = S.key;
+		E.first = S.first;
+		E.count = S.count;
+		E.K = S.K;
+		const bool past = c >= (long long)(S.K - 1) * S.stride;  // the last keyframe is held
+		E.i = past ? S.K - 1 : (int)(c / S.stride);
+		E.s = past ? 0.0 : (double)(c % S.stride) / (double)S.stride;
+		E.mode = S.mode;
+		E.per_instance = S.per_instance;
+		E.rot = S.rot;
+	}
+	hipError_t e = saip::launch_goal_schedule(P, b->stream);
+	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "goal schedule launch failed: %s", hipGetErrorString(e));
+	return SAIP_OK;
+}
+
 // steps x { internal OTGs, control cycle, integrate } on the engine stream, no host synchronisation.  One period is 3-5 small
 // launches.  Plain back-to-back stream launches are the default: they were measured FASTER than replaying a hipGraph of the period
 // (68.6 vs 74.2 us per period at B = 4096, 65.7 vs 70.4 us at B = 256, tools/rollout_bench.py) -- the host enqueues far ahead of the
@@ -2241,7 +2423,11 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 	for (auto& T : b->tasks) any_otg = any_otg || T.otg_enabled;
 	SimRequest sim = {substeps, sim_dt, damping, {0, 0, 0}};
 	for (int i = 0; i < 3; i++) sim.gravity[i] = gravity ? gravity[i] : b->model->dev.gravity[i];
+	// with a goal schedule attached every period starts with the launch that writes its goals, and the integration is never fused with
+	// the next period's OTG step (which would read the next goal before it is written)
+	const bool scheduled = b->n_sched > 0;
 	auto period = [&](const bool more = false) -> saip_status {  // more: another period follows inside this call
+		if (scheduled && (st = apply_schedules(b))) return st;
 		// no internal OTG in the stack: the cycle launch integrates the state itself when it can (eight-lane kernel, no slow path behind)
 		bool integrated = false;
 		saip_status s2 = launch_cycle(b, false, (!any_otg && b->model->n == 7) ? &sim : nullptr, &integrated);
@@ -2252,7 +2438,7 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 		if (integrated) {  // the bookkeeping of enqueue_integrate
 			b->models_valid = false;
 			b->state_epoch++;
-		} else if ((s2 = enqueue_integrate(b, sim_dt, substeps, gravity, damping, more))) {
+		} else if ((s2 = enqueue_integrate(b, sim_dt, substeps, gravity, damping, more && !scheduled))) {
 			b->otg_prelaunched = false;
 			return s2;
 		}

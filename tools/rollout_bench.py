@@ -3,7 +3,10 @@
    SAIP_LIB=<path> selects the build (same-session A/B).
    --record-stride N / --record-channels q,dq,tau,pose,error / --record-summaries attach a rollout recorder (any of them does: stride 1,
    channels q,dq,tau, no summaries unless given; --record-channels none = summaries only) and the line gains what was recorded.
-   --no-otg runs the stack without internal OTGs (the cycle launch integrates in-kernel); --repeats R times the closed-loop period R times."""
+   --no-otg runs the stack without internal OTGs (the cycle launch integrates in-kernel); --repeats R times the closed-loop period R times.
+   --goal-schedule hold|linear times, in the same setting and run, the period without a schedule, the period cut into one rollout call per
+   period (no fused integrate + next-OTG launch, nothing else changed) and the period with a per-instance schedule on the position and
+   orientation rows of the motion-force task (8 keyframes, stride 50; linear interpolates the orientation on SO(3))."""
 import argparse
 import os
 import sys
@@ -20,6 +23,7 @@ ap.add_argument("--record-channels", default=None)
 ap.add_argument("--record-summaries", action="store_true")
 ap.add_argument("--no-otg", action="store_true")
 ap.add_argument("--repeats", type=int, default=1)
+ap.add_argument("--goal-schedule", choices=("hold", "linear"), default=None)
 args = ap.parse_args()
 record = args.record_stride is not None or args.record_channels is not None or args.record_summaries
 
@@ -42,6 +46,36 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
         what = f"; recorder: stride {stride}, channels {','.join(channels) or 'none'}, summaries {'on' if args.record_summaries else 'off'}"
     ctrl.rolloutAsync(50, 5e-4, 2, gravity=(0, 0, 0))
     ctrl.synchronize()
+    if args.goal_schedule:
+        def timed(calls, steps):
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                ctrl.rolloutAsync(steps, 5e-4, 2, gravity=(0, 0, 0))
+            ctrl.synchronize()
+            return (time.perf_counter() - t0) / (calls * steps) * 1e6
+
+        rng = np.random.default_rng(0)
+        goal = mf._get_goal()[:, :12]
+        keys = np.repeat(goal[None], 8, axis=0)
+        keys[:, :, :3] += rng.uniform(-0.03, 0.03, (8, B, 3))
+        for k in range(8):      # small rotations about the vertical in front of the goal orientation
+            a = rng.uniform(-0.2, 0.2, B)
+            Rz = np.zeros((B, 3, 3))
+            Rz[:, 0, 0], Rz[:, 0, 1], Rz[:, 1, 0], Rz[:, 1, 1], Rz[:, 2, 2] = np.cos(a), -np.sin(a), np.sin(a), np.cos(a), 1.0
+            keys[k, :, 3:] = (Rz @ goal[:, 3:].reshape(B, 3, 3)).reshape(B, 9)
+        for _ in range(args.repeats):
+            plain = timed(1, K)
+            unfused = timed(K, 1)
+            mf.setGoalSchedule((0, 12), keys, stride=50, mode=args.goal_schedule)
+            timed(1, 50)
+            ctrl.rewindGoalSchedules()
+            scheduled = timed(1, K)
+            mf.clearGoalSchedule()
+            mf.setGoalPosition(goal[:, :3])
+            mf.setGoalOrientation(goal[:, 3:].reshape(B, 3, 3))
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'}: closed-loop period {plain:.1f} us; "
+                  f"one rollout call per period {unfused:.1f} us; with a {args.goal_schedule} goal schedule {scheduled:.1f} us")
+        continue
     for _ in range(args.repeats):
         if record:
             ctrl.resetRolloutRecorder()
