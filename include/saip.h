@@ -34,6 +34,7 @@
 #ifndef SAIP_H_
 #define SAIP_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -246,6 +247,52 @@ saip_status saip_batch_goal_schedule_rewind(saip_batch*);
 /* any pointer may be NULL; period: the counter c */
 saip_status saip_batch_goal_schedule_info(saip_batch*, int task, int* first, int* count, int* n_keyframes, int* stride, int* mode, long long* period);
 double* saip_batch_goal_schedule_device(saip_batch*, int task);  /* NULL when the task has no schedule */
+/* ---- state snapshots: the complete per-instance state of a batch -- robot state, held torques, status, and per task the goal rows,
+ * the PID integrators, the internal OTG (profiles, scalars, frames, desired rows), the singularity handler's windows and the passivity
+ * observer's ring -- captured on the device and written back through a per-instance source index: instance i takes the state that
+ * instance src[i] had at the save.  NULL / the identity restores, src[i] = j broadcasts instance j, anything else resamples or permutes.
+ * What a sampling MPC does between two rollouts:
+ *     saip_batch_snapshot_save(b, s);                                  (the measured state, once)
+ *     { saip_batch_snapshot_restore(b, s, broadcast_of_0); saip_batch_rollout_async(b, K, ...); read the summaries }
+ *     saip_batch_snapshot_restore(b, s, best);
+ * The recorder and its period counter, the goal schedules and their period counter are NOT part of a snapshot: pair a restore with
+ * saip_batch_rollout_recorder_reset / saip_batch_goal_schedule_rewind.  Configuration (gains, limits, flags) is not part of it either:
+ * limits changed after a save still start a new trajectory on the next cycle.  The goal rows are part of it.
+ *   _create   allocates a copy of every state array the batch has at that moment (arrays of enabled features that the first cycle would
+ *             allocate are allocated here) and fixes the layout: a list of segments { name, rows, elem_bytes, group, kind, offset }.
+ *             kind SAIP_SNAPSHOT_SOA: rows x [ld] elements; _GROUPED: rows x [B * group] doubles, instance i owns elements i*group ..
+ *             i*group + group - 1 of every row; _AOS: [ld] records of elem_bytes.  offset: of the segment inside the host blob.
+ *   _save, _restore, _restore_device   one kernel launch on the engine stream behind whatever is enqueued; they do not wait for the
+ *             device.  _restore checks the host map first (every entry in 0 .. B-1, else SAIP_ERR_INVALID_ARGUMENT and nothing
+ *             happens) and uploads it from a staging buffer the snapshot owns.  _restore_device reads the map [B] (int) from device
+ *             memory in stream order; an entry outside 0 .. B-1 leaves that instance untouched.  Only columns 0 .. B-1 are written.
+ *             A restored state is a new state (like saip_batch_set_state_host): the task models are due.
+ *   refusals  a snapshot works with the batch that created it only (SAIP_ERR_INVALID_ARGUMENT otherwise).  SAIP_ERR_ORDER: the state
+ *             layout of the batch no longer matches (an internal OTG enabled for the first time, passivity or singularity state
+ *             allocated, torques bound to another buffer after _create -- the message names the first segment that differs; create a
+ *             new snapshot), a restore of a snapshot nothing was saved into, a batch before saip_batch_finalize or finalized for
+ *             model queries only.  A configuration-only batch: SAIP_ERR_NO_DEVICE, after the argument errors.  A failed call writes
+ *             nothing to its outputs.
+ *   host blob _export_host / _import_host copy a snapshot to / from host memory (they wait for the stream): saip_snapshot_bytes bytes =
+ *             a 256-byte header { char magic[8] = "SAIPSNAP"; uint32 version, n_segments; uint64 fingerprint, bytes; int32
+ *             otg_prelaunched, n_tasks; { int32 sh_cycle, otg_inited } [8]; zero padding } and the segments at their offsets.  The
+ *             fingerprint hashes dof, B, ld and every segment's name, rows, elem_bytes and group.  _import_host refuses a short
+ *             buffer, a bad magic, another version and another fingerprint with SAIP_ERR_INVALID_ARGUMENT before it touches the
+ *             device (with a NULL snapshot the blob is checked against the layout of the batch, then refused).  The format is not
+ *             stable across versions of the library; the header is what detects that. */
+typedef struct saip_snapshot saip_snapshot;
+enum { SAIP_SNAPSHOT_SOA = 0, SAIP_SNAPSHOT_GROUPED = 1, SAIP_SNAPSHOT_AOS = 2 };
+saip_status saip_batch_snapshot_create(saip_batch*, saip_snapshot** out);
+void saip_snapshot_destroy(saip_snapshot*);  /* waits for the batch's stream; also valid after saip_batch_destroy of its batch */
+saip_status saip_batch_snapshot_save(saip_batch*, saip_snapshot*);
+saip_status saip_batch_snapshot_restore(saip_batch*, const saip_snapshot*, const int* src_host /* [B], NULL = identity */);
+saip_status saip_batch_snapshot_restore_device(saip_batch*, const saip_snapshot*, const int* src_dev /* [B] */);
+int saip_snapshot_segments(const saip_snapshot*);
+/* any output pointer may be NULL; name stays valid as long as the snapshot */
+saip_status saip_snapshot_segment_info(const saip_snapshot*, int i, const char** name, int* rows, int* elem_bytes, int* group, int* kind, size_t* offset);
+size_t saip_snapshot_bytes(const saip_snapshot*);
+saip_status saip_snapshot_export_host(saip_batch*, const saip_snapshot*, void* out, size_t bytes);
+saip_status saip_snapshot_import_host(saip_batch*, saip_snapshot*, const void* in, size_t bytes);
 /* ---- rollout recorder: a per-period trajectory log and running summaries of saip_batch_rollout_async, kept on the device (the
  * reference's example loops print or log the same quantities every period: state, torques, position / orientation error).  A recorder
  * is attached to a finalized batch and stays attached across rollout calls until detached.  It observes rollout periods only

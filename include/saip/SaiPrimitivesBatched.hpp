@@ -866,6 +866,90 @@ public:
 	// the period counter of the tasks' goal schedules (TemplateTask::setGoalSchedule) back to 0
 	void rewindGoalSchedules() { check(saip_batch_goal_schedule_rewind(_batch)); }
 
+	// ---- state snapshots: the complete per-instance state saved on the device and written back through a source index (saip.h).
+	// A sampling MPC: auto s = ctrl.saveState(); { ctrl.restoreState(s, 0); ctrl.rolloutAsync(K, ...); rolloutSummary(); } ctrl.restoreState(s, best);
+	// Pair a restore with resetRolloutRecorder() / rewindGoalSchedules(): neither is part of a snapshot.
+	class StateSnapshot {
+	public:
+		struct Segment {
+			std::string name;
+			int rows = 0, elem_bytes = 0, group = 1, kind = SAIP_SNAPSHOT_SOA;
+			size_t offset = 0;  // inside tobytes()
+		};
+		StateSnapshot() = default;
+		StateSnapshot(StateSnapshot&& o) noexcept : _s(o._s), _batch(o._batch) { o._s = nullptr; }
+		StateSnapshot& operator=(StateSnapshot&& o) noexcept {
+			if (this != &o) {
+				close();
+				_s = o._s;
+				_batch = o._batch;
+				o._s = nullptr;
+			}
+			return *this;
+		}
+		StateSnapshot(const StateSnapshot&) = delete;
+		StateSnapshot& operator=(const StateSnapshot&) = delete;
+		~StateSnapshot() { close(); }
+		void close() {
+			saip_snapshot_destroy(_s);
+			_s = nullptr;
+		}
+		bool valid() const { return _s != nullptr; }
+		saip_snapshot* handle() const { return _s; }
+		size_t bytes() const { return saip_snapshot_bytes(_s); }
+		std::vector<Segment> segments() const {
+			std::vector<Segment> out((size_t)saip_snapshot_segments(_s));
+			for (size_t i = 0; i < out.size(); i++) {
+				const char* name = nullptr;
+				check(saip_snapshot_segment_info(_s, (int)i, &name, &out[i].rows, &out[i].elem_bytes, &out[i].group, &out[i].kind, &out[i].offset));
+				out[i].name = name;
+			}
+			return out;
+		}
+		// the snapshot as a host blob (waits for the engine stream); not a stable format across versions of the library
+		std::vector<unsigned char> tobytes() const {
+			std::vector<unsigned char> blob(bytes());
+			check(saip_snapshot_export_host(_batch, _s, blob.data(), blob.size()));
+			return blob;
+		}
+
+	private:
+		friend class RobotController;
+		saip_snapshot* _s = nullptr;
+		saip_batch* _batch = nullptr;
+	};
+	StateSnapshot createStateSnapshot() {
+		StateSnapshot s;
+		check(saip_batch_snapshot_create(_batch, &s._s));
+		s._batch = _batch;
+		return s;
+	}
+	// capture the complete resident state into `snapshot` (asynchronous), or into a new one
+	void saveState(StateSnapshot& snapshot) {
+		pushState();
+		check(saip_batch_snapshot_save(_batch, snapshot._s));
+	}
+	StateSnapshot saveState() {
+		StateSnapshot s = createStateSnapshot();
+		saveState(s);
+		return s;
+	}
+	// instance i takes the state instance source[i] had at the save: every instance its own / all that of `instance` / a host map of B
+	// indices (checked) / a device map of B ints read in stream order (an entry outside 0 .. B-1 leaves that instance as it is)
+	void restoreState(const StateSnapshot& snapshot) { restored(saip_batch_snapshot_restore(_batch, snapshot._s, nullptr)); }
+	void restoreState(const StateSnapshot& snapshot, int instance) { restoreState(snapshot, std::vector<int>((size_t)_robot->batchSize(), instance)); }
+	void restoreState(const StateSnapshot& snapshot, const std::vector<int>& source) {
+		if ((int)source.size() != _robot->batchSize()) throw std::invalid_argument("restoreState: one source index per instance expected");
+		restored(saip_batch_snapshot_restore(_batch, snapshot._s, source.data()));
+	}
+	void restoreStateDevice(const StateSnapshot& snapshot, const int* source_dev) { restored(saip_batch_snapshot_restore_device(_batch, snapshot._s, source_dev)); }
+	// a new snapshot of this controller filled from a blob of tobytes(); the controller must have the layout the blob was taken from
+	StateSnapshot stateSnapshotFromBytes(const std::vector<unsigned char>& blob) {
+		StateSnapshot s = createStateSnapshot();
+		check(saip_snapshot_import_host(_batch, s._s, blob.data(), blob.size()));
+		return s;
+	}
+
 	// ---- rollout recorder: per-period trajectory log and running summaries of rolloutAsync, kept on the device (saip.h)
 	struct RolloutLog {
 		int samples = 0, rows = 0, first_period = 0, stride = 1;
@@ -897,6 +981,11 @@ public:
 	}
 
 private:
+	void restored(saip_status st) {
+		check(st);
+		for (auto& a : _robot->_attached)
+			if (a.batch == _batch) a.pushed = _robot->_version;  // the device holds the restored state, not the SaiModel mirror (pullState reads it back)
+	}
 	template <typename T>
 	std::shared_ptr<T> byName(const std::string& name, TaskType type, const char* what) {
 		for (auto& t : _tasks)

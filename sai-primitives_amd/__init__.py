@@ -8,5 +8,5 @@ there is no CPU path: without the built library or without a GPU every compute c
 """
 from .capi import (lib, build_library, SaipError, SaipUnsupported, SaipNoDevice, device_count,  # noqa: F401
                    SAIP_MAX_QUERY_FRAMES, SAIP_QUERY_JACOBIAN, SAIP_QUERY_WORLD)
-from .controller import (SaiModel, MotionForceTask, JointTask, RobotController, TaskType,  # noqa: F401
+from .controller import (SaiModel, MotionForceTask, JointTask, RobotController, StateSnapshot, TaskType,  # noqa: F401
                          DynamicDecouplingType, PIDGains, load_robot_description)

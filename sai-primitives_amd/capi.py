@@ -7,8 +7,8 @@ import subprocess
 
 _DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_DIR, "libsaip.so")
-SOURCES = ["csrc/saip_engine.cpp", "csrc/saip_comm.cpp", "csrc/saip_kernel_wg.hip", "csrc/saip_kernel_lane.hip", "csrc/saip_kernel_lane_lean.hip", "csrc/saip_kernel_oct.hip", "csrc/saip_kernel_octjf.hip", "csrc/saip_kernel_wave.hip", "csrc/saip_otg.hip", "csrc/saip_dynamics.hip", "csrc/saip_dynamics_oct.hip", "csrc/saip_task_diag.hip", "csrc/saip_model_query.hip", "csrc/saip_rollout_record.hip", "csrc/saip_goal_schedule.hip"]
-HEADERS = ["csrc/saip_device.h", "csrc/saip_cycle_plan.h", "csrc/saip_law.h", "csrc/saip_wg_linalg.h", "csrc/saip_wg_cycle.h", "csrc/saip_fk.h", "csrc/saip_oct_common.h", "csrc/saip_wave_prims.h", "csrc/saip_dynamics_oct_body.h", "csrc/saip_otg3.h", "csrc/saip_otg3_step1.h", "csrc/saip_otg3_step2.h", "csrc/saip_rbd.h", "../include/saip.h"]
+SOURCES = ["csrc/saip_engine.cpp", "csrc/saip_comm.cpp", "csrc/saip_kernel_wg.hip", "csrc/saip_kernel_lane.hip", "csrc/saip_kernel_lane_lean.hip", "csrc/saip_kernel_oct.hip", "csrc/saip_kernel_octjf.hip", "csrc/saip_kernel_wave.hip", "csrc/saip_otg.hip", "csrc/saip_dynamics.hip", "csrc/saip_dynamics_oct.hip", "csrc/saip_task_diag.hip", "csrc/saip_model_query.hip", "csrc/saip_rollout_record.hip", "csrc/saip_goal_schedule.hip", "csrc/saip_state_snapshot.hip"]
+HEADERS = ["csrc/saip_device.h", "csrc/saip_cycle_plan.h", "csrc/saip_state_snapshot.h", "csrc/saip_law.h", "csrc/saip_wg_linalg.h", "csrc/saip_wg_cycle.h", "csrc/saip_fk.h", "csrc/saip_oct_common.h", "csrc/saip_wave_prims.h", "csrc/saip_dynamics_oct_body.h", "csrc/saip_otg3.h", "csrc/saip_otg3_step1.h", "csrc/saip_otg3_step2.h", "csrc/saip_rbd.h", "../include/saip.h"]
 
 SAIP_OK, SAIP_ERR_INVALID_ARGUMENT, SAIP_ERR_UNSUPPORTED, SAIP_ERR_NO_DEVICE, SAIP_ERR_DEVICE, SAIP_ERR_ORDER = range(6)
 SAIP_MAX_QUERY_FRAMES = 8
@@ -16,6 +16,7 @@ SAIP_QUERY_JACOBIAN, SAIP_QUERY_WORLD = 1, 2
 SAIP_RECORD_Q, SAIP_RECORD_DQ, SAIP_RECORD_TAU, SAIP_RECORD_POSE, SAIP_RECORD_ERROR = 1, 2, 4, 8, 16
 SAIP_RECORD_SUMMARY_ROWS = 8
 SAIP_SCHEDULE_HOLD, SAIP_SCHEDULE_LINEAR = 0, 1
+SAIP_SNAPSHOT_SOA, SAIP_SNAPSHOT_GROUPED, SAIP_SNAPSHOT_AOS = 0, 1, 2
 NAME_LEN = 48
 
 
@@ -170,6 +171,16 @@ def lib():
         "saip_batch_goal_schedule_rewind": (C.c_int, [vp]),
         "saip_batch_goal_schedule_info": (C.c_int, [vp, C.c_int, ip, ip, ip, ip, ip, C.POINTER(C.c_longlong)]),
         "saip_batch_goal_schedule_device": (vp, [vp, C.c_int]),
+        "saip_batch_snapshot_create": (C.c_int, [vp, C.POINTER(vp)]),
+        "saip_snapshot_destroy": (None, [vp]),
+        "saip_batch_snapshot_save": (C.c_int, [vp, vp]),
+        "saip_batch_snapshot_restore": (C.c_int, [vp, vp, ip]),
+        "saip_batch_snapshot_restore_device": (C.c_int, [vp, vp, vp]),
+        "saip_snapshot_segments": (C.c_int, [vp]),
+        "saip_snapshot_segment_info": (C.c_int, [vp, C.c_int, C.POINTER(C.c_char_p), ip, ip, ip, ip, C.POINTER(C.c_size_t)]),
+        "saip_snapshot_bytes": (C.c_size_t, [vp]),
+        "saip_snapshot_export_host": (C.c_int, [vp, vp, vp, C.c_size_t]),
+        "saip_snapshot_import_host": (C.c_int, [vp, vp, vp, C.c_size_t]),
         "saip_batch_get_state_host": (C.c_int, [vp, dp, dp]),
         "saip_batch_set_torques_host": (C.c_int, [vp, dp]),
         "saip_batch_get_otg_status_host": (C.c_int, [vp, C.c_int, ip, ip]),

@@ -1406,6 +1406,47 @@ class RobotController:
         """the period counter of the tasks' goal schedules (task.setGoalSchedule) back to 0: the next rollout starts at the first keyframe"""
         self._call("saip_batch_goal_schedule_rewind")
 
+    # -- state snapshots: the complete per-instance state, saved on the device and written back through a source index (saip.h)
+    def saveState(self, snapshot=None):
+        """capture the complete resident state of every instance (robot state, torques, goals, integrators, internal OTGs, singularity
+        and passivity state) into `snapshot`, or into a new StateSnapshot; asynchronous on the engine stream.  Returns the snapshot."""
+        self._push_state()
+        if snapshot is None:
+            snapshot = StateSnapshot(self)
+        elif snapshot._ctrl is not self:
+            raise ValueError("saveState: the snapshot belongs to another controller")
+        self._call("saip_batch_snapshot_save", snapshot._handle())
+        return snapshot
+
+    def restoreState(self, snapshot, source=None):
+        """instance i takes the state instance source[i] had when `snapshot` was saved.  source: None (every instance its own), an int
+        (that instance's state into all), a sequence / NumPy int array of B indices (checked on the host), or a torch int32 device
+        tensor of B indices read in stream order (an entry outside 0 .. B-1 leaves that instance as it is).  Asynchronous.  The rollout
+        recorder and the goal schedules are not part of a snapshot: pair with resetRolloutRecorder() / rewindGoalSchedules()."""
+        if not isinstance(snapshot, StateSnapshot) or snapshot._ctrl is not self:
+            raise ValueError("restoreState: the snapshot belongs to another controller")
+        B, h = self.batch_size, snapshot._handle()
+        if source is None:
+            self._call("saip_batch_snapshot_restore", h, None)
+        elif hasattr(source, "data_ptr") and getattr(source, "is_cuda", False):
+            import torch
+            if source.dtype != torch.int32 or source.numel() != B or not source.is_contiguous():
+                raise ValueError(f"restoreState: a contiguous int32 device tensor of {B} indices expected")
+            self._call("saip_batch_snapshot_restore_device", h, C.c_void_p(source.data_ptr()))
+        else:
+            src = np.asarray(source.cpu() if hasattr(source, "cpu") else source)
+            if src.dtype.kind not in "iu":
+                raise ValueError("restoreState: integer source indices expected")
+            if src.ndim == 0:
+                src = np.full(B, int(src))
+            if src.shape != (B,):
+                raise ValueError(f"restoreState: {B} source indices expected, got shape {src.shape}")
+            if ((src < 0) | (src >= B)).any():
+                raise ValueError(f"restoreState: source indices must lie in 0 .. {B - 1}")
+            src = np.ascontiguousarray(src, dtype=np.int32)
+            self._call("saip_batch_snapshot_restore", h, src.ctypes.data_as(C.POINTER(C.c_int)))
+        self._pushed_version = self._robot._state_version  # the device holds the restored state, not the SaiModel mirror (pullState reads it back)
+
     # -- rollout recorder: per-period trajectory log and running summaries of rolloutAsync, kept on the device (saip.h)
     _REC_CHANNELS = {"q": capi.SAIP_RECORD_Q, "dq": capi.SAIP_RECORD_DQ, "tau": capi.SAIP_RECORD_TAU, "pose": capi.SAIP_RECORD_POSE,
                      "error": capi.SAIP_RECORD_ERROR}
@@ -1542,6 +1583,62 @@ class RobotController:
 
     def bindTauDevice(self, ptr):
         self._call("saip_batch_bind_tau_device", C.c_void_p(ptr))
+
+
+class StateSnapshot:
+    """A device-resident copy of the complete state of a RobotController's instances (RobotController.saveState / restoreState)."""
+    KINDS = {capi.SAIP_SNAPSHOT_SOA: "soa", capi.SAIP_SNAPSHOT_GROUPED: "grouped", capi.SAIP_SNAPSHOT_AOS: "aos"}
+
+    def __init__(self, controller):
+        h = C.c_void_p()
+        controller._call("saip_batch_snapshot_create", C.byref(h))
+        self._h, self._ctrl = h, controller
+
+    def _handle(self):
+        if not self._h:
+            raise capi.SaipError("the StateSnapshot has been closed")
+        return self._h
+
+    def segments(self):
+        """the layout: a list of dicts name, rows, elem_bytes, group, kind ("soa" rows x [ld], "grouped" rows x [B * group], "aos" [ld]
+        records), offset (of the segment inside tobytes())"""
+        L, out = capi.lib(), []
+        for i in range(L.saip_snapshot_segments(self._handle())):
+            name, rows, eb, grp, kind, off = C.c_char_p(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+            capi.check(L.saip_snapshot_segment_info(self._h, i, C.byref(name), C.byref(rows), C.byref(eb), C.byref(grp), C.byref(kind), C.byref(off)))
+            out.append(dict(name=name.value.decode(), rows=rows.value, elem_bytes=eb.value, group=grp.value, kind=self.KINDS[kind.value], offset=off.value))
+        return out
+
+    def nbytes(self):
+        return capi.lib().saip_snapshot_bytes(self._handle())
+
+    def tobytes(self):
+        """the snapshot as a host blob (waits for the engine stream): header with magic, format version and layout fingerprint, then
+        the segments.  Not a stable format across versions of the library."""
+        buf = np.empty(self.nbytes(), np.uint8)
+        self._ctrl._call("saip_snapshot_export_host", self._handle(), buf.ctypes.data_as(C.c_void_p), buf.size)
+        return buf.tobytes()
+
+    @classmethod
+    def frombytes(cls, controller, data):
+        """a new snapshot of `controller` filled from a blob of tobytes(); the controller must have the layout the blob was taken from
+        (same robot, batch size and task stack with the same features enabled), else ValueError"""
+        snap = cls(controller)
+        buf = np.frombuffer(bytes(data), np.uint8)
+        try:
+            controller._call("saip_snapshot_import_host", snap._h, buf.ctypes.data_as(C.c_void_p), buf.size)
+        except Exception:
+            snap.close()
+            raise
+        return snap
+
+    def close(self):
+        if getattr(self, "_h", None):
+            capi.lib().saip_snapshot_destroy(self._h)  # (valid after the batch is gone too: the batch frees the device memory then)
+            self._h = None
+
+    def __del__(self):
+        self.close()
 
 
 def controller_from_specs(description, tasks, batch_size, device=0, *, disable_otg=True, leading_dimension=None):

@@ -6,7 +6,10 @@
    --no-otg runs the stack without internal OTGs (the cycle launch integrates in-kernel); --repeats R times the closed-loop period R times.
    --goal-schedule hold|linear times, in the same setting and run, the period without a schedule, the period cut into one rollout call per
    period (no fused integrate + next-OTG launch, nothing else changed) and the period with a per-instance schedule on the position and
-   orientation rows of the motion-force task (8 keyframes, stride 50; linear interpolates the orientation on SO(3))."""
+   orientation rows of the motion-force task (8 keyframes, stride 50; linear interpolates the orientation on SO(3)).
+   --snapshot prints the bytes of a state snapshot of the stack and, event-timed on the engine stream (mean of 50 back-to-back calls), a
+   save, an identity restore, a random-permutation restore, a broadcast restore and plain hipMemcpyAsync device-to-device copies of
+   segments of the same sizes (the yardstick of DESIGN.md 4.10)."""
 import argparse
 import os
 import sys
@@ -24,6 +27,7 @@ ap.add_argument("--record-summaries", action="store_true")
 ap.add_argument("--no-otg", action="store_true")
 ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--goal-schedule", choices=("hold", "linear"), default=None)
+ap.add_argument("--snapshot", action="store_true")
 args = ap.parse_args()
 record = args.record_stride is not None or args.record_channels is not None or args.record_summaries
 
@@ -46,6 +50,54 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
         what = f"; recorder: stride {stride}, channels {','.join(channels) or 'none'}, summaries {'on' if args.record_summaries else 'off'}"
     ctrl.rolloutAsync(50, 5e-4, 2, gravity=(0, 0, 0))
     ctrl.synchronize()
+    if args.snapshot:
+        import ctypes as C
+        hip = C.CDLL("libamdhip64.so")
+        vp = C.c_void_p
+        hip.hipMalloc.argtypes, hip.hipFree.argtypes = [C.POINTER(vp), C.c_size_t], [vp]
+        hip.hipEventCreate.argtypes, hip.hipEventRecord.argtypes, hip.hipEventSynchronize.argtypes = [C.POINTER(vp)], [vp, vp], [vp]
+        hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), vp, vp]
+        hip.hipMemcpyAsync.argtypes = [vp, vp, C.c_size_t, C.c_int, vp]
+        stream = ctrl.devicePointers()["stream"]
+        ev = [vp(), vp()]
+        for e in ev:
+            assert hip.hipEventCreate(C.byref(e)) == 0
+        snap = ctrl.saveState()
+        segs = snap.segments()
+        ends = [s["offset"] for s in segs[1:]] + [snap.nbytes()]
+        sizes = [e - s["offset"] for s, e in zip(segs, ends)]          # the segments' arrays, padding columns included
+        bufs = [vp(), vp()]
+        for p in bufs:
+            assert hip.hipMalloc(C.byref(p), snap.nbytes()) == 0
+        rng = np.random.default_rng(0)
+        perm, bcast = rng.permutation(B).astype(np.int32), np.full(B, B // 2, np.int32)
+
+        def copies():
+            for s, n in zip(segs, sizes):
+                assert hip.hipMemcpyAsync(bufs[0].value + s["offset"], bufs[1].value + s["offset"], n, 3, stream) == 0   # device to device
+
+        def timed_us(fn, reps=50):
+            fn()
+            ctrl.synchronize()
+            assert hip.hipEventRecord(ev[0], stream) == 0
+            for _ in range(reps):
+                fn()
+            assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
+            ms = C.c_float()
+            assert hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
+            return ms.value / reps * 1e3
+
+        for _ in range(args.repeats):
+            t = dict(save=timed_us(lambda: ctrl.saveState(snap)), identity=timed_us(lambda: ctrl.restoreState(snap)),
+                     permutation=timed_us(lambda: ctrl.restoreState(snap, perm)), broadcast=timed_us(lambda: ctrl.restoreState(snap, bcast)),
+                     copies=timed_us(copies))
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'}: snapshot {snap.nbytes()} bytes in "
+                  f"{len(segs)} segments; save {t['save']:.1f} us; identity restore {t['identity']:.1f} us; permutation restore {t['permutation']:.1f} us; "
+                  f"broadcast restore {t['broadcast']:.1f} us; hipMemcpyAsync D2D per segment {t['copies']:.1f} us")
+        for p in bufs:
+            hip.hipFree(p)
+        snap.close()
+        continue
     if args.goal_schedule:
         def timed(calls, steps):
             t0 = time.perf_counter()
