@@ -220,7 +220,8 @@ saip_status saip_batch_rollout_async(saip_batch*, int steps, double sim_dt, int 
  * a joint task).  At most one schedule per task; it stays attached across rollout calls until detached.
  *   keyframes: host [n_keyframes][n_components][B] with per_instance = 1, [n_keyframes][n_components] (the same for every instance)
  *        with per_instance = 0; copied to the device by _attach ([K][count][ld] or [K][count]), never inside a rollout.
- *        saip_batch_goal_schedule_device returns the resident copy, to be rewritten in place between rollouts (a sampler on the device).
+ *        saip_batch_goal_schedule_device returns the resident copy, to be rewritten in place between rollouts (a sampler on the device:
+ *        saip_batch_sampler_* below is one).
  *   timing: a period counter c, shared by every schedule of the batch, starts at 0 at _attach and _rewind and advances with every period
  *        of saip_batch_rollout_async.  Period c uses keyframe i = c / stride and the fraction s = (c % stride) / (double)stride; from
  *        c = (n_keyframes - 1) * stride on, the last keyframe is held.  i and s are computed at enqueue time and passed as launch arguments.
@@ -256,8 +257,9 @@ double* saip_batch_goal_schedule_device(saip_batch*, int task);  /* NULL when th
  *     { saip_batch_snapshot_restore(b, s, broadcast_of_0); saip_batch_rollout_async(b, K, ...); read the summaries }
  *     saip_batch_snapshot_restore(b, s, best);
  * The recorder and its period counter, the goal schedules and their period counter are NOT part of a snapshot: pair a restore with
- * saip_batch_rollout_recorder_reset / saip_batch_goal_schedule_rewind.  Configuration (gains, limits, flags) is not part of it either:
- * limits changed after a save still start a new trajectory on the next cycle.  The goal rows are part of it.
+ * saip_batch_rollout_recorder_reset / saip_batch_goal_schedule_rewind.  A sampler's nominal plan, round counter and costs are not part
+ * of it either.  Configuration (gains, limits, flags) is not part of it either: limits changed after a save still start a new
+ * trajectory on the next cycle.  The goal rows are part of it.
  *   _create   allocates a copy of every state array the batch has at that moment (arrays of enabled features that the first cycle would
  *             allocate are allocated here) and fixes the layout: a list of segments { name, rows, elem_bytes, group, kind, offset }.
  *             kind SAIP_SNAPSHOT_SOA: rows x [ld] elements; _GROUPED: rows x [B * group] doubles, instance i owns elements i*group ..
@@ -293,6 +295,58 @@ saip_status saip_snapshot_segment_info(const saip_snapshot*, int i, const char**
 size_t saip_snapshot_bytes(const saip_snapshot*);
 saip_status saip_snapshot_export_host(saip_batch*, const saip_snapshot*, void* out, size_t bytes);
 saip_status saip_snapshot_import_host(saip_batch*, saip_snapshot*, const void* in, size_t bytes);
+/* ---- resident rollout sampler: the three steps of a sampling-MPC round that complete the loop above on the device -- make the B
+ * candidates differ, turn the recorded rollout into one cost per candidate, fold the costs back into the plan (MPPI, model-predictive
+ * path-integral control; a tiny temperature takes the best).  A sampler belongs to ONE task's goal schedule, which must be per-instance
+ * (HOLD or LINEAR); it keeps a nominal plan [K][count] and rewrites the schedule's resident keyframes in place around it.
+ *   coordinates  the rows of the schedule's range in order; when the range covers rows 3..11 of a motion-force task (all nine or none:
+ *        a partial cover is refused) those nine rows are replaced by three tangent coordinates, axis-angle in radians in the keyframe's
+ *        own frame, applied as R Exp(.).  d = count - 6 with a rotation, d = count without; sigma is [d].
+ *   noise  Philox4x32-10 with counter (instance, keyframe, (task << 16) | p, round) and key (seed_lo, seed_hi); words 0, 1 and words 2, 3
+ *        make two uniforms u = (((hi >> 5) * 2^26 + (lo >> 6)) + 0.5) * 2^-53, Box-Muller makes the normals of coordinates 2p and 2p + 1
+ *        from them.  The noise of an instance depends on (seed, round, task, instance, keyframe, coordinate) only.
+ *   _perturb  every sampled task, one launch: key[k][c][i] = nominal[k][c] + sigma * z (product and sum rounded once each), rotations
+ *        R_nom Exp(sigma o z); instances 0 .. exempt - 1 get the nominal rows bit for bit.  Uses the round counter, then advances it.
+ *   _cost  one launch: cost_i = sum over r < 8 with w_summary[r] != 0 of w_summary[r] * summary[r][i], then + w_path * sum over the
+ *        samples of the recorder's ring (oldest first) of |p_i - target|^2, then + w_final * |p_i(last sample) - target|^2, p the position
+ *        rows of the POSE channel; every product and sum rounded once, left to right from 0, |e|^2 as ((e0 e0 + e1 e1) + e2 e2).  The
+ *        two target terms are present only with a target.  _set_cost_host / _get_cost_host / _cost_device: the cost array [ld] itself.
+ *   _update  two launches: beta = the minimum finite cost, best = the lowest index that attains it, w_i = exp(-(cost_i - beta) /
+ *        temperature) (0 for a cost that is not finite); per keyframe nominal[k][c] <- sum w_i key[k][c][i] / sum w_i, rotations
+ *        R_nom <- R_nom Exp(sum w_i Log(R_nom^T R_i) / sum w_i) (with all the weight on one instance in double precision: that instance's
+ *        rotation rows).  No atomics: lane l of 256 adds instances l, l + 256, ... in that order, then a fixed tree over the lanes, so
+ *        two runs give the same bits.  It writes the result { best, n_valid, min_cost, sum_w, ess = (sum w)^2 / sum w^2 } and the best map
+ *        [B] = best on the device; saip_batch_snapshot_restore_device takes the map as it is.  Without a finite cost the nominal stays,
+ *        best = -1 and the map holds -1 (such an entry leaves the instance as it is).
+ *   _shift  nominal[k] <- nominal[min(k + n, K - 1)]: the warm start of a receding horizon.
+ * Everything is enqueued on the engine stream; only the _host entries wait.  The cost array, the result and the best map belong to the
+ * batch: allocated by the first _attach, freed by the last _detach (task = -1 detaches all).  saip_batch_goal_schedule_detach of a
+ * sampled task detaches its sampler first.  The nominal plan, the round counter and the costs are NOT part of a state snapshot.
+ * A sampled range has at most 36 rows (the goal block of a motion-force task; a longer range of a joint task is refused).  With a LINEAR
+ * schedule over the rotation rows the nominal plan is checked like the schedule's keyframes, in _attach and in _set_nominal_host (every
+ * keyframe a rotation to 1e-6, consecutive keyframes at most pi - 1e-3 apart); a HOLD schedule's nominal is not checked, like its
+ * keyframes.  The perturbed keyframes are not checked: keeping sigma small enough that consecutive perturbed rotations stay inside
+ * pi - 1e-3 of each other is the caller's obligation.
+ * SAIP_ERR_INVALID_ARGUMENT: a temperature that is not finite or <= 0 and n < 0 (both before anything else is looked at), exempt
+ * outside 0 .. B, a negative or non-finite sigma, a batch-uniform schedule, a range over part of rows 3..11 or of more than 36 rows, a
+ * nominal plan that fails the check above.  SAIP_ERR_ORDER: a task without a schedule, a second _attach on a
+ * task, any other entry without a sampler, _cost with a non-zero summary weight but no recorder summaries, _cost with a target but no
+ * POSE channel or no sample yet.  Argument and order errors are reported before the device is needed; a failed call writes nothing. */
+saip_status saip_batch_sampler_attach(saip_batch*, int task, const double* sigma /* [d] */, const double* nominal /* [K][count], NULL = column 0 of the resident keyframes */, int exempt);
+saip_status saip_batch_sampler_detach(saip_batch*, int task /* -1: all */);
+saip_status saip_batch_sampler_seed(saip_batch*, unsigned long long seed);  /* also sets round = 0 */
+saip_status saip_batch_sampler_perturb(saip_batch*);                        /* every sampled task; round += 1 */
+saip_status saip_batch_sampler_cost(saip_batch*, const double w_summary[8] /* NULL = none */, const double target[3] /* NULL = none */, double w_path, double w_final);
+saip_status saip_batch_sampler_set_cost_host(saip_batch*, const double* cost /* [B] */);
+saip_status saip_batch_sampler_get_cost_host(saip_batch*, double* cost /* [B] */);  /* synchronous */
+double* saip_batch_sampler_cost_device(saip_batch*);                        /* [ld]; NULL without a sampler */
+saip_status saip_batch_sampler_update(saip_batch*, double temperature);     /* every sampled task */
+saip_status saip_batch_sampler_shift(saip_batch*, int n);
+saip_status saip_batch_sampler_result_host(saip_batch*, int* best, int* n_valid, double* min_cost, double* sum_w, double* ess);  /* synchronous; any NULL */
+const int* saip_batch_sampler_best_map_device(saip_batch*);                 /* [ld]; NULL without a sampler */
+saip_status saip_batch_sampler_get_nominal_host(saip_batch*, int task, double* out /* [K][count] */);
+saip_status saip_batch_sampler_set_nominal_host(saip_batch*, int task, const double* in);
+saip_status saip_batch_sampler_info(saip_batch*, int task, int* d, int* exempt, unsigned long long* seed, long long* round);
 /* ---- rollout recorder: a per-period trajectory log and running summaries of saip_batch_rollout_async, kept on the device (the
  * reference's example loops print or log the same quantities every period: state, torques, position / orientation error).  A recorder
  * is attached to a finalized batch and stays attached across rollout calls until detached.  It observes rollout periods only

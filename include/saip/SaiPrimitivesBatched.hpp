@@ -362,6 +362,40 @@ public:
 		need();
 		return saip_batch_goal_schedule_device(_batch, _id);
 	}
+	// ---- resident rollout sampler on this task's per-instance goal schedule (saip.h): sigma [d] over the scheduled rows in order, an
+	// orientation (rows 3..11 of a motion-force task) counting as three tangent coordinates; nominal [n_keyframes][count], empty =
+	// instance 0's keyframes; instances 0 .. exempt - 1 always run the nominal plan
+	void attachSampler(const std::vector<double>& sigma, const std::vector<double>& nominal = {}, int exempt = 1) {
+		need();
+		int first = 0, count = 0, nk = 0;
+		check(saip_batch_goal_schedule_info(_batch, _id, &first, &count, &nk, nullptr, nullptr, nullptr));
+		int f0 = 0, c0 = 0;
+		const bool rot = scheduleField("orientation", &f0, &c0) && first <= 3 && first + count >= 12;
+		if ((int)sigma.size() != (rot ? count - 6 : count)) throw std::invalid_argument("attachSampler: one sigma per sampler coordinate expected");
+		if (!nominal.empty() && nominal.size() != (size_t)nk * count) throw std::invalid_argument("attachSampler: expected a [n_keyframes][count] nominal plan");
+		check(saip_batch_sampler_attach(_batch, _id, sigma.data(), nominal.empty() ? nullptr : nominal.data(), exempt));
+	}
+	void detachSampler() {
+		need();
+		check(saip_batch_sampler_detach(_batch, _id));
+	}
+	std::vector<double> samplerNominal() {
+		need();
+		check(saip_batch_sampler_info(_batch, _id, nullptr, nullptr, nullptr, nullptr));
+		int count = 0, nk = 0;
+		check(saip_batch_goal_schedule_info(_batch, _id, nullptr, &count, &nk, nullptr, nullptr, nullptr));
+		std::vector<double> out((size_t)nk * count);
+		check(saip_batch_sampler_get_nominal_host(_batch, _id, out.data()));
+		return out;
+	}
+	void setSamplerNominal(const std::vector<double>& nominal) {
+		need();
+		check(saip_batch_sampler_info(_batch, _id, nullptr, nullptr, nullptr, nullptr));
+		int count = 0, nk = 0;
+		check(saip_batch_goal_schedule_info(_batch, _id, nullptr, &count, &nk, nullptr, nullptr, nullptr));
+		if (nominal.size() != (size_t)nk * count) throw std::invalid_argument("setSamplerNominal: expected a [n_keyframes][count] nominal plan");
+		check(saip_batch_sampler_set_nominal_host(_batch, _id, nominal.data()));
+	}
 	// (B x dof x dof as [dof*dof][B]) nullspace projector of this task for the current state, TemplateTask.h:71-77
 	std::vector<double> getTaskNullspace() {
 		need();
@@ -948,6 +982,46 @@ public:
 		StateSnapshot s = createStateSnapshot();
 		check(saip_snapshot_import_host(_batch, s._s, blob.data(), blob.size()));
 		return s;
+	}
+
+	// ---- resident rollout sampler (task->attachSampler; saip.h): the device steps of a sampling-MPC round
+	//   auto s = ctrl.saveState();
+	//   per round: ctrl.restoreState(s, 0); rewindGoalSchedules(); resetRolloutRecorder(); perturbGoalSchedules(); rolloutAsync(K, dt);
+	//              rolloutCost(...); updateSampler(temperature);
+	//   ctrl.restoreStateBest(s);
+	struct SamplerResult {
+		int best = -1, n_valid = 0;
+		double min_cost = 0, sum_w = 0, ess = 0;
+	};
+	void seedSampler(unsigned long long seed) { check(saip_batch_sampler_seed(_batch, seed)); }
+	void perturbGoalSchedules() { check(saip_batch_sampler_perturb(_batch)); }
+	// summary_weights: 8 or none; target: 3 or none
+	void rolloutCost(const std::vector<double>& summary_weights = {}, const std::vector<double>& target = {}, double path_weight = 0, double final_weight = 0) {
+		if (!summary_weights.empty() && summary_weights.size() != SAIP_RECORD_SUMMARY_ROWS) throw std::invalid_argument("rolloutCost: 8 summary weights expected");
+		if (!target.empty() && target.size() != 3) throw std::invalid_argument("rolloutCost: a target of 3 components expected");
+		check(saip_batch_sampler_cost(_batch, summary_weights.empty() ? nullptr : summary_weights.data(), target.empty() ? nullptr : target.data(), path_weight, final_weight));
+	}
+	void setRolloutCost(const std::vector<double>& cost) {
+		if ((int)cost.size() != _robot->batchSize()) throw std::invalid_argument("setRolloutCost: one cost per instance expected");
+		check(saip_batch_sampler_set_cost_host(_batch, cost.data()));
+	}
+	std::vector<double> getRolloutCost() {
+		std::vector<double> out((size_t)_robot->batchSize());
+		check(saip_batch_sampler_get_cost_host(_batch, out.data()));
+		return out;
+	}
+	void updateSampler(double temperature) { check(saip_batch_sampler_update(_batch, temperature)); }
+	void shiftSampler(int n) { check(saip_batch_sampler_shift(_batch, n)); }
+	SamplerResult samplerResult() {
+		SamplerResult r;
+		check(saip_batch_sampler_result_host(_batch, &r.best, &r.n_valid, &r.min_cost, &r.sum_w, &r.ess));
+		return r;
+	}
+	// every instance takes the saved state of the last update's best instance (the device-resident best map; none is moved without a finite cost)
+	void restoreStateBest(const StateSnapshot& snapshot) {
+		const int* map = saip_batch_sampler_best_map_device(_batch);
+		if (!map) throw std::runtime_error("restoreStateBest: no sampler is attached");
+		restoreStateDevice(snapshot, map);
 	}
 
 	// ---- rollout recorder: per-period trajectory log and running summaries of rolloutAsync, kept on the device (saip.h)

@@ -641,6 +641,61 @@ class _Task:
         ctrl = self._need_ctrl()
         return capi.lib().saip_batch_goal_schedule_device(ctrl._h, self._id)
 
+    # -- resident rollout sampler: perturb this task's scheduled keyframes around a nominal plan, update the plan from costs (saip.h)
+    def _sampler_shape(self):
+        """(first, count, K, rotation rows start inside the range or None, d) of this task's schedule as a sampler sees it"""
+        info = self.goalScheduleInfo()
+        first, count = info["first"], info["count"]
+        rot = isinstance(self, MotionForceTask) and first <= 3 and first + count >= 12
+        return first, count, info["n_keyframes"], (3 - first if rot else None), (count - 6 if rot else count)
+
+    def _sampler_plan(self, nominal, what):
+        _, count, K, _, _ = self._sampler_shape()
+        a = np.asarray(nominal, float)
+        if count == 9 and a.shape[-2:] == (3, 3):
+            a = a.reshape(a.shape[:-2] + (9,))
+        if a.shape != (K, count):
+            raise ValueError(f"{what}: a nominal plan of shape ({K}, {count}) expected, got {a.shape}")
+        return np.ascontiguousarray(a)
+
+    def attachSampler(self, sigma, nominal=None, exempt=1):
+        """attach a sampler to this task's goal schedule (per-instance keyframes): perturbGoalSchedules() rewrites the keyframes as
+        nominal + sigma * noise, updateSampler() folds the costs back into the nominal plan.  sigma: (d,) standard deviations or one
+        number for all; the coordinates are the scheduled rows in order, an orientation (rows 3..11 of a motion-force task) counting as
+        three tangent coordinates in radians.  nominal: (K, count), orientations also as (K, 3, 3); None takes instance 0's keyframes.
+        exempt: instances 0 .. exempt - 1 always run the nominal plan itself."""
+        ctrl = self._need_ctrl()
+        _, count, K, _, d = self._sampler_shape()
+        sg = np.asarray(sigma, float)
+        sg = np.full(d, float(sg)) if sg.ndim == 0 else np.ascontiguousarray(sg)
+        if sg.shape != (d,):
+            raise ValueError(f"attachSampler: sigma of shape ({d},) expected, got {sg.shape}")
+        nom = None if nominal is None else self._sampler_plan(nominal, "attachSampler")
+        ctrl._call("saip_batch_sampler_attach", self._id, _dptr(sg), None if nom is None else _dptr(nom), int(exempt))
+
+    def detachSampler(self):
+        self._need_ctrl()._call("saip_batch_sampler_detach", self._id)
+
+    def samplerNominal(self):
+        """the nominal plan (K, count), read back from the device (waits for the engine stream)"""
+        ctrl = self._need_ctrl()
+        capi.check(capi.lib().saip_batch_sampler_info(ctrl._h, self._id, None, None, None, None))
+        _, count, K, _, _ = self._sampler_shape()
+        out = np.empty((K, count))
+        ctrl._call("saip_batch_sampler_get_nominal_host", self._id, _dptr(out))
+        return out
+
+    def setSamplerNominal(self, nominal):
+        ctrl = self._need_ctrl()
+        capi.check(capi.lib().saip_batch_sampler_info(ctrl._h, self._id, None, None, None, None))
+        ctrl._call("saip_batch_sampler_set_nominal_host", self._id, _dptr(self._sampler_plan(nominal, "setSamplerNominal")))
+
+    def samplerInfo(self):
+        """dict d, exempt, seed, round (seed and round are the controller's)"""
+        d, ex, seed, rnd = C.c_int(0), C.c_int(0), C.c_ulonglong(0), C.c_longlong(0)
+        self._need_ctrl()._call("saip_batch_sampler_info", self._id, C.byref(d), C.byref(ex), C.byref(seed), C.byref(rnd))
+        return dict(d=d.value, exempt=ex.value, seed=seed.value, round=rnd.value)
+
     def getTaskNullspace(self, device=False):
         """(B, dof, dof) nullspace projector N of this task for the current state (TemplateTask.h:71-77)"""
         if self._manual:
@@ -1406,6 +1461,58 @@ class RobotController:
         """the period counter of the tasks' goal schedules (task.setGoalSchedule) back to 0: the next rollout starts at the first keyframe"""
         self._call("saip_batch_goal_schedule_rewind")
 
+    # -- resident rollout sampler: the device steps of a sampling-MPC round (task.attachSampler; saip.h)
+    def seedSampler(self, seed):
+        """the seed of the samplers' noise; the round counter goes back to 0"""
+        self._call("saip_batch_sampler_seed", C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def perturbGoalSchedules(self):
+        """rewrite the resident keyframes of every sampled task around its nominal plan (one launch); advances the round counter"""
+        self._call("saip_batch_sampler_perturb")
+
+    def rolloutCost(self, summary_weights=None, target=None, path_weight=0, final_weight=0):
+        """one cost per instance on the device from what the recorder holds: sum_r summary_weights[r] * rolloutSummary()[:, r]
+        + path_weight * sum over the logged samples of |position - target|^2 + final_weight * |last logged position - target|^2"""
+        w = t = None
+        if summary_weights is not None:
+            w = np.ascontiguousarray(summary_weights, float)
+            if w.shape != (capi.SAIP_RECORD_SUMMARY_ROWS,):
+                raise ValueError(f"rolloutCost: {capi.SAIP_RECORD_SUMMARY_ROWS} summary weights expected, got shape {w.shape}")
+        if target is not None:
+            t = np.ascontiguousarray(target, float)
+            if t.shape != (3,):
+                raise ValueError(f"rolloutCost: a target of shape (3,) expected, got {t.shape}")
+        self._call("saip_batch_sampler_cost", None if w is None else _dptr(w), None if t is None else _dptr(t), float(path_weight), float(final_weight))
+
+    def setRolloutCost(self, cost):
+        """upload (B,) costs in place of rolloutCost() (NaN and +-inf mark an instance as invalid)"""
+        c = np.ascontiguousarray(cost, float)
+        if c.shape != (self.batch_size,):
+            raise ValueError(f"setRolloutCost: {self.batch_size} costs expected, got shape {c.shape}")
+        self._call("saip_batch_sampler_set_cost_host", _dptr(c))
+
+    def getRolloutCost(self):
+        """(B,) the costs on the device (waits for the engine stream)"""
+        out = np.empty(self.batch_size)
+        self._call("saip_batch_sampler_get_cost_host", _dptr(out))
+        return out
+
+    def updateSampler(self, temperature):
+        """softmin-weighted update of every sampled task's nominal plan from the costs (MPPI; a tiny temperature takes the best);
+        writes samplerResult() and the "best" source map of restoreState on the device.  Asynchronous."""
+        self._call("saip_batch_sampler_update", float(temperature))
+
+    def shiftSampler(self, n):
+        """nominal[k] <- nominal[min(k + n, K - 1)]: the warm start of a receding horizon"""
+        self._call("saip_batch_sampler_shift", int(n))
+
+    def samplerResult(self):
+        """dict best, n_valid, min_cost, sum_w, ess of the last updateSampler() (waits for the engine stream)"""
+        best, nv = C.c_int(0), C.c_int(0)
+        mc, sw, ess = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._call("saip_batch_sampler_result_host", C.byref(best), C.byref(nv), C.byref(mc), C.byref(sw), C.byref(ess))
+        return dict(best=best.value, n_valid=nv.value, min_cost=mc.value, sum_w=sw.value, ess=ess.value)
+
     # -- state snapshots: the complete per-instance state, saved on the device and written back through a source index (saip.h)
     def saveState(self, snapshot=None):
         """capture the complete resident state of every instance (robot state, torques, goals, integrators, internal OTGs, singularity
@@ -1421,13 +1528,21 @@ class RobotController:
     def restoreState(self, snapshot, source=None):
         """instance i takes the state instance source[i] had when `snapshot` was saved.  source: None (every instance its own), an int
         (that instance's state into all), a sequence / NumPy int array of B indices (checked on the host), or a torch int32 device
-        tensor of B indices read in stream order (an entry outside 0 .. B-1 leaves that instance as it is).  Asynchronous.  The rollout
+        tensor of B indices read in stream order (an entry outside 0 .. B-1 leaves that instance as it is), or "best": the map the last
+        updateSampler() left on the device.  Asynchronous.  The rollout
         recorder and the goal schedules are not part of a snapshot: pair with resetRolloutRecorder() / rewindGoalSchedules()."""
         if not isinstance(snapshot, StateSnapshot) or snapshot._ctrl is not self:
             raise ValueError("restoreState: the snapshot belongs to another controller")
         B, h = self.batch_size, snapshot._handle()
         if source is None:
             self._call("saip_batch_snapshot_restore", h, None)
+        elif isinstance(source, str):
+            if source != "best":
+                raise ValueError(f"restoreState: unknown source {source!r} (the only named source is \"best\")")
+            ptr = capi.lib().saip_batch_sampler_best_map_device(self._h)
+            if not ptr:
+                raise capi.SaipError("restoreState: source \"best\" needs a sampler (task.attachSampler)")
+            self._call("saip_batch_snapshot_restore_device", h, C.c_void_p(ptr))
         elif hasattr(source, "data_ptr") and getattr(source, "is_cuda", False):
             import torch
             if source.dtype != torch.int32 or source.numel() != B or not source.is_contiguous():

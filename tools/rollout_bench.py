@@ -9,7 +9,11 @@
    orientation rows of the motion-force task (8 keyframes, stride 50; linear interpolates the orientation on SO(3)).
    --snapshot prints the bytes of a state snapshot of the stack and, event-timed on the engine stream (mean of 50 back-to-back calls), a
    save, an identity restore, a random-permutation restore, a broadcast restore and plain hipMemcpyAsync device-to-device copies of
-   segments of the same sizes (the yardstick of DESIGN.md 4.10)."""
+   segments of the same sizes (the yardstick of DESIGN.md 4.10).
+   --sampler attaches a resident rollout sampler to a 16-keyframe position + orientation schedule of the motion-force task and prints the
+   event-timed mean of 50 calls each of perturb, cost and update, and beside them the host round trip they replace: rolloutSummary(), the
+   NumPy perturb and update of tests/sampler_ref.py, detach and attach of the new keyframes, by wall clock around a synchronise
+   (DESIGN.md 4.11)."""
 import argparse
 import os
 import sys
@@ -28,6 +32,7 @@ ap.add_argument("--no-otg", action="store_true")
 ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--goal-schedule", choices=("hold", "linear"), default=None)
 ap.add_argument("--snapshot", action="store_true")
+ap.add_argument("--sampler", action="store_true")
 args = ap.parse_args()
 record = args.record_stride is not None or args.record_channels is not None or args.record_summaries
 
@@ -97,6 +102,64 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
         for p in bufs:
             hip.hipFree(p)
         snap.close()
+        continue
+    if args.sampler:
+        import ctypes as C
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import sampler_ref as SR
+        hip = C.CDLL("libamdhip64.so")
+        vp = C.c_void_p
+        hip.hipEventCreate.argtypes, hip.hipEventRecord.argtypes, hip.hipEventSynchronize.argtypes = [C.POINTER(vp)], [vp, vp], [vp]
+        hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), vp, vp]
+        stream = ctrl.devicePointers()["stream"]
+        ev = [vp(), vp()]
+        for e in ev:
+            assert hip.hipEventCreate(C.byref(e)) == 0
+
+        def timed_us(fn, reps=50):
+            fn()
+            ctrl.synchronize()
+            assert hip.hipEventRecord(ev[0], stream) == 0
+            for _ in range(reps):
+                fn()
+            assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
+            ms = C.c_float()
+            assert hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
+            return ms.value / reps * 1e3
+
+        KF, sigma, T = 16, np.array([0.02, 0.02, 0.02, 0.05, 0.05, 0.05]), 0.05
+        nominal = np.repeat(mf._get_goal()[0, :12][None], KF, axis=0)
+        ctrl.recordRollouts(8, max(1, K // 8), ("pose",), task=mf, summaries=True)     # 8 samples over the K periods rolled below
+        mf.setGoalSchedule((0, 12), np.repeat(nominal[:, None], B, axis=1), stride=25, mode="linear")
+        mf.attachSampler(sigma, nominal=nominal, exempt=1)
+        ctrl.seedSampler(1)
+        ctrl.rolloutAsync(K, 5e-4, 2, gravity=(0, 0, 0))
+        w8, target = np.array([1e-4, 1.0, 1.0, 0, 0, 0, 0, 10.0]), nominal[0, :3] + 0.03
+
+        def host_round(rnd):
+            S = ctrl.rolloutSummary()
+            cost = S @ w8
+            keys = SR.perturb(nominal, sigma, 1, rnd, 0, B, 1, 3)
+            w, res = SR.weights(cost, T)
+            new = SR.update(nominal, keys, w, res["best"], 3)
+            mf.clearGoalSchedule()
+            mf.setGoalSchedule((0, 12), keys, stride=25, mode="linear")
+            ctrl.synchronize()
+            return new
+
+        for r in range(args.repeats):
+            t = dict(perturb=timed_us(ctrl.perturbGoalSchedules), cost=timed_us(lambda: ctrl.rolloutCost(w8, target, 0.1, 1.0)),
+                     update=timed_us(lambda: ctrl.updateSampler(T)))
+            mf.detachSampler()
+            ctrl.synchronize()
+            t0 = time.perf_counter()
+            for i in range(3):
+                host_round(i)
+            host = (time.perf_counter() - t0) / 3 * 1e6
+            mf.attachSampler(sigma, nominal=nominal, exempt=1)
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'}: sampler, {KF} keyframes of position + "
+                  f"orientation: perturb {t['perturb']:.1f} us; cost {t['cost']:.1f} us; update {t['update']:.1f} us; host round trip (summary, NumPy perturb + "
+                  f"update, detach + attach) {host:.0f} us")
         continue
     if args.goal_schedule:
         def timed(calls, steps):
