@@ -347,6 +347,52 @@ const int* saip_batch_sampler_best_map_device(saip_batch*);                 /* [
 saip_status saip_batch_sampler_get_nominal_host(saip_batch*, int task, double* out /* [K][count] */);
 saip_status saip_batch_sampler_set_nominal_host(saip_batch*, int task, const double* in);
 saip_status saip_batch_sampler_info(saip_batch*, int task, int* d, int* exempt, unsigned long long* seed, long long* round);
+/* ---- contact planes and a simulated force sensor: something for the resident simulator to touch, so that a force task (closed-loop
+ * force / moment control, the passivity observer, the sensed-wrench diagnostics) can be rolled out with no host in the loop.  One
+ * attachment per batch: ONE contact point p = x_c + R_c r_c carried by the body of a motion-force task (x_c, R_c: its control point and
+ * control frame in the world, r_c: an offset in the control frame, NULL = 0) against n_planes (1..SAIP_CONTACT_MAX_PLANES) world-fixed
+ * half-spaces.  A plane is eight doubles { n[3], o, k, c, mu, v_s }: normal (normalised by the engine), offset, stiffness k > 0,
+ * damping c >= 0, friction mu >= 0, slip-regularisation speed v_s > 0.  `planes` is [P][8] (batch-uniform) or [P][8][B] (per_instance).
+ * With d = n.p - o and v the velocity of the point, a plane acts only when d < 0:
+ *   v_n = n.v    f_n = max(0, -k d - c v_n)    v_t = v - v_n n    f_t = -mu f_n v_t / max(|v_t|, v_s)    f = sum (f_n n + f_t)
+ * every product and sum rounded once, in that order (csrc/saip_contact.h; tests/contact_ref.py restates it in NumPy bit for bit).
+ *   while attached, every integration of saip_batch_rollout_async and saip_batch_integrate becomes, per SUBSTEP: one launch that writes
+ *        tau_sim[j] = (tau[j] is NaN ? 0 : tau[j]) + (J_v^T f)[j] into a buffer of the attachment (a flagged instance still gets pushed
+ *        by the wall; a joint that is not an ancestor of the body gets no contact torque), then the integrator with that buffer and one
+ *        substep.  The force is an explicit penalty force: it is stable roughly while k dt^2 / m_eff < 1 (dt the substep, m_eff the
+ *        effective mass at the point along the normal); this is not enforced.  The torque array of the batch is left as the cycle wrote
+ *        it (the recorder keeps logging the commanded torques).  The fused forms of a rollout period are not used while attached.
+ *   sensor != 0: a rollout period starts (behind its goal schedules) with one launch that writes the wrench a sensor would report at
+ *        the period's state into rows 30..35 of the task's goal block: world F = -f, m = (p - x_c) x F (the wrench the sensor applies
+ *        to the environment, MotionForceTask.h:538-553), then FS = R_cs^T R_c^T F, MS = R_cs^T (R_c^T m - t_cs x R_c^T F) -- the exact
+ *        inverse of what the control law does with those rows.  saip_batch_contact_sense enqueues the same launch, so the host-driven
+ *        loop { _contact_sense, saip_batch_step_async, saip_batch_integrate } leaves the bits of a rollout period.  A goal schedule of
+ *        that task that covers any of rows 30..35 cannot coexist with the sensor (SAIP_ERR_ORDER from whichever _attach comes second).
+ *   readout [8][ld] (both launches): f (world) 3, p 3, the smallest d over the planes, the number of active planes -- of the LAST launch.
+ *   summaries [4][ld], advanced by every substep: sum dt sum f_n, max |f|, max penetration (-d), substeps in contact.  _summary_reset
+ *        zeroes them on the stream; _set_planes_host replaces the table (same shape) and waits; _planes_device is the resident table
+ *        ([P][8] or [P][8][ld]) for domain randomisation on the device -- what is written there is not checked.
+ * The attachment's arrays are configuration, scratch and readout: not part of a state snapshot.  Without an attachment every entry
+ * point enqueues exactly what it did before.  SAIP_ERR_INVALID_ARGUMENT: a task that is not a motion-force task, n_planes outside
+ * 1..4, NULL planes, a value that is not finite, a zero normal, k <= 0, c < 0, mu < 0, v_s <= 0.  SAIP_ERR_ORDER: before finalize, a
+ * model-only batch, a second _attach, any other entry without an attachment, _contact_sense on an attachment without the sensor.
+ * Argument and order errors are reported before the device is needed. */
+#define SAIP_CONTACT_MAX_PLANES 4
+#define SAIP_CONTACT_PLANE_WORDS 8
+#define SAIP_CONTACT_READOUT_ROWS 8
+#define SAIP_CONTACT_SUMMARY_ROWS 4
+saip_status saip_batch_contact_attach(saip_batch*, int task, const double r_c[3] /* NULL = 0 */, int n_planes, const double* planes, int per_instance, int sensor);
+saip_status saip_batch_contact_detach(saip_batch*);
+saip_status saip_batch_contact_info(saip_batch*, int* task, int* n_planes, int* per_instance, int* sensor, double* r_c /* [3] */);  /* any NULL */
+saip_status saip_batch_contact_set_planes_host(saip_batch*, const double* planes);
+double* saip_batch_contact_planes_device(saip_batch*);   /* NULL when detached */
+saip_status saip_batch_contact_sense(saip_batch*);
+saip_status saip_batch_contact_readout_host(saip_batch*, double* out /* [8][B] */);  /* synchronous */
+double* saip_batch_contact_readout_device(saip_batch*);  /* [8][ld]; NULL when detached */
+double* saip_batch_contact_torques_device(saip_batch*);  /* [dof][ld] tau_sim of the last integrated substep; NULL when detached */
+saip_status saip_batch_contact_summary_host(saip_batch*, double* out /* [4][B] */);  /* synchronous */
+double* saip_batch_contact_summary_device(saip_batch*);  /* [4][ld]; NULL when detached */
+saip_status saip_batch_contact_summary_reset(saip_batch*);
 /* ---- rollout recorder: a per-period trajectory log and running summaries of saip_batch_rollout_async, kept on the device (the
  * reference's example loops print or log the same quantities every period: state, torques, position / orientation error).  A recorder
  * is attached to a finalized batch and stays attached across rollout calls until detached.  It observes rollout periods only

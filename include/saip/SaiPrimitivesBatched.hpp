@@ -23,6 +23,7 @@
 #include <functional>
 #include <memory>
 #include <stdexcept>
+#include <array>
 #include <string>
 #include <vector>
 
@@ -365,6 +366,12 @@ public:
 	// ---- resident rollout sampler on this task's per-instance goal schedule (saip.h): sigma [d] over the scheduled rows in order, an
 	// orientation (rows 3..11 of a motion-force task) counting as three tangent coordinates; nominal [n_keyframes][count], empty =
 	// instance 0's keyframes; instances 0 .. exempt - 1 always run the nominal plan
+	void contactMine(int* n_planes = nullptr, int* per_instance = nullptr) {  // the controller's contact planes are attached to THIS task
+		need();
+		int task = -1;
+		check(saip_batch_contact_info(_batch, &task, n_planes, per_instance, nullptr, nullptr));
+		if (task != _id) throw std::runtime_error("the contact planes of this controller are attached to another task");
+	}
 	void attachSampler(const std::vector<double>& sigma, const std::vector<double>& nominal = {}, int exempt = 1) {
 		need();
 		int first = 0, count = 0, nk = 0;
@@ -378,6 +385,50 @@ public:
 	void detachSampler() {
 		need();
 		check(saip_batch_sampler_detach(_batch, _id));
+	}
+	// ---- contact planes and the simulated force sensor of the resident simulator (saip.h): one contact point (`point`, in this task's control
+	// frame) on this task's body against 1..4 world-fixed half-spaces.  planes: [P][8] rows { n[3], offset, k, c, mu, v_s }, or [P][8][B] with
+	// per_instance.  A motion-force task only (the engine refuses any other).
+	void attachContactPlanes(const std::vector<double>& planes, int n_planes, const std::array<double, 3>& point = {0.0, 0.0, 0.0}, bool sensor = true,
+							 bool per_instance = false) {
+		need();
+		const size_t cols = per_instance ? (size_t)saip_batch_size(_batch) : 1;
+		if (n_planes < 1 || planes.size() != (size_t)n_planes * SAIP_CONTACT_PLANE_WORDS * cols)
+			throw std::invalid_argument("attachContactPlanes: expected [n_planes][8] planes, or [n_planes][8][B] per instance");
+		check(saip_batch_contact_attach(_batch, _id, point.data(), n_planes, planes.data(), per_instance ? 1 : 0, sensor ? 1 : 0));
+	}
+	void detachContactPlanes() {
+		contactMine();
+		check(saip_batch_contact_detach(_batch));
+	}
+	void setContactPlanes(const std::vector<double>& planes) {
+		int np = 0, per = 0;
+		contactMine(&np, &per);
+		if (planes.size() != (size_t)np * SAIP_CONTACT_PLANE_WORDS * (per ? (size_t)saip_batch_size(_batch) : 1))
+			throw std::invalid_argument("setContactPlanes: the shape of the attached plane table expected");
+		check(saip_batch_contact_set_planes_host(_batch, planes.data()));
+	}
+	double* contactPlanesDevice() {
+		need();
+		return saip_batch_contact_planes_device(_batch);
+	}
+	// [8][B]: force on the robot (world) 3, point 3, smallest signed distance, active planes -- of the last contact launch; waits for the stream
+	std::vector<double> contactReadout() {
+		contactMine();
+		std::vector<double> out((size_t)SAIP_CONTACT_READOUT_ROWS * saip_batch_size(_batch));
+		check(saip_batch_contact_readout_host(_batch, out.data()));
+		return out;
+	}
+	// [4][B]: sum dt * normal force, max |f|, max penetration, substeps in contact; waits for the stream
+	std::vector<double> contactSummary() {
+		contactMine();
+		std::vector<double> out((size_t)SAIP_CONTACT_SUMMARY_ROWS * saip_batch_size(_batch));
+		check(saip_batch_contact_summary_host(_batch, out.data()));
+		return out;
+	}
+	void resetContactSummary() {
+		contactMine();
+		check(saip_batch_contact_summary_reset(_batch));
 	}
 	std::vector<double> samplerNominal() {
 		need();
@@ -1052,6 +1103,13 @@ public:
 		std::vector<double> out((size_t)SAIP_RECORD_SUMMARY_ROWS * _robot->batchSize());
 		check(saip_batch_rollout_summary_host(_batch, out.data()));
 		return out;
+	}
+	// the simulated sensor of the attached contact planes (task->attachContactPlanes) at the current state: what a rollout period does first,
+	// for a host-driven loop { contactSense, computeControlTorques / stepAsync, integrate }
+	void contactSense() {
+		check(saip_batch_contact_info(_batch, nullptr, nullptr, nullptr, nullptr, nullptr));  // without an attachment: that error, before the device is needed
+		pushState();
+		check(saip_batch_contact_sense(_batch));
 	}
 
 private:

@@ -845,6 +845,86 @@ class MotionForceTask(_Task):
     def disablePassivity(self):
         self._cfg("saip_batch_set_passivity", 0)
 
+    # -- contact planes and the simulated force sensor of the resident simulator (saip.h)
+    @staticmethod
+    def _contact_planes(planes, per_instance, B, who, n_planes=None):
+        a = np.asarray(planes, float)
+        W = capi.SAIP_CONTACT_PLANE_WORDS
+        if per_instance:
+            if a.ndim != 3 or a.shape[1:] != (B, W) or (n_planes is not None and a.shape[0] != n_planes):
+                raise ValueError(f"{who}: per-instance planes of shape ({'P' if n_planes is None else n_planes}, {B}, {W}) expected, got {a.shape}")
+            return np.ascontiguousarray(a.transpose(0, 2, 1))
+        if a.ndim != 2 or a.shape[1] != W or (n_planes is not None and a.shape[0] != n_planes):
+            raise ValueError(f"{who}: planes of shape ({'P' if n_planes is None else n_planes}, {W}) expected, got {a.shape}")
+        return np.ascontiguousarray(a)
+
+    def attachContactPlanes(self, planes, point=(0.0, 0.0, 0.0), sensor=True, per_instance=False):
+        """give the resident simulator something to touch: one contact point (`point`, in this task's control frame) on this task's body
+        against 1..4 world-fixed half-spaces.  planes: (P, 8) rows { n[3], offset, stiffness k, damping c, friction mu, slip speed v_s },
+        or (P, B, 8) with per_instance.  While attached, integrate() and rolloutAsync() add the contact force to the torques in front of
+        every substep; with `sensor` a rollout period starts by writing the wrench a force sensor would report into this task's sensed
+        force / moment (contactSense() does the same for a host-driven loop)."""
+        ctrl = self._need_ctrl()
+        a = self._contact_planes(planes, per_instance, ctrl.batch_size, "attachContactPlanes")
+        rc = np.ascontiguousarray(np.asarray(point, float).reshape(-1))
+        if rc.shape != (3,):
+            raise ValueError(f"attachContactPlanes: a point of shape (3,) expected, got {rc.shape}")
+        ctrl._call("saip_batch_contact_attach", self._id, _dptr(rc), a.shape[0], _dptr(a), int(bool(per_instance)), int(bool(sensor)))
+
+    def _contact_info(self):
+        v = [C.c_int(0) for _ in range(4)]
+        rc = np.zeros(3)
+        ctrl = self._need_ctrl()
+        ctrl._call("saip_batch_contact_info", *(C.byref(x) for x in v), _dptr(rc))
+        if v[0].value != self._id:
+            raise capi.SaipError(f"the contact planes of this controller are attached to task {v[0].value}, not to [{self.getTaskName()}]")
+        return dict(task=v[0].value, n_planes=v[1].value, per_instance=bool(v[2].value), sensor=bool(v[3].value), point=rc)
+
+    def contactInfo(self):
+        """dict task, n_planes, per_instance, sensor, point"""
+        return self._contact_info()
+
+    def detachContactPlanes(self):
+        self._contact_info()
+        self._need_ctrl()._call("saip_batch_contact_detach")
+
+    def setContactPlanes(self, planes):
+        """replace the plane table (same shape as attached); takes effect with the next launch"""
+        info = self._contact_info()
+        ctrl = self._need_ctrl()
+        a = self._contact_planes(planes, info["per_instance"], ctrl.batch_size, "setContactPlanes", info["n_planes"])
+        ctrl._call("saip_batch_contact_set_planes_host", _dptr(a))
+
+    def contactPlanesDevice(self):
+        """device pointer of the resident plane table, (P, 8) or (P, 8, ld), for domain randomisation on the device; None when detached"""
+        return capi.lib().saip_batch_contact_planes_device(self._need_ctrl()._h)
+
+    def contactTorquesDevice(self):
+        """device pointer of (dof, ld) commanded + contact torques of the last integrated substep; None when detached"""
+        return capi.lib().saip_batch_contact_torques_device(self._need_ctrl()._h)
+
+    def contactReadout(self):
+        """dict of the last contact launch: force (B, 3) on the robot in the world frame, point (B, 3), distance (B,) the smallest signed
+        distance over the planes, active (B,) the number of planes in contact (waits for the engine stream)"""
+        self._contact_info()
+        ctrl = self._need_ctrl()
+        out = np.empty((capi.SAIP_CONTACT_READOUT_ROWS, ctrl.batch_size))
+        ctrl._call("saip_batch_contact_readout_host", _dptr(out))
+        return dict(force=out[0:3].T.copy(), point=out[3:6].T.copy(), distance=out[6].copy(), active=out[7].astype(int))
+
+    def contactSummary(self):
+        """dict of the running summaries over the integrated substeps: impulse (B,) sum dt * normal force, max_force (B,), max_penetration
+        (B,), substeps_in_contact (B,) (waits for the engine stream)"""
+        self._contact_info()
+        ctrl = self._need_ctrl()
+        out = np.empty((capi.SAIP_CONTACT_SUMMARY_ROWS, ctrl.batch_size))
+        ctrl._call("saip_batch_contact_summary_host", _dptr(out))
+        return dict(impulse=out[0].copy(), max_force=out[1].copy(), max_penetration=out[2].copy(), substeps_in_contact=out[3].astype(int))
+
+    def resetContactSummary(self):
+        self._contact_info()
+        self._need_ctrl()._call("saip_batch_contact_summary_reset")
+
     def updateSensedForceAndMoment(self, sensed_force_sensor_frame, sensed_moment_sensor_frame):  # MotionForceTask.cpp:805-828
         self._set_field(30, 3, sensed_force_sensor_frame, "updateSensedForceAndMoment (force)")
         self._set_field(33, 3, sensed_moment_sensor_frame, "updateSensedForceAndMoment (moment)")
@@ -1456,6 +1536,13 @@ class RobotController:
         self._push_state()
         g, gp = self._grav(gravity)
         self._call("saip_batch_rollout_async", int(steps), float(sim_dt), int(substeps), gp, float(damping))
+
+    def contactSense(self):
+        """enqueue the simulated sensor of the attached contact planes (task.attachContactPlanes) at the current state: what a rollout
+        period does first, for a host-driven loop { contactSense, computeControlTorques / stepAsync, integrate }"""
+        self._call("saip_batch_contact_info", None, None, None, None, None)  # without an attachment: that error, before the device is needed
+        self._push_state()
+        self._call("saip_batch_contact_sense")
 
     def rewindGoalSchedules(self):
         """the period counter of the tasks' goal schedules (task.setGoalSchedule) back to 0: the next rollout starts at the first keyframe"""

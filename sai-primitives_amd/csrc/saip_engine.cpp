@@ -16,6 +16,7 @@
 #include "saip_cycle_plan.h"
 #include "saip_state_snapshot.h"
 #include "saip_sampler.h"
+#include "saip_contact.h"
 
 namespace saip {
 hipError_t launch_cycle_wg(const CycleParams& P, bool tree, hipStream_t stream);
@@ -42,6 +43,7 @@ hipError_t launch_sampler_perturb(const SamplerParams& P, hipStream_t stream);
 hipError_t launch_sampler_cost(const SamplerCostParams& P, hipStream_t stream);
 hipError_t launch_sampler_update(const SamplerParams& P, const double* cost, double temperature, double* w, SamplerResult* res, int* best_map, hipStream_t stream);
 hipError_t launch_sampler_shift(const SamplerParams& P, int n, hipStream_t stream);
+hipError_t launch_contact_apply(const ContactParams& P, bool tree, hipStream_t stream);
 }  // namespace saip
 
 using saip::CycleParams;
@@ -485,6 +487,17 @@ struct saip_batch {
 	double* samp_w = nullptr;                // [ld] softmin weights of the last update
 	int* samp_best_map = nullptr;            // [ld]
 	saip::SamplerResult* samp_result = nullptr;
+	// saip_batch_contact_attach: contact planes and the simulated force sensor of the resident simulator (saip_contact.hip), at most one
+	// per batch.  Its arrays are configuration, scratch and readout: its own (freed by _detach), not part of `allocs` or of a snapshot.
+	struct Contact {
+		bool attached = false;
+		int task = -1, n_planes = 0, per_instance = 0, sensor = 0;
+		double rc[3] = {0, 0, 0};
+		double* planes = nullptr;            // [P][8] (batch-uniform) or [P][8][ld]
+		double* tau_sim = nullptr;           // [n][ld] commanded + contact torques of the substep being integrated
+		double* readout = nullptr;           // [8][ld]
+		double* summary = nullptr;           // [4][ld]
+	} contact;
 };
 
 static bool has_device(const saip_batch* b) { return b->device >= 0; }
@@ -538,6 +551,8 @@ extern "C" void saip_batch_destroy(saip_batch* b) {
 		for (auto& S : b->samp)
 			if (S.nominal) (void)hipFree(S.nominal);
 		for (void* p : {(void*)b->samp_cost, (void*)b->samp_w, (void*)b->samp_best_map, (void*)b->samp_result})
+			if (p) (void)hipFree(p);
+		for (void* p : {(void*)b->contact.planes, (void*)b->contact.tau_sim, (void*)b->contact.readout, (void*)b->contact.summary})
 			if (p) (void)hipFree(p);
 		if (b->stream) (void)hipStreamDestroy(b->stream);
 	}
@@ -2083,6 +2098,196 @@ extern "C" saip_status saip_batch_set_kernel(saip_batch* b, int which) {
 }
 extern "C" const char* saip_batch_kernel_name(saip_batch* b) { return b ? b->kernel_name.c_str() : ""; }
 
+// ---- contact planes and the simulated force sensor (saip_contact.hip): the resident simulator gets something to touch
+static saip_status need_controller(const saip_batch* b, const char* fn);
+static saip_status need_contact(const saip_batch* b, const char* fn) {
+	saip_status st = need_controller(b, fn);
+	if (st) return st;
+	if (!b->contact.attached) return fail(SAIP_ERR_ORDER, "%s: no contact planes are attached (saip_batch_contact_attach)", fn);
+	return SAIP_OK;
+}
+static void contact_free(saip_batch* b) {
+	auto& C = b->contact;
+	for (void* p : {(void*)C.planes, (void*)C.tau_sim, (void*)C.readout, (void*)C.summary})
+		if (p) (void)hipFree(p);
+	C = saip_batch::Contact();
+}
+// the plane table as the device keeps it: [P][8] or [P][8][B] with every normal normalised; nullptr: fine, else what is wrong
+static const char* contact_check_planes(const double* planes, int P, size_t cols, std::vector<double>& out) {
+	out.assign(planes, planes + (size_t)P * saip::CONTACT_PLANE_WORDS * cols);
+	for (size_t i = 0; i < out.size(); i++)
+		if (!std::isfinite(out[i])) return "a plane value is not finite";
+	for (int k = 0; k < P; k++)
+		for (size_t i = 0; i < cols; i++) {
+			double* w = out.data() + (size_t)k * saip::CONTACT_PLANE_WORDS * cols + i;
+			const double nn = std::sqrt(w[0] * w[0] + w[cols] * w[cols] + w[2 * cols] * w[2 * cols]);
+			if (!(nn > 0) || !std::isfinite(nn)) return "a plane normal is zero";
+			for (int e = 0; e < 3; e++) w[e * cols] /= nn;
+			if (!(w[4 * cols] > 0)) return "stiffness k > 0 required";
+			if (!(w[5 * cols] >= 0)) return "damping c >= 0 required";
+			if (!(w[6 * cols] >= 0)) return "friction mu >= 0 required";
+			if (!(w[7 * cols] > 0)) return "slip-regularisation speed v_s > 0 required";
+		}
+	return nullptr;
+}
+static saip_status contact_upload_planes(saip_batch* b, double* dev, const std::vector<double>& host, int P, int per_instance, const char* fn) {
+	const size_t rows = (size_t)P * saip::CONTACT_PLANE_WORDS;
+	hipError_t e;
+	if (per_instance)
+		e = hipMemcpy2DAsync(dev, (size_t)b->ld * sizeof(double), host.data(), (size_t)b->B * sizeof(double), (size_t)b->B * sizeof(double), rows,
+							 hipMemcpyHostToDevice, b->stream);
+	else e = hipMemcpyAsync(dev, host.data(), rows * sizeof(double), hipMemcpyHostToDevice, b->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(b->stream);  // `host` goes out of scope with the caller
+	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "%s: plane upload failed: %s", fn, hipGetErrorString(e));
+	return SAIP_OK;
+}
+static bool contact_rows_overlap(int first, int count) { return first < 36 && first + count > 30; }
+extern "C" saip_status saip_batch_contact_attach(saip_batch* b, int task, const double* r_c, int n_planes, const double* planes, int per_instance,
+												 int sensor) {
+	const char* fn = "saip_batch_contact_attach";
+	saip_status st = need_controller(b, fn);
+	if (st) return st;
+	if (task < 0 || task >= (int)b->tasks.size()) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: task id %d out of range", fn, task);
+	if (b->tasks[task].dev.type != saip::TASK_MOTION_FORCE) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: task %d is not a motion-force task", fn, task);
+	if (b->contact.attached) return fail(SAIP_ERR_ORDER, "%s: contact planes are already attached (saip_batch_contact_detach first)", fn);
+	if (n_planes < 1 || n_planes > saip::CONTACT_MAX_PLANES) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: 1..%d planes required (got %d)", fn, saip::CONTACT_MAX_PLANES, n_planes);
+	if (!planes) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null planes", fn);
+	per_instance = per_instance ? 1 : 0;
+	sensor = sensor ? 1 : 0;
+	double rc[3] = {0, 0, 0};
+	for (int e = 0; e < 3 && r_c; e++) {
+		if (!std::isfinite(r_c[e])) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the contact point is not finite", fn);
+		rc[e] = r_c[e];
+	}
+	// [n][ld], [P][8][ld] doubles: the byte counts must fit a size_t
+	const size_t widest = (size_t)(b->model->n > 32 ? b->model->n : 32) * sizeof(double);
+	if ((size_t)b->ld > SIZE_MAX / widest) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: arrays of leading dimension %d are too large", fn, b->ld);
+	std::vector<double> host;
+	if (const char* bad = contact_check_planes(planes, n_planes, per_instance ? (size_t)b->B : 1, host)) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, bad);
+	if (sensor && task < (int)b->sched.size() && b->sched[task].attached && contact_rows_overlap(b->sched[task].first, b->sched[task].count))
+		return fail(SAIP_ERR_ORDER, "%s: the goal schedule of task %d covers sensed-wrench rows 30..35, which the simulated sensor writes", fn, task);
+	if ((st = need_ready(b, fn))) return st;
+	auto& C = b->contact;
+	auto alloc_zero = [&](double** p, size_t count) -> saip_status {
+		HIP_TRY(hipMalloc((void**)p, count * sizeof(double)));
+		HIP_TRY(hipMemsetAsync(*p, 0, count * sizeof(double), b->stream));
+		return SAIP_OK;
+	};
+	const size_t ld = b->ld, rows = (size_t)n_planes * saip::CONTACT_PLANE_WORDS;
+	if ((st = alloc_zero(&C.planes, rows * (per_instance ? ld : 1))) || (st = alloc_zero(&C.tau_sim, (size_t)b->model->n * ld)) ||
+		(st = alloc_zero(&C.readout, (size_t)saip::CONTACT_READOUT_ROWS * ld)) || (st = alloc_zero(&C.summary, (size_t)saip::CONTACT_SUMMARY_ROWS * ld)) ||
+		(st = contact_upload_planes(b, C.planes, host, n_planes, per_instance, fn))) {
+		contact_free(b);
+		return st;
+	}
+	C.attached = true;
+	C.task = task;
+	C.n_planes = n_planes;
+	C.per_instance = per_instance;
+	C.sensor = sensor;
+	for (int e = 0; e < 3; e++) C.rc[e] = rc[e];
+	b->otg_prelaunched = false;
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_contact_detach(saip_batch* b) {
+	const char* fn = "saip_batch_contact_detach";
+	saip_status st = need_contact(b, fn);
+	if (st || (st = need_ready(b, fn))) return st;
+	HIP_TRY(hipStreamSynchronize(b->stream));  // a contact substep may still be in flight
+	contact_free(b);
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_contact_info(saip_batch* b, int* task, int* n_planes, int* per_instance, int* sensor, double* r_c) {
+	saip_status st = need_contact(b, "saip_batch_contact_info");
+	if (st) return st;
+	const auto& C = b->contact;
+	if (task) *task = C.task;
+	if (n_planes) *n_planes = C.n_planes;
+	if (per_instance) *per_instance = C.per_instance;
+	if (sensor) *sensor = C.sensor;
+	for (int e = 0; e < 3 && r_c; e++) r_c[e] = C.rc[e];
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_contact_set_planes_host(saip_batch* b, const double* planes) {
+	const char* fn = "saip_batch_contact_set_planes_host";
+	saip_status st = need_contact(b, fn);
+	if (st) return st;
+	if (!planes) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null planes", fn);
+	const auto& C = b->contact;
+	std::vector<double> host;
+	if (const char* bad = contact_check_planes(planes, C.n_planes, C.per_instance ? (size_t)b->B : 1, host)) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, bad);
+	if ((st = need_ready(b, fn))) return st;
+	return contact_upload_planes(b, C.planes, host, C.n_planes, C.per_instance, fn);
+}
+extern "C" double* saip_batch_contact_planes_device(saip_batch* b) { return b ? b->contact.planes : nullptr; }
+extern "C" double* saip_batch_contact_torques_device(saip_batch* b) { return b ? b->contact.tau_sim : nullptr; }
+extern "C" double* saip_batch_contact_readout_device(saip_batch* b) { return b ? b->contact.readout : nullptr; }
+extern "C" double* saip_batch_contact_summary_device(saip_batch* b) { return b ? b->contact.summary : nullptr; }
+// one launch of the contact kernel at the resident state; dt: the substep an APPLY launch stands in front of
+static saip_status contact_launch(saip_batch* b, int mode, double dt) {
+	const auto& C = b->contact;
+	{
+		CycleParams cp;  // (the task constants on the device must be current: uploaded here when the configuration changed)
+		saip_status st = make_params(b, cp, false);
+		if (st) return st;
+	}
+	saip::ContactParams P;
+	memset(&P, 0, sizeof(P));
+	P.B = b->B;
+	P.ld = b->ld;
+	P.n = b->model->n;
+	P.mode = mode;
+	P.task = C.task;
+	P.n_planes = C.n_planes;
+	P.per_instance = C.per_instance;
+	P.dt = dt;
+	for (int e = 0; e < 3; e++) P.rc[e] = C.rc[e];
+	P.model = b->model_dev;
+	P.tasks = b->tasks_dev;
+	P.q = b->q;
+	P.dq = b->dq;
+	P.planes = C.planes;
+	P.goal = b->tasks[C.task].goal_dev;
+	P.tau_cmd = b->tau_bound ? b->tau_bound : b->tau;
+	P.tau_sim = C.tau_sim;
+	P.readout = C.readout;
+	P.summary = C.summary;
+	hipError_t e = saip::launch_contact_apply(P, b->model->dev.is_tree != 0, b->stream);
+	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "contact launch failed: %s", hipGetErrorString(e));
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_contact_sense(saip_batch* b) {
+	const char* fn = "saip_batch_contact_sense";
+	saip_status st = need_contact(b, fn);
+	if (st) return st;
+	if (!b->contact.sensor) return fail(SAIP_ERR_ORDER, "%s: the contact planes were attached without the simulated sensor", fn);
+	if ((st = need_ready(b, fn))) return st;
+	return contact_launch(b, saip::CONTACT_SENSE, 0.0);
+}
+extern "C" saip_status saip_batch_contact_readout_host(saip_batch* b, double* out) {
+	const char* fn = "saip_batch_contact_readout_host";
+	saip_status st = need_contact(b, fn);
+	if (st) return st;
+	if (!out) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null output", fn);
+	if ((st = need_ready(b, fn))) return st;
+	return copy_d2h(b, out, b->contact.readout, saip::CONTACT_READOUT_ROWS);
+}
+extern "C" saip_status saip_batch_contact_summary_host(saip_batch* b, double* out) {
+	const char* fn = "saip_batch_contact_summary_host";
+	saip_status st = need_contact(b, fn);
+	if (st) return st;
+	if (!out) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null output", fn);
+	if ((st = need_ready(b, fn))) return st;
+	return copy_d2h(b, out, b->contact.summary, saip::CONTACT_SUMMARY_ROWS);
+}
+extern "C" saip_status saip_batch_contact_summary_reset(saip_batch* b) {
+	const char* fn = "saip_batch_contact_summary_reset";
+	saip_status st = need_contact(b, fn);
+	if (st || (st = need_ready(b, fn))) return st;
+	HIP_TRY(hipMemsetAsync(b->contact.summary, 0, (size_t)saip::CONTACT_SUMMARY_ROWS * b->ld * sizeof(double), b->stream));
+	return SAIP_OK;
+}
+
 // ---- the step after the path: forward dynamics + semi-implicit Euler on the resident state (saip_dynamics.hip)
 static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, const double* gravity, double damping, bool with_next_otg = false) {
 	SimParams S;
@@ -2100,6 +2305,21 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 	S.ddq = nullptr;
 	hipError_t e;
 	const bool tree = b->model->dev.is_tree != 0;  // trees: the lane-per-instance tree kernel, whatever the dof (the eight-lane step is chain-only)
+	if (b->contact.attached) {
+		// contact planes: the penalty force is re-evaluated in front of every substep (held over a control period it is unstable at
+		// useful stiffness), and the integrator takes commanded + contact torques; never fused with the next period's OTG step
+		S.substeps = 1;
+		S.tau = b->contact.tau_sim;
+		for (int s = 0; s < substeps; s++) {
+			saip_status st = contact_launch(b, saip::CONTACT_APPLY, dt);
+			if (st) return st;
+			e = saip::launch_integrate(S, tree, b->stream);
+			if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "integrate launch failed: %s", hipGetErrorString(e));
+		}
+		b->models_valid = false;
+		b->state_epoch++;
+		return SAIP_OK;
+	}
 	if (with_next_otg && S.n == 7 && !tree && otg_pair_ready(b)) {
 		// rollouts: this integration and the NEXT period's trajectory generation in one launch (they are independent)
 		e = saip::launch_integrate_otg_pair(S, b->tasks[0].otg, b->tasks[1].otg, b->B, b->ld, b->stream);
@@ -2333,6 +2553,8 @@ extern "C" saip_status saip_batch_goal_schedule_attach(saip_batch* b, int task, 
 	if (first < 0 || count <= 0 || count > T.dev.goal_comps || first > T.dev.goal_comps - count)
 		return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: components [%d, %d + %d) outside the %d goal components of task %d", fn, first, first, count, T.dev.goal_comps, task);
 	if (n_keyframes < 1 || stride < 1) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: n_keyframes >= 1 and stride >= 1 required", fn);
+	if (b->contact.attached && b->contact.sensor && b->contact.task == task && contact_rows_overlap(first, count))
+		return fail(SAIP_ERR_ORDER, "%s: rows 30..35 of task %d are written by the simulated sensor of the attached contact planes", fn, task);
 	if (mode != saip::SCHED_HOLD && mode != saip::SCHED_LINEAR) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: unknown mode %d", fn, mode);
 	per_instance = per_instance ? 1 : 0;
 	// [K][count][ld] (or [K][count]) doubles: the byte count must fit a size_t
@@ -2468,11 +2690,15 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 	// with a goal schedule attached every period starts with the launch that writes its goals, and the integration is never fused with
 	// the next period's OTG step (which would read the next goal before it is written)
 	const bool scheduled = b->n_sched > 0;
+	// with contact planes attached neither fused form is used: the contact force sits between the cycle and every integration substep
+	const bool contact = b->contact.attached;
 	auto period = [&](const bool more = false) -> saip_status {  // more: another period follows inside this call
 		if (scheduled && (st = apply_schedules(b))) return st;
+		// contact planes with the simulated sensor: the sensed wrench of this period's state, in front of the OTGs (which pass it on) and the cycle
+		if (contact && b->contact.sensor && (st = contact_launch(b, saip::CONTACT_SENSE, 0.0))) return st;
 		// no internal OTG in the stack: the cycle launch integrates the state itself when it can (eight-lane kernel, no slow path behind)
 		bool integrated = false;
-		saip_status s2 = launch_cycle(b, false, (!any_otg && b->model->n == 7) ? &sim : nullptr, &integrated);
+		saip_status s2 = launch_cycle(b, false, (!any_otg && b->model->n == 7 && !contact) ? &sim : nullptr, &integrated);
 		if (s2) {
 			b->otg_prelaunched = false;  // a failed period must not leave the next standalone cycle believing its OTG step has already run
 			return s2;

@@ -13,7 +13,11 @@
    --sampler attaches a resident rollout sampler to a 16-keyframe position + orientation schedule of the motion-force task and prints the
    event-timed mean of 50 calls each of perturb, cost and update, and beside them the host round trip they replace: rolloutSummary(), the
    NumPy perturb and update of tests/sampler_ref.py, detach and attach of the new keyframes, by wall clock around a synchronise
-   (DESIGN.md 4.11)."""
+   (DESIGN.md 4.11).
+   --contact [--contact-planes P] [--contact-sensor] [--contact-stack 2|13] [--substeps S] times, interleaved in the same run, the
+   closed-loop period without and with contact planes attached to the motion-force task (P planes: a table just under the control point
+   and P - 1 far walls), and the integrate call alone both ways; --contact-stack 13 runs config 13's closed-loop force stack
+   (DESIGN.md 4.12)."""
 import argparse
 import os
 import sys
@@ -33,11 +37,16 @@ ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--goal-schedule", choices=("hold", "linear"), default=None)
 ap.add_argument("--snapshot", action="store_true")
 ap.add_argument("--sampler", action="store_true")
+ap.add_argument("--contact", action="store_true")
+ap.add_argument("--contact-planes", type=int, default=1)
+ap.add_argument("--contact-sensor", action="store_true")
+ap.add_argument("--contact-stack", type=int, choices=(2, 13), default=2)
+ap.add_argument("--substeps", type=int, default=2)
 args = ap.parse_args()
 record = args.record_stride is not None or args.record_channels is not None or args.record_summaries
 
 for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
-    d = W.make_inputs(2, B)
+    d = W.make_inputs(args.contact_stack if args.contact else 2, B)
     robot, ctrl, tasks = controller_from_specs(d["model"].name, d["tasks"], B, device=0, disable_otg=args.no_otg)
     robot.setQ(d["q"])
     robot.setDq(np.zeros((B, 7)))
@@ -160,6 +169,38 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
             print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'}: sampler, {KF} keyframes of position + "
                   f"orientation: perturb {t['perturb']:.1f} us; cost {t['cost']:.1f} us; update {t['update']:.1f} us; host round trip (summary, NumPy perturb + "
                   f"update, detach + attach) {host:.0f} us")
+        continue
+    if args.contact:
+        P, sub = args.contact_planes, args.substeps
+        p0 = robot.position(d["tasks"][0]["link"], tuple(d["tasks"][0]["pos_in_link"]))
+        planes = np.zeros((P, B, 8))
+        planes[:] = [1.0, 0.0, 0.0, -10.0, 2.0e4, 400.0, 0.3, 1e-3]          # far walls: evaluated, never active
+        planes[0] = [0.0, 0.0, 1.0, 0.0, 2.0e4, 400.0, 0.3, 1e-3]
+        planes[0, :, 3] = p0[:, 2] + 1e-3                                     # a table 1 mm above every control point
+
+        def period_us():
+            t0 = time.perf_counter()
+            ctrl.rolloutAsync(K, 5e-4, sub, gravity=(0, 0, 0))
+            ctrl.synchronize()
+            return (time.perf_counter() - t0) / K * 1e6
+
+        def integrate_us():
+            t0 = time.perf_counter()
+            for _ in range(200):
+                ctrl.integrate(5e-4, sub, gravity=(0, 0, 0))
+            ctrl.synchronize()
+            return (time.perf_counter() - t0) / 200 * 1e6
+
+        for _ in range(args.repeats):
+            plain, plain_i = period_us(), integrate_us()
+            mf.attachContactPlanes(planes, sensor=args.contact_sensor, per_instance=True)
+            period_us()
+            with_c, with_i = period_us(), integrate_us()
+            touching = int((mf.contactReadout()["active"] > 0).sum())
+            mf.detachContactPlanes()
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} cfg{args.contact_stack} otg {'off' if args.no_otg else 'on'} substeps {sub}: "
+                  f"closed-loop period {plain:.1f} us, integrate {plain_i:.1f} us; with {P} contact plane(s), sensor {'on' if args.contact_sensor else 'off'}: "
+                  f"period {with_c:.1f} us, integrate {with_i:.1f} us ({touching} of {B} instances touching at the end)")
         continue
     if args.goal_schedule:
         def timed(calls, steps):
