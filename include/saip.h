@@ -393,6 +393,66 @@ double* saip_batch_contact_torques_device(saip_batch*);  /* [dof][ld] tau_sim of
 saip_status saip_batch_contact_summary_host(saip_batch*, double* out /* [4][B] */);  /* synchronous */
 double* saip_batch_contact_summary_device(saip_batch*);  /* [4][ld]; NULL when detached */
 saip_status saip_batch_contact_summary_reset(saip_batch*);
+/* ---- clearance monitor: link spheres against world-fixed obstacles and against each other, evaluated inside rollouts, so that a
+ * sampler can score colliding as well as reaching with no host in the loop.  One attachment per batch.
+ *   spheres   n_spheres (1..SAIP_CLEARANCE_MAX_SPHERES), batch-uniform: links[s] a saip_model_link_index value, centres[3 s ..] the centre
+ *             in that link's frame, radii[s] >= 0.  A link welded to a movable body is composed with its fixed transform here; a link
+ *             welded to the fixed base gives a constant centre.  Centres are in the frame of the robot's base, as a task's pose is.
+ *   obstacles n_obstacles (0..SAIP_CLEARANCE_MAX_OBSTACLES), each eight doubles { kind, a[3], b[3], r }: kind 0 a capsule (the segment
+ *             a-b with radius r >= 0; a == b is a sphere), kind 1 a half-space (a the unit normal, b[0] the offset; the rest is ignored).
+ *             `obstacles` is [O][8] (batch-uniform) or [O][8][B] (per_instance).
+ *   pairs     n_pairs (0..SAIP_CLEARANCE_MAX_PAIRS) pairs (s1, s2) of sphere indices, s1 != s2: pairs[2 p], pairs[2 p + 1].
+ *   margin    >= 0: distances below it are penalised.
+ * Items are numbered k = s O + o for sphere x obstacle, then S O + p for pair p; each has a signed distance (negative: penetration):
+ *   capsule     e = b - a, w = c - a, t = e.e > 0 ? clamp((w.e) / (e.e), 0, 1) : 0, |w - t e| - (r_s + r_o)
+ *   half-space  (n.c - o) - r_s                pair  |c_s1 - c_s2| - (r_s1 + r_s2)
+ * every product and sum rounded once, in that order, and summed over the items in a fixed eight-lane split (csrc/saip_clearance.h;
+ * tests/clearance_ref.py restates it in NumPy bit for bit).
+ *   readout [8][ld], of the LAST launch: the smallest distance dmin; its item k (as a double); the penalty sum_k max(0, margin - dist_k)^2;
+ *        the number of items under the margin; rows 4..6 the centre of the (first) sphere of item k; row 7 the smallest self-pair
+ *        distance (+inf without pairs).  An instance with a sphere centre that is not finite is invalid: rows 0, 2, 4..7 NaN, k = -1, count 0.
+ *   summaries [4][ld], advanced once per rollout period: min over the periods of dmin (NaN is sticky); sum dt penalty (dt = sim_dt x
+ *        substeps); periods with dmin < 0; the index, counted from the last reset, of the first such period, else -1.
+ *   while attached, every period of saip_batch_rollout_async gains exactly one launch, behind the period's integration (whichever fused
+ *        or un-fused form ran) and in front of the recorder.  saip_batch_clearance_evaluate enqueues the same launch at the resident
+ *        state and writes the readout (and the kept centres) only.  _summary_reset sets the summaries to +inf, 0, 0, -1 and the period
+ *        counter to 0 on the stream; pair it with a snapshot restore, since the attachment's arrays are configuration, scratch and
+ *        readout and not part of a state snapshot.  _set_obstacles_host replaces the table (same shape) and waits; _obstacles_device is
+ *        the resident table ([O][8] or [O][8][ld]; NULL without obstacles) for domain randomisation on the device -- what is written
+ *        there is not checked.  _centres_device is [3 S][ld] (row 3 s + e), NULL unless keep_centres.
+ *   saip_batch_clearance_add_cost: cost[i] = cost[i] + (w_penalty S1[i] + (S0[i] < d_safe ? w_collision : 0)) on the sampler's cost
+ *        array (S0, S1: summary rows 0 and 1); a NaN S0 gives a NaN cost.  A cost that is not finite is an invalid sample to
+ *        saip_batch_sampler_update, so w_collision = +inf is a hard constraint.
+ * Without an attachment every entry point enqueues exactly what it did before.  SAIP_ERR_INVALID_ARGUMENT (the message names the
+ * entry): a value that is not finite, a radius below 0, a half-space normal off unit length by more than 1e-6, an unknown kind, a link
+ * or sphere index out of range, a pair of a sphere with itself, 0 spheres, 0 obstacles together with 0 pairs, counts above the maxima,
+ * a negative margin, a NaN weight.  SAIP_ERR_ORDER: before finalize, a model-only batch, a second _attach, any other entry without an
+ * attachment, _set_obstacles_host on an attachment without obstacles, _add_cost without a sampler.  Argument and order errors are
+ * reported before the device is needed. */
+#define SAIP_CLEARANCE_MAX_SPHERES 32
+#define SAIP_CLEARANCE_MAX_OBSTACLES 16
+#define SAIP_CLEARANCE_MAX_PAIRS 64
+#define SAIP_CLEARANCE_OBSTACLE_WORDS 8
+#define SAIP_CLEARANCE_READOUT_ROWS 8
+#define SAIP_CLEARANCE_SUMMARY_ROWS 4
+#define SAIP_CLEARANCE_CAPSULE 0
+#define SAIP_CLEARANCE_HALF_SPACE 1
+saip_status saip_batch_clearance_attach(saip_batch*, int n_spheres, const int* links, const double* centres /* [S][3] */, const double* radii,
+                                        int n_obstacles, const double* obstacles, int per_instance, int n_pairs, const int* pairs /* [P][2] */,
+                                        double margin, int keep_centres);
+saip_status saip_batch_clearance_detach(saip_batch*);
+saip_status saip_batch_clearance_info(saip_batch*, int* n_spheres, int* n_obstacles, int* per_instance, int* n_pairs, double* margin,
+                                      int* keep_centres, long long* period /* monitored since the last reset */);  /* any NULL */
+saip_status saip_batch_clearance_set_obstacles_host(saip_batch*, const double* obstacles);
+double* saip_batch_clearance_obstacles_device(saip_batch*);  /* NULL when detached or without obstacles */
+saip_status saip_batch_clearance_evaluate(saip_batch*);
+saip_status saip_batch_clearance_readout_host(saip_batch*, double* out /* [8][B] */);  /* synchronous */
+double* saip_batch_clearance_readout_device(saip_batch*);    /* [8][ld]; NULL when detached */
+saip_status saip_batch_clearance_summary_host(saip_batch*, double* out /* [4][B] */);  /* synchronous */
+double* saip_batch_clearance_summary_device(saip_batch*);    /* [4][ld]; NULL when detached */
+saip_status saip_batch_clearance_summary_reset(saip_batch*);
+double* saip_batch_clearance_centres_device(saip_batch*);    /* [3 S][ld]; NULL unless keep_centres */
+saip_status saip_batch_clearance_add_cost(saip_batch*, double w_penalty, double w_collision, double d_safe);
 /* ---- rollout recorder: a per-period trajectory log and running summaries of saip_batch_rollout_async, kept on the device (the
  * reference's example loops print or log the same quantities every period: state, torques, position / orientation error).  A recorder
  * is attached to a finalized batch and stays attached across rollout calls until detached.  It observes rollout periods only

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cmath>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <array>
@@ -1110,6 +1111,78 @@ public:
 		check(saip_batch_contact_info(_batch, nullptr, nullptr, nullptr, nullptr, nullptr));  // without an attachment: that error, before the device is needed
 		pushState();
 		check(saip_batch_contact_sense(_batch));
+	}
+
+	// ---- clearance monitor: link spheres against world-fixed obstacles and against each other, inside rollouts (saip.h).  While attached
+	// every period of rolloutAsync advances clearanceSummary(); clearanceCost() adds it to the sampler's cost:
+	//   per round: ... resetRolloutRecorder(); resetClearanceSummary(); perturbGoalSchedules(); rolloutAsync(K, dt); rolloutCost(...);
+	//              clearanceCost(w_penalty); updateSampler(temperature);
+	struct ClearanceSphere {
+		std::string link;
+		std::array<double, 3> centre;  // in the link frame
+		double radius;
+	};
+	struct ClearanceInfo {
+		int n_spheres = 0, n_obstacles = 0, per_instance = 0, n_pairs = 0, keep_centres = 0;
+		double margin = 0;
+		long long period = 0;  // monitored periods since the last reset
+	};
+	// obstacles: [O][8] rows { kind, a[3], b[3], r } (kind 0 a capsule a-b of radius r, kind 1 a half-space with unit normal a and offset
+	// b[0]), or [O][8][B] with per_instance; pairs: (s1, s2) sphere indices
+	void attachClearance(const std::vector<ClearanceSphere>& spheres, const std::vector<double>& obstacles = {}, const std::vector<std::array<int, 2>>& pairs = {},
+						 double margin = 0.0, bool per_instance = false, bool keep_centres = false) {
+		const size_t per = (size_t)SAIP_CLEARANCE_OBSTACLE_WORDS * (per_instance ? (size_t)_robot->batchSize() : 1);
+		if (obstacles.size() % per) throw std::invalid_argument("attachClearance: expected [O][8] obstacles, or [O][8][B] per instance");
+		std::vector<int> links, pr;
+		std::vector<double> centres, radii;
+		for (const auto& s : spheres) {
+			links.push_back(_robot->linkIndex(s.link));
+			centres.insert(centres.end(), s.centre.begin(), s.centre.end());
+			radii.push_back(s.radius);
+		}
+		for (const auto& p : pairs) pr.insert(pr.end(), p.begin(), p.end());
+		check(saip_batch_clearance_attach(_batch, (int)spheres.size(), links.data(), centres.data(), radii.data(), (int)(obstacles.size() / per),
+										  obstacles.empty() ? nullptr : obstacles.data(), per_instance ? 1 : 0, (int)pairs.size(), pr.empty() ? nullptr : pr.data(), margin,
+										  keep_centres ? 1 : 0));
+	}
+	void detachClearance() { check(saip_batch_clearance_detach(_batch)); }
+	ClearanceInfo clearanceInfo() {
+		ClearanceInfo i;
+		check(saip_batch_clearance_info(_batch, &i.n_spheres, &i.n_obstacles, &i.per_instance, &i.n_pairs, &i.margin, &i.keep_centres, &i.period));
+		return i;
+	}
+	void setClearanceObstacles(const std::vector<double>& obstacles) {
+		const ClearanceInfo i = clearanceInfo();
+		if (obstacles.size() != (size_t)i.n_obstacles * SAIP_CLEARANCE_OBSTACLE_WORDS * (i.per_instance ? (size_t)_robot->batchSize() : 1))
+			throw std::invalid_argument("setClearanceObstacles: the shape of the attached obstacle table expected");
+		check(saip_batch_clearance_set_obstacles_host(_batch, obstacles.data()));
+	}
+	// one evaluation at the current state: clearanceReadout() (and the kept centres) only, the summaries stay
+	void evaluateClearance() {
+		clearanceInfo();  // without an attachment: that error, before the device is needed
+		pushState();
+		check(saip_batch_clearance_evaluate(_batch));
+	}
+	// [8][B]: the smallest signed distance, its item k (s O + o, then S O + p), the penalty, the items under the margin, the centre of the
+	// (first) sphere of item k (3), the smallest self-pair distance -- of the last launch; waits for the stream
+	std::vector<double> clearanceReadout() {
+		std::vector<double> out((size_t)SAIP_CLEARANCE_READOUT_ROWS * _robot->batchSize());
+		check(saip_batch_clearance_readout_host(_batch, out.data()));
+		return out;
+	}
+	// [4][B]: min over the monitored periods of the distance, sum dt * penalty, periods in collision, the first of them or -1; waits for the stream
+	std::vector<double> clearanceSummary() {
+		std::vector<double> out((size_t)SAIP_CLEARANCE_SUMMARY_ROWS * _robot->batchSize());
+		check(saip_batch_clearance_summary_host(_batch, out.data()));
+		return out;
+	}
+	// pair it with restoreState: the summaries are not part of a snapshot
+	void resetClearanceSummary() { check(saip_batch_clearance_summary_reset(_batch)); }
+	double* clearanceObstaclesDevice() { return saip_batch_clearance_obstacles_device(_batch); }
+	double* clearanceCentresDevice() { return saip_batch_clearance_centres_device(_batch); }  // [3 S][ld]; nullptr unless keep_centres
+	// cost += w_penalty * summary penalty + (min distance < d_safe ? w_collision : 0), after rolloutCost(); the default makes collision a hard constraint
+	void clearanceCost(double w_penalty, double w_collision = std::numeric_limits<double>::infinity(), double d_safe = 0.0) {
+		check(saip_batch_clearance_add_cost(_batch, w_penalty, w_collision, d_safe));
 	}
 
 private:

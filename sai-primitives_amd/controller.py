@@ -1544,6 +1544,107 @@ class RobotController:
         self._push_state()
         self._call("saip_batch_contact_sense")
 
+    # -- clearance monitor: link spheres against world-fixed obstacles and against each other, inside rollouts (saip.h)
+    @staticmethod
+    def _clearance_obstacles(obstacles, per_instance, B, who, n_obstacles=None):
+        a = np.asarray(obstacles, float)
+        W, O = capi.SAIP_CLEARANCE_OBSTACLE_WORDS, "O" if n_obstacles is None else n_obstacles
+        if per_instance:
+            if a.ndim != 3 or a.shape[1:] != (B, W) or (n_obstacles is not None and a.shape[0] != n_obstacles):
+                raise ValueError(f"{who}: per-instance obstacles of shape ({O}, {B}, {W}) expected, got {a.shape}")
+            return np.ascontiguousarray(a.transpose(0, 2, 1))
+        if a.ndim != 2 or a.shape[1] != W or (n_obstacles is not None and a.shape[0] != n_obstacles):
+            raise ValueError(f"{who}: obstacles of shape ({O}, {W}) expected, got {a.shape}")
+        return np.ascontiguousarray(a)
+
+    def attachClearance(self, spheres, obstacles=None, pairs=None, margin=0.0, per_instance=False, keep_centres=False):
+        """watch the clearance of the robot during rollouts.  spheres: up to 32 of (link name, centre in the link frame (3), radius);
+        obstacles: up to 16 rows { kind, a[3], b[3], r } -- kind 0 a capsule (segment a-b, radius r; a == b a sphere), kind 1 a half-space
+        (a the unit normal, b[0] the offset) -- of shape (O, 8), or (O, B, 8) with per_instance; pairs: up to 64 (s1, s2) of sphere
+        indices checked against each other; margin >= 0: distances below it are penalised.  While attached every period of
+        rolloutAsync() advances clearanceSummary(); clearanceCost() adds it to the sampler's cost."""
+        spheres = list(spheres)
+        links = np.empty(len(spheres), np.int32)
+        centres, radii = np.zeros((len(spheres), 3)), np.zeros(len(spheres))
+        for s, sph in enumerate(spheres):
+            if len(sph) != 3:
+                raise ValueError(f"attachClearance: sphere {s}: (link, centre, radius) expected")
+            links[s] = self._robot.linkIndex(sph[0])
+            if links[s] < 0:
+                raise ValueError(f"attachClearance: sphere {s}: unknown link [{sph[0]}]")
+            c = np.asarray(sph[1], float).reshape(-1)
+            if c.shape != (3,):
+                raise ValueError(f"attachClearance: sphere {s}: a centre of shape (3,) expected, got {c.shape}")
+            centres[s], radii[s] = c, float(sph[2])
+        a = None if obstacles is None else self._clearance_obstacles(obstacles, per_instance, self.batch_size, "attachClearance")
+        p = None if pairs is None else np.ascontiguousarray(pairs, np.int32)
+        if p is not None and p.size and (p.ndim != 2 or p.shape[1] != 2):
+            raise ValueError(f"attachClearance: pairs of shape (P, 2) expected, got {p.shape}")
+        n_o, n_p = 0 if a is None else a.shape[0], 0 if p is None else p.size // 2
+        ip = C.POINTER(C.c_int)
+        self._call("saip_batch_clearance_attach", len(spheres), links.ctypes.data_as(ip), _dptr(centres), _dptr(radii), n_o, None if n_o == 0 else _dptr(a),
+                   int(bool(per_instance)), n_p, None if n_p == 0 else p.ctypes.data_as(ip), float(margin), int(bool(keep_centres)))
+        self._clearance_pairs = np.zeros((0, 2), int) if n_p == 0 else p.reshape(-1, 2).astype(int)
+
+    def clearanceInfo(self):
+        """dict n_spheres, n_obstacles, per_instance, n_pairs, margin, keep_centres, period (monitored periods since the last reset)"""
+        v = [C.c_int(0) for _ in range(5)]
+        m, per = C.c_double(0), C.c_longlong(0)
+        self._call("saip_batch_clearance_info", C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(v[3]), C.byref(m), C.byref(v[4]), C.byref(per))
+        return dict(n_spheres=v[0].value, n_obstacles=v[1].value, per_instance=bool(v[2].value), n_pairs=v[3].value, margin=m.value,
+                    keep_centres=bool(v[4].value), period=per.value)
+
+    def detachClearance(self):
+        self._call("saip_batch_clearance_detach")
+
+    def setClearanceObstacles(self, obstacles):
+        """replace the obstacle table (same shape as attached); takes effect with the next launch"""
+        info = self.clearanceInfo()
+        a = self._clearance_obstacles(obstacles, info["per_instance"], self.batch_size, "setClearanceObstacles", info["n_obstacles"])
+        self._call("saip_batch_clearance_set_obstacles_host", _dptr(a))
+
+    def evaluateClearance(self):
+        """enqueue one evaluation at the current state: clearanceReadout() (and the kept centres) only, the summaries stay"""
+        self.clearanceInfo()  # without an attachment: that error, before the device is needed
+        self._push_state()
+        self._call("saip_batch_clearance_evaluate")
+
+    def clearanceReadout(self):
+        """dict of the last clearance launch: distance (B,) the smallest signed distance, item (B,) its number, closest: per instance
+        ("obstacle", sphere, obstacle), ("pair", s1, s2) or None (invalid instance), penalty (B,), under_margin (B,), point (B, 3) the
+        centre of the closest item's (first) sphere, pair_distance (B,) the smallest self-pair distance (waits for the engine stream)"""
+        info = self.clearanceInfo()
+        out = np.empty((capi.SAIP_CLEARANCE_READOUT_ROWS, self.batch_size))
+        self._call("saip_batch_clearance_readout_host", _dptr(out))
+        S, O = info["n_spheres"], info["n_obstacles"]
+        item = out[1].astype(int)
+        closest = [None if k < 0 else ("obstacle", int(k) // O, int(k) % O) if k < S * O else ("pair",) + tuple(int(x) for x in self._clearance_pairs[k - S * O])
+                   for k in item]
+        return dict(distance=out[0].copy(), item=item, closest=closest, penalty=out[2].copy(), under_margin=out[3].astype(int), point=out[4:7].T.copy(),
+                    pair_distance=out[7].copy())
+
+    def clearanceSummary(self):
+        """dict over the monitored periods: min_distance (B,) (NaN once an instance was invalid), penalty (B,) sum dt * penalty,
+        periods_in_collision (B,), first_collision (B,) the index of the first period with a negative distance, else -1 (waits for the
+        engine stream)"""
+        self.clearanceInfo()
+        out = np.empty((capi.SAIP_CLEARANCE_SUMMARY_ROWS, self.batch_size))
+        self._call("saip_batch_clearance_summary_host", _dptr(out))
+        return dict(min_distance=out[0].copy(), penalty=out[1].copy(), periods_in_collision=out[2].astype(int), first_collision=out[3].astype(int))
+
+    def resetClearanceSummary(self):
+        """summaries back to +inf, 0, 0, -1 and the period counter to 0; pair it with restoreState (the summaries are not part of a snapshot)"""
+        self._call("saip_batch_clearance_summary_reset")
+
+    def clearanceCentresDevice(self):
+        """device pointer of the (3 S, ld) sphere centres of the last launch; None unless attached with keep_centres"""
+        return capi.lib().saip_batch_clearance_centres_device(self._h)
+
+    def clearanceCost(self, w_penalty, w_collision=float("inf"), d_safe=0.0):
+        """cost += w_penalty * summary penalty + (min_distance < d_safe ? w_collision : 0) on the device, after rolloutCost(); an infinite
+        cost is an invalid sample to updateSampler(), so the default w_collision makes collision a hard constraint"""
+        self._call("saip_batch_clearance_add_cost", float(w_penalty), float(w_collision), float(d_safe))
+
     def rewindGoalSchedules(self):
         """the period counter of the tasks' goal schedules (task.setGoalSchedule) back to 0: the next rollout starts at the first keyframe"""
         self._call("saip_batch_goal_schedule_rewind")

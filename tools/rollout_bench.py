@@ -17,7 +17,10 @@
    --contact [--contact-planes P] [--contact-sensor] [--contact-stack 2|13] [--substeps S] times, interleaved in the same run, the
    closed-loop period without and with contact planes attached to the motion-force task (P planes: a table just under the control point
    and P - 1 far walls), and the integrate call alone both ways; --contact-stack 13 runs config 13's closed-loop force stack
-   (DESIGN.md 4.12)."""
+   (DESIGN.md 4.12).
+   --clearance [--clearance-spheres S] [--clearance-obstacles O] [--clearance-pairs P] times, interleaved in the same run, the closed-loop
+   period without and with a clearance monitor of S link spheres, O batch-uniform obstacles (capsules, every fourth a half-space) and P self
+   pairs, and prints the event-timed mean of 200 back-to-back evaluations alone."""
 import argparse
 import os
 import sys
@@ -42,6 +45,10 @@ ap.add_argument("--contact-planes", type=int, default=1)
 ap.add_argument("--contact-sensor", action="store_true")
 ap.add_argument("--contact-stack", type=int, choices=(2, 13), default=2)
 ap.add_argument("--substeps", type=int, default=2)
+ap.add_argument("--clearance", action="store_true")
+ap.add_argument("--clearance-spheres", type=int, default=8)
+ap.add_argument("--clearance-obstacles", type=int, default=4)
+ap.add_argument("--clearance-pairs", type=int, default=0)
 args = ap.parse_args()
 record = args.record_stride is not None or args.record_channels is not None or args.record_summaries
 
@@ -201,6 +208,56 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
             print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} cfg{args.contact_stack} otg {'off' if args.no_otg else 'on'} substeps {sub}: "
                   f"closed-loop period {plain:.1f} us, integrate {plain_i:.1f} us; with {P} contact plane(s), sensor {'on' if args.contact_sensor else 'off'}: "
                   f"period {with_c:.1f} us, integrate {with_i:.1f} us ({touching} of {B} instances touching at the end)")
+        continue
+    if args.clearance:
+        import ctypes as C
+        S, O, P = args.clearance_spheres, args.clearance_obstacles, args.clearance_pairs
+        rng = np.random.default_rng(0)
+        names = [f"link{i}" for i in range(1, 8)] + ["end-effector"]
+        spheres = [(names[s % 8], rng.uniform(-0.05, 0.05, 3), 0.05) for s in range(S)]
+        obst = np.zeros((O, 8))
+        obst[:, 1:4] = rng.uniform(-0.8, 0.8, (O, 3))
+        obst[:, 4:7] = obst[:, 1:4] + rng.uniform(-0.3, 0.3, (O, 3))
+        obst[:, 7] = 0.03
+        obst[3::4] = [1.0, 0.0, 0.0, 1.0, -0.2, 0.0, 0.0, 0.0]               # every fourth: a floor
+        pairs = [(p % S, (p % S + 1 + p // S) % S) for p in range(P)]
+        hip = C.CDLL("libamdhip64.so")
+        vp = C.c_void_p
+        hip.hipEventCreate.argtypes, hip.hipEventRecord.argtypes, hip.hipEventSynchronize.argtypes = [C.POINTER(vp)], [vp, vp], [vp]
+        hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), vp, vp]
+        stream = ctrl.devicePointers()["stream"]
+        ev = [vp(), vp()]
+        for e in ev:
+            assert hip.hipEventCreate(C.byref(e)) == 0
+
+        def period_us():
+            t0 = time.perf_counter()
+            ctrl.rolloutAsync(K, 5e-4, args.substeps, gravity=(0, 0, 0))
+            ctrl.synchronize()
+            return (time.perf_counter() - t0) / K * 1e6
+
+        def evaluate_us(reps=200):
+            ctrl.evaluateClearance()
+            ctrl.synchronize()
+            assert hip.hipEventRecord(ev[0], stream) == 0
+            for _ in range(reps):
+                ctrl._call("saip_batch_clearance_evaluate")
+            assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
+            ms = C.c_float()
+            assert hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
+            return ms.value / reps * 1e3
+
+        for _ in range(args.repeats):
+            plain = period_us()
+            ctrl.attachClearance(spheres, obst if O else None, pairs or None, margin=0.05)
+            period_us()
+            with_c, alone = period_us(), evaluate_us()
+            under = int((ctrl.clearanceSummary()["min_distance"] < 0.05).sum())
+            ctrl.detachClearance()
+            again = period_us()
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {args.substeps}: "
+                  f"closed-loop period {plain:.1f} us; with a clearance monitor of {S} spheres, {O} obstacles, {P} pairs {with_c:.1f} us; without it again "
+                  f"{again:.1f} us; one evaluation alone {alone:.2f} us ({under} of {B} instances under the margin)")
         continue
     if args.goal_schedule:
         def timed(calls, steps):
