@@ -393,6 +393,44 @@ double* saip_batch_contact_torques_device(saip_batch*);  /* [dof][ld] tau_sim of
 saip_status saip_batch_contact_summary_host(saip_batch*, double* out /* [4][B] */);  /* synchronous */
 double* saip_batch_contact_summary_device(saip_batch*);  /* [4][ld]; NULL when detached */
 saip_status saip_batch_contact_summary_reset(saip_batch*);
+/* ---- contact patches: multi-point contact with a wrench sensor.  A patch is n_points (1..SAIP_CONTACT_PATCH_MAX_POINTS) offsets r_i in
+ * the control frame of a motion-force task (`points`, [n][3]), carried by that task's body, against the patch's own planes (format, checks
+ * and layouts of saip_batch_contact_attach).  Up to SAIP_CONTACT_PATCH_MAX patches per batch, on different tasks (the two arms of a tree),
+ * never together with the single-point attachment above: SAIP_ERR_ORDER from whichever _attach comes second, from a second patch on a
+ * task and from a third patch.  Per point p_i = x_c + R_c r_i and f_i as above; an instance has eight slots, the unused ones hold exact
+ * zeros, and every sum over the slots has the shape v[i] += v[i + off], off = 4, 2, 1 (csrc/saip_contact_patch.h; tests/contact_patch_ref.py
+ * restates it bit for bit):  F = sum f_i,  M = sum (p_i - x_c) x f_i,  n_touch = points with an active plane.
+ *   per SUBSTEP of saip_batch_rollout_async / saip_batch_integrate one launch for all patches (in place of the single-point launch) writes
+ *        tau_sim[j] = ((tau[j] is NaN ? 0 : tau[j]) + ext_0[j]) + ext_1[j], ext_k[j] = sum_i (J_v(p_i)^T f_i)[j] of patch k (in attach
+ *        order), added only for ancestor joints of the patch's body and only when a point of it touches.  One point gives the numbers of
+ *        the single-point attachment.  The fused forms of a rollout period are not used while a patch is attached.
+ *   sensor != 0: as above, with world F_w = -F, m_w = -M in place of the single point's wrench.  A rollout period enqueues the sensing
+ *        launch only if some patch has the sensor, and it evaluates those patches only; saip_batch_contact_patch_sense enqueues the same
+ *        launch, so { _contact_patch_sense, saip_batch_step_async, saip_batch_integrate } leaves the bits of a rollout period.  The
+ *        schedule-versus-sensor rule on rows 30..35 holds per task.
+ *   readout [20][ld] per patch, of the LAST launch that evaluated it: F 3, M 3 (about x_c, world), the smallest d over the points, n_touch,
+ *        the lowest point index that attains it, x_c 3, then the normal-force sum of each of the eight slots.
+ *   summaries [6][ld] per patch, advanced by every substep: sum dt sum f_n, max |F|, max penetration, substeps with n_touch > 0, max |M|,
+ *        substeps in full contact (n_touch == n_points).  They are not part of a state snapshot: a restore pairs with _summary_reset.
+ * `task` selects the patch; -1 is every patch for _detach and _summary_reset and the first attached one elsewhere.  Errors as for
+ * saip_batch_contact_attach, plus SAIP_ERR_INVALID_ARGUMENT for n_points outside 1..8, NULL points and a point that is not finite, and
+ * SAIP_ERR_ORDER for a task without a patch and for _sense when no patch has the sensor. */
+#define SAIP_CONTACT_PATCH_MAX_POINTS 8
+#define SAIP_CONTACT_PATCH_MAX 2
+#define SAIP_CONTACT_PATCH_READOUT_ROWS 20
+#define SAIP_CONTACT_PATCH_SUMMARY_ROWS 6
+saip_status saip_batch_contact_patch_attach(saip_batch*, int task, int n_points, const double* points /* [n][3] */, int n_planes, const double* planes, int per_instance, int sensor);
+saip_status saip_batch_contact_patch_detach(saip_batch*, int task /* -1 = all */);
+saip_status saip_batch_contact_patch_info(saip_batch*, int task, int* n_patches, int* n_points, int* n_planes, int* per_instance, int* sensor, double* points /* [8][3] */);  /* any NULL */
+saip_status saip_batch_contact_patch_set_planes_host(saip_batch*, int task, const double* planes);
+double* saip_batch_contact_patch_planes_device(saip_batch*, int task);   /* NULL when the task has no patch */
+saip_status saip_batch_contact_patch_sense(saip_batch*);
+saip_status saip_batch_contact_patch_readout_host(saip_batch*, int task, double* out /* [20][B] */);  /* synchronous */
+double* saip_batch_contact_patch_readout_device(saip_batch*, int task);  /* [20][ld] */
+saip_status saip_batch_contact_patch_summary_host(saip_batch*, int task, double* out /* [6][B] */);  /* synchronous */
+double* saip_batch_contact_patch_summary_device(saip_batch*, int task);  /* [6][ld] */
+saip_status saip_batch_contact_patch_summary_reset(saip_batch*, int task /* -1 = all */);
+double* saip_batch_contact_patch_torques_device(saip_batch*);  /* [dof][ld] tau_sim of the last integrated substep; NULL without a patch */
 /* ---- clearance monitor: link spheres against world-fixed obstacles and against each other, evaluated inside rollouts, so that a
  * sampler can score colliding as well as reaching with no host in the loop.  One attachment per batch.
  *   spheres   n_spheres (1..SAIP_CLEARANCE_MAX_SPHERES), batch-uniform: links[s] a saip_model_link_index value, centres[3 s ..] the centre

@@ -431,6 +431,70 @@ public:
 		contactMine();
 		check(saip_batch_contact_summary_reset(_batch));
 	}
+	// ---- contact patches (saip.h): 1..8 contact points (`points`, [n][3], in this task's control frame) on this task's body against the
+	// patch's own planes (format of attachContactPlanes), the net force and moment fed to the integrator and to the simulated sensor.  Up
+	// to two patches per controller, on different motion-force tasks; never together with attachContactPlanes.
+	void attachContactPatch(const std::vector<double>& points, const std::vector<double>& planes, int n_planes, bool sensor = true, bool per_instance = false) {
+		need();
+		const size_t cols = per_instance ? (size_t)saip_batch_size(_batch) : 1;
+		if (points.empty() || points.size() % 3 != 0) throw std::invalid_argument("attachContactPatch: expected [n][3] points");
+		if (n_planes < 1 || planes.size() != (size_t)n_planes * SAIP_CONTACT_PLANE_WORDS * cols)
+			throw std::invalid_argument("attachContactPatch: expected [n_planes][8] planes, or [n_planes][8][B] per instance");
+		check(saip_batch_contact_patch_attach(_batch, _id, (int)(points.size() / 3), points.data(), n_planes, planes.data(), per_instance ? 1 : 0, sensor ? 1 : 0));
+	}
+	void detachContactPatch() {
+		need();
+		check(saip_batch_contact_patch_detach(_batch, _id));
+	}
+	void setContactPatchPlanes(const std::vector<double>& planes) {
+		need();
+		int np = 0, per = 0;
+		check(saip_batch_contact_patch_info(_batch, _id, nullptr, nullptr, &np, &per, nullptr, nullptr));
+		if (planes.size() != (size_t)np * SAIP_CONTACT_PLANE_WORDS * (per ? (size_t)saip_batch_size(_batch) : 1))
+			throw std::invalid_argument("setContactPatchPlanes: the shape of the attached plane table expected");
+		check(saip_batch_contact_patch_set_planes_host(_batch, _id, planes.data()));
+	}
+	int contactPatchPoints() {  // the number of points of this task's patch
+		need();
+		int n = 0;
+		check(saip_batch_contact_patch_info(_batch, _id, nullptr, &n, nullptr, nullptr, nullptr, nullptr));
+		return n;
+	}
+	double* contactPatchPlanesDevice() {
+		need();
+		return saip_batch_contact_patch_planes_device(_batch, _id);
+	}
+	double* contactPatchReadoutDevice() {
+		need();
+		return saip_batch_contact_patch_readout_device(_batch, _id);
+	}
+	double* contactPatchSummaryDevice() {
+		need();
+		return saip_batch_contact_patch_summary_device(_batch, _id);
+	}
+	double* contactPatchTorquesDevice() {
+		need();
+		return saip_batch_contact_patch_torques_device(_batch);
+	}
+	// [20][B]: net force on the robot (world) 3, net moment about the control point 3, smallest signed distance, points touching, index of the
+	// deepest point, control point 3, normal-force sum of each of the eight point slots -- of the last launch; waits for the stream
+	std::vector<double> contactPatchReadout() {
+		need();
+		std::vector<double> out((size_t)SAIP_CONTACT_PATCH_READOUT_ROWS * saip_batch_size(_batch));
+		check(saip_batch_contact_patch_readout_host(_batch, _id, out.data()));
+		return out;
+	}
+	// [6][B]: sum dt * normal force, max |F|, max penetration, substeps in contact, max |M|, substeps in full contact; waits for the stream
+	std::vector<double> contactPatchSummary() {
+		need();
+		std::vector<double> out((size_t)SAIP_CONTACT_PATCH_SUMMARY_ROWS * saip_batch_size(_batch));
+		check(saip_batch_contact_patch_summary_host(_batch, _id, out.data()));
+		return out;
+	}
+	void resetContactPatchSummary() {  // pairs with a snapshot restore: the summaries are not part of a snapshot
+		need();
+		check(saip_batch_contact_patch_summary_reset(_batch, _id));
+	}
 	std::vector<double> samplerNominal() {
 		need();
 		check(saip_batch_sampler_info(_batch, _id, nullptr, nullptr, nullptr, nullptr));
@@ -1111,6 +1175,12 @@ public:
 		check(saip_batch_contact_info(_batch, nullptr, nullptr, nullptr, nullptr, nullptr));  // without an attachment: that error, before the device is needed
 		pushState();
 		check(saip_batch_contact_sense(_batch));
+	}
+	// the simulated sensors of the attached contact patches (task->attachContactPatch): the same, for { contactPatchSense, stepAsync, integrate }
+	void contactPatchSense() {
+		check(saip_batch_contact_patch_info(_batch, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));  // without a patch: that error first
+		pushState();
+		check(saip_batch_contact_patch_sense(_batch));
 	}
 
 	// ---- clearance monitor: link spheres against world-fixed obstacles and against each other, inside rollouts (saip.h).  While attached

@@ -7,8 +7,8 @@ import subprocess
 
 _DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_DIR, "libsaip.so")
-SOURCES = ["csrc/saip_engine.cpp", "csrc/saip_comm.cpp", "csrc/saip_kernel_wg.hip", "csrc/saip_kernel_lane.hip", "csrc/saip_kernel_lane_lean.hip", "csrc/saip_kernel_oct.hip", "csrc/saip_kernel_octjf.hip", "csrc/saip_kernel_wave.hip", "csrc/saip_otg.hip", "csrc/saip_dynamics.hip", "csrc/saip_dynamics_oct.hip", "csrc/saip_task_diag.hip", "csrc/saip_model_query.hip", "csrc/saip_rollout_record.hip", "csrc/saip_goal_schedule.hip", "csrc/saip_state_snapshot.hip", "csrc/saip_sampler.hip", "csrc/saip_contact.hip", "csrc/saip_clearance.hip"]
-HEADERS = ["csrc/saip_device.h", "csrc/saip_cycle_plan.h", "csrc/saip_state_snapshot.h", "csrc/saip_sampler.h", "csrc/saip_contact.h", "csrc/saip_clearance.h", "csrc/saip_law.h", "csrc/saip_wg_linalg.h", "csrc/saip_wg_cycle.h", "csrc/saip_fk.h", "csrc/saip_oct_common.h", "csrc/saip_wave_prims.h", "csrc/saip_dynamics_oct_body.h", "csrc/saip_otg3.h", "csrc/saip_otg3_step1.h", "csrc/saip_otg3_step2.h", "csrc/saip_rbd.h", "../include/saip.h"]
+SOURCES = ["csrc/saip_engine.cpp", "csrc/saip_comm.cpp", "csrc/saip_kernel_wg.hip", "csrc/saip_kernel_lane.hip", "csrc/saip_kernel_lane_lean.hip", "csrc/saip_kernel_oct.hip", "csrc/saip_kernel_octjf.hip", "csrc/saip_kernel_wave.hip", "csrc/saip_otg.hip", "csrc/saip_dynamics.hip", "csrc/saip_dynamics_oct.hip", "csrc/saip_task_diag.hip", "csrc/saip_model_query.hip", "csrc/saip_rollout_record.hip", "csrc/saip_goal_schedule.hip", "csrc/saip_state_snapshot.hip", "csrc/saip_sampler.hip", "csrc/saip_contact.hip", "csrc/saip_contact_patch.hip", "csrc/saip_clearance.hip"]
+HEADERS = ["csrc/saip_device.h", "csrc/saip_cycle_plan.h", "csrc/saip_state_snapshot.h", "csrc/saip_sampler.h", "csrc/saip_contact.h", "csrc/saip_contact_patch.h", "csrc/saip_clearance.h", "csrc/saip_law.h", "csrc/saip_wg_linalg.h", "csrc/saip_wg_cycle.h", "csrc/saip_fk.h", "csrc/saip_oct_common.h", "csrc/saip_wave_prims.h", "csrc/saip_dynamics_oct_body.h", "csrc/saip_otg3.h", "csrc/saip_otg3_step1.h", "csrc/saip_otg3_step2.h", "csrc/saip_rbd.h", "../include/saip.h"]
 
 SAIP_OK, SAIP_ERR_INVALID_ARGUMENT, SAIP_ERR_UNSUPPORTED, SAIP_ERR_NO_DEVICE, SAIP_ERR_DEVICE, SAIP_ERR_ORDER = range(6)
 SAIP_MAX_QUERY_FRAMES = 8
@@ -18,6 +18,7 @@ SAIP_RECORD_SUMMARY_ROWS = 8
 SAIP_SCHEDULE_HOLD, SAIP_SCHEDULE_LINEAR = 0, 1
 SAIP_SNAPSHOT_SOA, SAIP_SNAPSHOT_GROUPED, SAIP_SNAPSHOT_AOS = 0, 1, 2
 SAIP_CONTACT_MAX_PLANES, SAIP_CONTACT_PLANE_WORDS, SAIP_CONTACT_READOUT_ROWS, SAIP_CONTACT_SUMMARY_ROWS = 4, 8, 8, 4
+SAIP_CONTACT_PATCH_MAX_POINTS, SAIP_CONTACT_PATCH_MAX, SAIP_CONTACT_PATCH_READOUT_ROWS, SAIP_CONTACT_PATCH_SUMMARY_ROWS = 8, 2, 20, 6
 SAIP_CLEARANCE_MAX_SPHERES, SAIP_CLEARANCE_MAX_OBSTACLES, SAIP_CLEARANCE_MAX_PAIRS = 32, 16, 64
 SAIP_CLEARANCE_OBSTACLE_WORDS, SAIP_CLEARANCE_READOUT_ROWS, SAIP_CLEARANCE_SUMMARY_ROWS = 8, 8, 4
 SAIP_CLEARANCE_CAPSULE, SAIP_CLEARANCE_HALF_SPACE = 0, 1
@@ -212,6 +213,18 @@ def lib():
         "saip_batch_contact_summary_host": (C.c_int, [vp, dp]),
         "saip_batch_contact_summary_device": (vp, [vp]),
         "saip_batch_contact_summary_reset": (C.c_int, [vp]),
+        "saip_batch_contact_patch_attach": (C.c_int, [vp, C.c_int, C.c_int, dp, C.c_int, dp, C.c_int, C.c_int]),
+        "saip_batch_contact_patch_detach": (C.c_int, [vp, C.c_int]),
+        "saip_batch_contact_patch_info": (C.c_int, [vp, C.c_int, ip, ip, ip, ip, ip, dp]),
+        "saip_batch_contact_patch_set_planes_host": (C.c_int, [vp, C.c_int, dp]),
+        "saip_batch_contact_patch_planes_device": (vp, [vp, C.c_int]),
+        "saip_batch_contact_patch_sense": (C.c_int, [vp]),
+        "saip_batch_contact_patch_readout_host": (C.c_int, [vp, C.c_int, dp]),
+        "saip_batch_contact_patch_readout_device": (vp, [vp, C.c_int]),
+        "saip_batch_contact_patch_torques_device": (vp, [vp]),
+        "saip_batch_contact_patch_summary_host": (C.c_int, [vp, C.c_int, dp]),
+        "saip_batch_contact_patch_summary_device": (vp, [vp, C.c_int]),
+        "saip_batch_contact_patch_summary_reset": (C.c_int, [vp, C.c_int]),
         "saip_batch_clearance_attach": (C.c_int, [vp, C.c_int, ip, dp, dp, C.c_int, dp, C.c_int, C.c_int, ip, C.c_double, C.c_int]),
         "saip_batch_clearance_detach": (C.c_int, [vp]),
         "saip_batch_clearance_info": (C.c_int, [vp, ip, ip, ip, ip, dp, ip, C.POINTER(C.c_longlong)]),

@@ -925,6 +925,77 @@ class MotionForceTask(_Task):
         self._contact_info()
         self._need_ctrl()._call("saip_batch_contact_summary_reset")
 
+    # -- contact patches: up to eight contact points on this task's body, net force and moment, a wrench sensor (saip.h)
+    def attachContactPatch(self, points, planes, sensor=True, per_instance=False):
+        """multi-point contact: `points` (n, 3), 1..8 offsets in this task's control frame, against the patch's own 1..4 planes (format of
+        attachContactPlanes: (P, 8), or (P, B, 8) with per_instance).  While attached, integrate() and rolloutAsync() add the net contact
+        torques in front of every substep; with `sensor` a rollout period starts by writing the sensed force AND moment of the patch
+        (contactPatchSense() does the same for a host-driven loop).  Up to two patches per controller, on different tasks; never
+        together with attachContactPlanes."""
+        ctrl = self._need_ctrl()
+        a = self._contact_planes(planes, per_instance, ctrl.batch_size, "attachContactPatch")
+        pts = np.ascontiguousarray(np.asarray(points, float))
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError(f"attachContactPatch: points of shape (n, 3) expected, got {pts.shape}")
+        ctrl._call("saip_batch_contact_patch_attach", self._id, pts.shape[0], _dptr(pts), a.shape[0], _dptr(a), int(bool(per_instance)), int(bool(sensor)))
+
+    def contactPatchInfo(self):
+        """dict n_patches (of the controller), n_points, n_planes, per_instance, sensor, points (n, 3)"""
+        v = [C.c_int(0) for _ in range(5)]
+        pts = np.zeros((capi.SAIP_CONTACT_PATCH_MAX_POINTS, 3))
+        self._need_ctrl()._call("saip_batch_contact_patch_info", self._id, *(C.byref(x) for x in v), _dptr(pts))
+        return dict(n_patches=v[0].value, n_points=v[1].value, n_planes=v[2].value, per_instance=bool(v[3].value), sensor=bool(v[4].value),
+                    points=pts[:v[1].value].copy())
+
+    def detachContactPatch(self):
+        self._need_ctrl()._call("saip_batch_contact_patch_detach", self._id)
+
+    def setContactPatchPlanes(self, planes):
+        """replace the plane table of this task's patch (same shape as attached); takes effect with the next launch"""
+        info = self.contactPatchInfo()
+        ctrl = self._need_ctrl()
+        a = self._contact_planes(planes, info["per_instance"], ctrl.batch_size, "setContactPatchPlanes", info["n_planes"])
+        ctrl._call("saip_batch_contact_patch_set_planes_host", self._id, _dptr(a))
+
+    def contactPatchPlanesDevice(self):
+        """device pointer of the patch's resident plane table, (P, 8) or (P, 8, ld); None without a patch"""
+        return capi.lib().saip_batch_contact_patch_planes_device(self._need_ctrl()._h, self._id)
+
+    def contactPatchReadoutDevice(self):
+        """device pointer of the patch's readout (20, ld); None without a patch"""
+        return capi.lib().saip_batch_contact_patch_readout_device(self._need_ctrl()._h, self._id)
+
+    def contactPatchSummaryDevice(self):
+        """device pointer of the patch's summaries (6, ld); None without a patch"""
+        return capi.lib().saip_batch_contact_patch_summary_device(self._need_ctrl()._h, self._id)
+
+    def contactPatchTorquesDevice(self):
+        """device pointer of (dof, ld) commanded + contact torques of the last integrated substep (shared by the patches); None without one"""
+        return capi.lib().saip_batch_contact_patch_torques_device(self._need_ctrl()._h)
+
+    def contactPatchReadout(self):
+        """dict of the last launch that evaluated this patch: force (B, 3) and moment (B, 3) about the control point on the robot, world
+        frame; distance (B,) the smallest signed distance over the points; n_touch (B,) points in contact; deepest (B,) the index of the
+        deepest point; control_point (B, 3); normal_forces (B, 8) per point slot (waits for the engine stream)"""
+        ctrl = self._need_ctrl()
+        out = np.empty((capi.SAIP_CONTACT_PATCH_READOUT_ROWS, ctrl.batch_size))
+        ctrl._call("saip_batch_contact_patch_readout_host", self._id, _dptr(out))
+        return dict(force=out[0:3].T.copy(), moment=out[3:6].T.copy(), distance=out[6].copy(), n_touch=out[7].astype(int), deepest=out[8].astype(int),
+                    control_point=out[9:12].T.copy(), normal_forces=out[12:20].T.copy())
+
+    def contactPatchSummary(self):
+        """dict of the running summaries over the integrated substeps: impulse, max_force, max_penetration, substeps_in_contact, max_moment,
+        substeps_in_full_contact, each (B,) (waits for the engine stream)"""
+        ctrl = self._need_ctrl()
+        out = np.empty((capi.SAIP_CONTACT_PATCH_SUMMARY_ROWS, ctrl.batch_size))
+        ctrl._call("saip_batch_contact_patch_summary_host", self._id, _dptr(out))
+        return dict(impulse=out[0].copy(), max_force=out[1].copy(), max_penetration=out[2].copy(), substeps_in_contact=out[3].astype(int),
+                    max_moment=out[4].copy(), substeps_in_full_contact=out[5].astype(int))
+
+    def resetContactPatchSummary(self):
+        """zero this patch's summaries on the stream (what goes with a snapshot restore: the summaries are not part of a snapshot)"""
+        self._need_ctrl()._call("saip_batch_contact_patch_summary_reset", self._id)
+
     def updateSensedForceAndMoment(self, sensed_force_sensor_frame, sensed_moment_sensor_frame):  # MotionForceTask.cpp:805-828
         self._set_field(30, 3, sensed_force_sensor_frame, "updateSensedForceAndMoment (force)")
         self._set_field(33, 3, sensed_moment_sensor_frame, "updateSensedForceAndMoment (moment)")
@@ -1543,6 +1614,13 @@ class RobotController:
         self._call("saip_batch_contact_info", None, None, None, None, None)  # without an attachment: that error, before the device is needed
         self._push_state()
         self._call("saip_batch_contact_sense")
+
+    def contactPatchSense(self):
+        """enqueue the simulated sensors of the attached contact patches (task.attachContactPatch) at the current state: what a rollout
+        period does first, for a host-driven loop { contactPatchSense, computeControlTorques / stepAsync, integrate }"""
+        self._call("saip_batch_contact_patch_info", -1, None, None, None, None, None, None)  # without a patch: that error, before the device is needed
+        self._push_state()
+        self._call("saip_batch_contact_patch_sense")
 
     # -- clearance monitor: link spheres against world-fixed obstacles and against each other, inside rollouts (saip.h)
     @staticmethod

@@ -17,6 +17,7 @@
 #include "saip_state_snapshot.h"
 #include "saip_sampler.h"
 #include "saip_contact.h"
+#include "saip_contact_patch.h"
 #include "saip_clearance.h"
 
 namespace saip {
@@ -45,6 +46,7 @@ hipError_t launch_sampler_cost(const SamplerCostParams& P, hipStream_t stream);
 hipError_t launch_sampler_update(const SamplerParams& P, const double* cost, double temperature, double* w, SamplerResult* res, int* best_map, hipStream_t stream);
 hipError_t launch_sampler_shift(const SamplerParams& P, int n, hipStream_t stream);
 hipError_t launch_contact_apply(const ContactParams& P, bool tree, hipStream_t stream);
+hipError_t launch_contact_patch_apply(const ContactPatchParams& P, bool tree, hipStream_t stream);
 hipError_t launch_clearance_eval(const ClearanceParams& P, bool tree, hipStream_t stream);
 hipError_t launch_clearance_add_cost(int B, int ld, const double* summary, double* cost, double w_penalty, double w_collision, double d_safe, hipStream_t stream);
 hipError_t launch_clearance_summary_reset(int B, int ld, double* summary, hipStream_t stream);
@@ -502,6 +504,18 @@ struct saip_batch {
 		double* readout = nullptr;           // [8][ld]
 		double* summary = nullptr;           // [4][ld]
 	} contact;
+	// saip_batch_contact_patch_attach: contact patches (saip_contact_patch.hip), at most saip::PATCH_MAX per batch, on different motion-force
+	// tasks, in the order they were attached (a detach closes the gap).  Never together with `contact`.  Their arrays are their own, like
+	// those of `contact`; tau_sim is shared by the patches.
+	struct ContactPatch {
+		int task = -1, n_points = 0, n_planes = 0, per_instance = 0, sensor = 0;
+		double r[saip::PATCH_MAX_POINTS][3] = {};
+		double* planes = nullptr;            // [P][8] (batch-uniform) or [P][8][ld]
+		double* readout = nullptr;           // [20][ld]
+		double* summary = nullptr;           // [6][ld]
+	} patch[saip::PATCH_MAX];
+	int n_patch = 0;
+	double* patch_tau_sim = nullptr;         // [n][ld], while n_patch > 0
 	// saip_batch_clearance_attach: link spheres against obstacles and each other (saip_clearance.hip), at most one per batch.  Its arrays
 	// are configuration, scratch and readout: its own (freed by _detach), not part of `allocs` or of a snapshot.
 	struct Clearance {
@@ -572,6 +586,10 @@ extern "C" void saip_batch_destroy(saip_batch* b) {
 			if (p) (void)hipFree(p);
 		for (void* p : {(void*)b->contact.planes, (void*)b->contact.tau_sim, (void*)b->contact.readout, (void*)b->contact.summary})
 			if (p) (void)hipFree(p);
+		for (const auto& C : b->patch)
+			for (void* p : {(void*)C.planes, (void*)C.readout, (void*)C.summary})
+				if (p) (void)hipFree(p);
+		if (b->patch_tau_sim) (void)hipFree(b->patch_tau_sim);
 		for (void* p : {(void*)b->clearance.geom_dev, (void*)b->clearance.obst, (void*)b->clearance.readout, (void*)b->clearance.summary, (void*)b->clearance.centres})
 			if (p) (void)hipFree(p);
 		if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -2162,16 +2180,43 @@ static saip_status contact_upload_planes(saip_batch* b, double* dev, const std::
 	return SAIP_OK;
 }
 static bool contact_rows_overlap(int first, int count) { return first < 36 && first + count > 30; }
+// what saip_batch_contact_attach and saip_batch_contact_patch_attach ask of their arguments alike: the carrier ...
+static saip_status contact_attach_task(const saip_batch* b, int task, const char* fn) {
+	if (task < 0 || task >= (int)b->tasks.size()) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: task id %d out of range", fn, task);
+	if (b->tasks[task].dev.type != saip::TASK_MOTION_FORCE) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: task %d is not a motion-force task", fn, task);
+	return SAIP_OK;
+}
+// ... and the planes, the array sizes and the sensor against the task's goal schedule; `host` receives the table as the device keeps it
+static saip_status contact_attach_planes(const saip_batch* b, int task, int n_planes, const double* planes, int per_instance, int sensor,
+										 std::vector<double>& host, const char* fn) {
+	if (n_planes < 1 || n_planes > saip::CONTACT_MAX_PLANES) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: 1..%d planes required (got %d)", fn, saip::CONTACT_MAX_PLANES, n_planes);
+	if (!planes) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null planes", fn);
+	// [n][ld], [P][8][ld] doubles: the byte counts must fit a size_t
+	const size_t widest = (size_t)(b->model->n > 32 ? b->model->n : 32) * sizeof(double);
+	if ((size_t)b->ld > SIZE_MAX / widest) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: arrays of leading dimension %d are too large", fn, b->ld);
+	if (const char* bad = contact_check_planes(planes, n_planes, per_instance ? (size_t)b->B : 1, host)) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, bad);
+	if (sensor && task < (int)b->sched.size() && b->sched[task].attached && contact_rows_overlap(b->sched[task].first, b->sched[task].count))
+		return fail(SAIP_ERR_ORDER, "%s: the goal schedule of task %d covers sensed-wrench rows 30..35, which the simulated sensor writes", fn, task);
+	return SAIP_OK;
+}
+// a zeroed device array of `count` doubles; *p stays null when either call fails
+static saip_status contact_alloc_zero(saip_batch* b, double** p, size_t count) {
+	HIP_TRY(hipMalloc((void**)p, count * sizeof(double)));
+	const hipError_t e = hipMemsetAsync(*p, 0, count * sizeof(double), b->stream);
+	if (e != hipSuccess) {
+		(void)hipFree(*p);
+		*p = nullptr;
+		return fail(SAIP_ERR_DEVICE, "hipMemsetAsync failed: %s", hipGetErrorString(e));
+	}
+	return SAIP_OK;
+}
 extern "C" saip_status saip_batch_contact_attach(saip_batch* b, int task, const double* r_c, int n_planes, const double* planes, int per_instance,
 												 int sensor) {
 	const char* fn = "saip_batch_contact_attach";
 	saip_status st = need_controller(b, fn);
-	if (st) return st;
-	if (task < 0 || task >= (int)b->tasks.size()) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: task id %d out of range", fn, task);
-	if (b->tasks[task].dev.type != saip::TASK_MOTION_FORCE) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: task %d is not a motion-force task", fn, task);
+	if (st || (st = contact_attach_task(b, task, fn))) return st;
 	if (b->contact.attached) return fail(SAIP_ERR_ORDER, "%s: contact planes are already attached (saip_batch_contact_detach first)", fn);
-	if (n_planes < 1 || n_planes > saip::CONTACT_MAX_PLANES) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: 1..%d planes required (got %d)", fn, saip::CONTACT_MAX_PLANES, n_planes);
-	if (!planes) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null planes", fn);
+	if (b->n_patch > 0) return fail(SAIP_ERR_ORDER, "%s: a contact patch is attached (saip_batch_contact_patch_detach first)", fn);
 	per_instance = per_instance ? 1 : 0;
 	sensor = sensor ? 1 : 0;
 	double rc[3] = {0, 0, 0};
@@ -2179,23 +2224,12 @@ extern "C" saip_status saip_batch_contact_attach(saip_batch* b, int task, const 
 		if (!std::isfinite(r_c[e])) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the contact point is not finite", fn);
 		rc[e] = r_c[e];
 	}
-	// [n][ld], [P][8][ld] doubles: the byte counts must fit a size_t
-	const size_t widest = (size_t)(b->model->n > 32 ? b->model->n : 32) * sizeof(double);
-	if ((size_t)b->ld > SIZE_MAX / widest) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: arrays of leading dimension %d are too large", fn, b->ld);
 	std::vector<double> host;
-	if (const char* bad = contact_check_planes(planes, n_planes, per_instance ? (size_t)b->B : 1, host)) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, bad);
-	if (sensor && task < (int)b->sched.size() && b->sched[task].attached && contact_rows_overlap(b->sched[task].first, b->sched[task].count))
-		return fail(SAIP_ERR_ORDER, "%s: the goal schedule of task %d covers sensed-wrench rows 30..35, which the simulated sensor writes", fn, task);
-	if ((st = need_ready(b, fn))) return st;
+	if ((st = contact_attach_planes(b, task, n_planes, planes, per_instance, sensor, host, fn)) || (st = need_ready(b, fn))) return st;
 	auto& C = b->contact;
-	auto alloc_zero = [&](double** p, size_t count) -> saip_status {
-		HIP_TRY(hipMalloc((void**)p, count * sizeof(double)));
-		HIP_TRY(hipMemsetAsync(*p, 0, count * sizeof(double), b->stream));
-		return SAIP_OK;
-	};
 	const size_t ld = b->ld, rows = (size_t)n_planes * saip::CONTACT_PLANE_WORDS;
-	if ((st = alloc_zero(&C.planes, rows * (per_instance ? ld : 1))) || (st = alloc_zero(&C.tau_sim, (size_t)b->model->n * ld)) ||
-		(st = alloc_zero(&C.readout, (size_t)saip::CONTACT_READOUT_ROWS * ld)) || (st = alloc_zero(&C.summary, (size_t)saip::CONTACT_SUMMARY_ROWS * ld)) ||
+	if ((st = contact_alloc_zero(b, &C.planes, rows * (per_instance ? ld : 1))) || (st = contact_alloc_zero(b, &C.tau_sim, (size_t)b->model->n * ld)) ||
+		(st = contact_alloc_zero(b, &C.readout, (size_t)saip::CONTACT_READOUT_ROWS * ld)) || (st = contact_alloc_zero(b, &C.summary, (size_t)saip::CONTACT_SUMMARY_ROWS * ld)) ||
 		(st = contact_upload_planes(b, C.planes, host, n_planes, per_instance, fn))) {
 		contact_free(b);
 		return st;
@@ -2305,6 +2339,193 @@ extern "C" saip_status saip_batch_contact_summary_reset(saip_batch* b) {
 	saip_status st = need_contact(b, fn);
 	if (st || (st = need_ready(b, fn))) return st;
 	HIP_TRY(hipMemsetAsync(b->contact.summary, 0, (size_t)saip::CONTACT_SUMMARY_ROWS * b->ld * sizeof(double), b->stream));
+	return SAIP_OK;
+}
+
+// ---- contact patches (saip_contact_patch.hip): up to eight points per patch, net force and moment, up to two patches on different tasks
+// the slot of the patch on `task` (-1: of the first patch); < 0 with the error set
+static int patch_slot(const saip_batch* b, int task, const char* fn, saip_status* st) {
+	if ((*st = need_controller(b, fn))) return -1;
+	if (b->n_patch == 0) {
+		*st = fail(SAIP_ERR_ORDER, "%s: no contact patch is attached (saip_batch_contact_patch_attach)", fn);
+		return -1;
+	}
+	if (task == -1) return 0;
+	for (int i = 0; i < b->n_patch; i++)
+		if (b->patch[i].task == task) return i;
+	*st = fail(SAIP_ERR_ORDER, "%s: task %d carries no contact patch", fn, task);
+	return -1;
+}
+static void patch_free(saip_batch* b, int slot) {
+	auto& C = b->patch[slot];
+	for (void* p : {(void*)C.planes, (void*)C.readout, (void*)C.summary})
+		if (p) (void)hipFree(p);
+	for (int i = slot; i + 1 < b->n_patch; i++) b->patch[i] = b->patch[i + 1];
+	b->patch[b->n_patch - 1] = saip_batch::ContactPatch();
+	if (--b->n_patch == 0 && b->patch_tau_sim) {
+		(void)hipFree(b->patch_tau_sim);
+		b->patch_tau_sim = nullptr;
+	}
+}
+extern "C" saip_status saip_batch_contact_patch_attach(saip_batch* b, int task, int n_points, const double* points, int n_planes, const double* planes,
+													   int per_instance, int sensor) {
+	const char* fn = "saip_batch_contact_patch_attach";
+	saip_status st = need_controller(b, fn);
+	if (st || (st = contact_attach_task(b, task, fn))) return st;
+	if (b->contact.attached) return fail(SAIP_ERR_ORDER, "%s: single-point contact planes are attached (saip_batch_contact_detach first)", fn);
+	if (b->n_patch == saip::PATCH_MAX) return fail(SAIP_ERR_ORDER, "%s: %d contact patches are attached already", fn, saip::PATCH_MAX);
+	for (int i = 0; i < b->n_patch; i++)
+		if (b->patch[i].task == task) return fail(SAIP_ERR_ORDER, "%s: task %d already carries a contact patch (saip_batch_contact_patch_detach first)", fn, task);
+	per_instance = per_instance ? 1 : 0;
+	sensor = sensor ? 1 : 0;
+	if (n_points < 1 || n_points > saip::PATCH_MAX_POINTS) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: 1..%d points required (got %d)", fn, saip::PATCH_MAX_POINTS, n_points);
+	if (!points) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null points", fn);
+	for (int i = 0; i < 3 * n_points; i++)
+		if (!std::isfinite(points[i])) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a contact point is not finite", fn);
+	std::vector<double> host;
+	if ((st = contact_attach_planes(b, task, n_planes, planes, per_instance, sensor, host, fn)) || (st = need_ready(b, fn))) return st;
+	const size_t ld = b->ld, rows = (size_t)n_planes * saip::CONTACT_PLANE_WORDS;
+	if (!b->patch_tau_sim && (st = contact_alloc_zero(b, &b->patch_tau_sim, (size_t)b->model->n * ld))) return st;
+	const int slot = b->n_patch++;
+	auto& C = b->patch[slot];
+	if ((st = contact_alloc_zero(b, &C.planes, rows * (per_instance ? ld : 1))) || (st = contact_alloc_zero(b, &C.readout, (size_t)saip::PATCH_READOUT_ROWS * ld)) ||
+		(st = contact_alloc_zero(b, &C.summary, (size_t)saip::PATCH_SUMMARY_ROWS * ld)) || (st = contact_upload_planes(b, C.planes, host, n_planes, per_instance, fn))) {
+		patch_free(b, slot);
+		return st;
+	}
+	C.task = task;
+	C.n_points = n_points;
+	C.n_planes = n_planes;
+	C.per_instance = per_instance;
+	C.sensor = sensor;
+	for (int i = 0; i < 3 * n_points; i++) C.r[i / 3][i % 3] = points[i];
+	b->otg_prelaunched = false;
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_contact_patch_detach(saip_batch* b, int task) {
+	const char* fn = "saip_batch_contact_patch_detach";
+	saip_status st;
+	const int slot = patch_slot(b, task, fn, &st);
+	if (slot < 0 || (st = need_ready(b, fn))) return st;
+	HIP_TRY(hipStreamSynchronize(b->stream));  // a contact substep may still be in flight
+	if (task == -1)
+		while (b->n_patch > 0) patch_free(b, b->n_patch - 1);
+	else patch_free(b, slot);
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_contact_patch_info(saip_batch* b, int task, int* n_patches, int* n_points, int* n_planes, int* per_instance, int* sensor,
+													 double* points) {
+	saip_status st;
+	const int slot = patch_slot(b, task, "saip_batch_contact_patch_info", &st);
+	if (slot < 0) return st;
+	const auto& C = b->patch[slot];
+	if (n_patches) *n_patches = b->n_patch;
+	if (n_points) *n_points = C.n_points;
+	if (n_planes) *n_planes = C.n_planes;
+	if (per_instance) *per_instance = C.per_instance;
+	if (sensor) *sensor = C.sensor;
+	for (int i = 0; i < 3 * C.n_points && points; i++) points[i] = C.r[i / 3][i % 3];
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_contact_patch_set_planes_host(saip_batch* b, int task, const double* planes) {
+	const char* fn = "saip_batch_contact_patch_set_planes_host";
+	saip_status st;
+	const int slot = patch_slot(b, task, fn, &st);
+	if (slot < 0) return st;
+	if (!planes) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null planes", fn);
+	const auto& C = b->patch[slot];
+	std::vector<double> host;
+	if (const char* bad = contact_check_planes(planes, C.n_planes, C.per_instance ? (size_t)b->B : 1, host)) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, bad);
+	if ((st = need_ready(b, fn))) return st;
+	return contact_upload_planes(b, C.planes, host, C.n_planes, C.per_instance, fn);
+}
+static const saip_batch::ContactPatch* patch_of(const saip_batch* b, int task) {
+	if (!b) return nullptr;
+	for (int i = 0; i < b->n_patch; i++)
+		if (b->patch[i].task == task || task == -1) return &b->patch[i];
+	return nullptr;
+}
+extern "C" double* saip_batch_contact_patch_planes_device(saip_batch* b, int task) { return patch_of(b, task) ? patch_of(b, task)->planes : nullptr; }
+extern "C" double* saip_batch_contact_patch_readout_device(saip_batch* b, int task) { return patch_of(b, task) ? patch_of(b, task)->readout : nullptr; }
+extern "C" double* saip_batch_contact_patch_summary_device(saip_batch* b, int task) { return patch_of(b, task) ? patch_of(b, task)->summary : nullptr; }
+extern "C" double* saip_batch_contact_patch_torques_device(saip_batch* b) { return b ? b->patch_tau_sim : nullptr; }
+// one launch of the patch kernel at the resident state, for every patch; dt: the substep an APPLY launch stands in front of
+static saip_status patch_launch(saip_batch* b, int mode, double dt) {
+	{
+		CycleParams cp;  // (the task constants on the device must be current: uploaded here when the configuration changed)
+		saip_status st = make_params(b, cp, false);
+		if (st) return st;
+	}
+	saip::ContactPatchParams P;
+	memset(&P, 0, sizeof(P));
+	P.B = b->B;
+	P.ld = b->ld;
+	P.n = b->model->n;
+	P.mode = mode;
+	P.n_patches = b->n_patch;
+	P.dt = dt;
+	P.model = b->model_dev;
+	P.tasks = b->tasks_dev;
+	P.q = b->q;
+	P.dq = b->dq;
+	P.tau_cmd = b->tau_bound ? b->tau_bound : b->tau;
+	P.tau_sim = b->patch_tau_sim;
+	for (int i = 0; i < b->n_patch; i++) {
+		const auto& C = b->patch[i];
+		saip::PatchDev& D = P.patch[i];
+		D.task = C.task;
+		D.n_points = C.n_points;
+		D.n_planes = C.n_planes;
+		D.per_instance = C.per_instance;
+		D.sensor = C.sensor;
+		memcpy(D.r, C.r, sizeof(D.r));
+		D.planes = C.planes;
+		D.goal = b->tasks[C.task].goal_dev;
+		D.readout = C.readout;
+		D.summary = C.summary;
+	}
+	hipError_t e = saip::launch_contact_patch_apply(P, b->model->dev.is_tree != 0, b->stream);
+	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "contact patch launch failed: %s", hipGetErrorString(e));
+	return SAIP_OK;
+}
+static bool patch_any_sensor(const saip_batch* b) {
+	for (int i = 0; i < b->n_patch; i++)
+		if (b->patch[i].sensor) return true;
+	return false;
+}
+extern "C" saip_status saip_batch_contact_patch_sense(saip_batch* b) {
+	const char* fn = "saip_batch_contact_patch_sense";
+	saip_status st;
+	if (patch_slot(b, -1, fn, &st) < 0) return st;
+	if (!patch_any_sensor(b)) return fail(SAIP_ERR_ORDER, "%s: no contact patch was attached with the simulated sensor", fn);
+	if ((st = need_ready(b, fn))) return st;
+	return patch_launch(b, saip::CONTACT_SENSE, 0.0);
+}
+extern "C" saip_status saip_batch_contact_patch_readout_host(saip_batch* b, int task, double* out) {
+	const char* fn = "saip_batch_contact_patch_readout_host";
+	saip_status st;
+	const int slot = patch_slot(b, task, fn, &st);
+	if (slot < 0) return st;
+	if (!out) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null output", fn);
+	if ((st = need_ready(b, fn))) return st;
+	return copy_d2h(b, out, b->patch[slot].readout, saip::PATCH_READOUT_ROWS);
+}
+extern "C" saip_status saip_batch_contact_patch_summary_host(saip_batch* b, int task, double* out) {
+	const char* fn = "saip_batch_contact_patch_summary_host";
+	saip_status st;
+	const int slot = patch_slot(b, task, fn, &st);
+	if (slot < 0) return st;
+	if (!out) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null output", fn);
+	if ((st = need_ready(b, fn))) return st;
+	return copy_d2h(b, out, b->patch[slot].summary, saip::PATCH_SUMMARY_ROWS);
+}
+extern "C" saip_status saip_batch_contact_patch_summary_reset(saip_batch* b, int task) {
+	const char* fn = "saip_batch_contact_patch_summary_reset";
+	saip_status st;
+	const int slot = patch_slot(b, task, fn, &st);
+	if (slot < 0 || (st = need_ready(b, fn))) return st;
+	for (int i = 0; i < b->n_patch; i++)
+		if (task == -1 || i == slot) HIP_TRY(hipMemsetAsync(b->patch[i].summary, 0, (size_t)saip::PATCH_SUMMARY_ROWS * b->ld * sizeof(double), b->stream));
 	return SAIP_OK;
 }
 
@@ -2568,13 +2789,15 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 	S.ddq = nullptr;
 	hipError_t e;
 	const bool tree = b->model->dev.is_tree != 0;  // trees: the lane-per-instance tree kernel, whatever the dof (the eight-lane step is chain-only)
-	if (b->contact.attached) {
+	if (b->contact.attached || b->n_patch > 0) {
 		// contact planes: the penalty force is re-evaluated in front of every substep (held over a control period it is unstable at
-		// useful stiffness), and the integrator takes commanded + contact torques; never fused with the next period's OTG step
+		// useful stiffness), and the integrator takes commanded + contact torques; never fused with the next period's OTG step.
+		// Contact patches take the same place with their own kernel.
+		const bool patches = b->n_patch > 0;
 		S.substeps = 1;
-		S.tau = b->contact.tau_sim;
+		S.tau = patches ? b->patch_tau_sim : b->contact.tau_sim;
 		for (int s = 0; s < substeps; s++) {
-			saip_status st = contact_launch(b, saip::CONTACT_APPLY, dt);
+			saip_status st = patches ? patch_launch(b, saip::CONTACT_APPLY, dt) : contact_launch(b, saip::CONTACT_APPLY, dt);
 			if (st) return st;
 			e = saip::launch_integrate(S, tree, b->stream);
 			if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "integrate launch failed: %s", hipGetErrorString(e));
@@ -2818,6 +3041,9 @@ extern "C" saip_status saip_batch_goal_schedule_attach(saip_batch* b, int task, 
 	if (n_keyframes < 1 || stride < 1) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: n_keyframes >= 1 and stride >= 1 required", fn);
 	if (b->contact.attached && b->contact.sensor && b->contact.task == task && contact_rows_overlap(first, count))
 		return fail(SAIP_ERR_ORDER, "%s: rows 30..35 of task %d are written by the simulated sensor of the attached contact planes", fn, task);
+	for (int i = 0; i < b->n_patch; i++)
+		if (b->patch[i].sensor && b->patch[i].task == task && contact_rows_overlap(first, count))
+			return fail(SAIP_ERR_ORDER, "%s: rows 30..35 of task %d are written by the simulated sensor of its contact patch", fn, task);
 	if (mode != saip::SCHED_HOLD && mode != saip::SCHED_LINEAR) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: unknown mode %d", fn, mode);
 	per_instance = per_instance ? 1 : 0;
 	// [K][count][ld] (or [K][count]) doubles: the byte count must fit a size_t
@@ -2954,11 +3180,14 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 	// the next period's OTG step (which would read the next goal before it is written)
 	const bool scheduled = b->n_sched > 0;
 	// with contact planes attached neither fused form is used: the contact force sits between the cycle and every integration substep
-	const bool contact = b->contact.attached;
+	// (contact patches: the same, with their kernel)
+	const bool contact = b->contact.attached || b->n_patch > 0;
+	const bool patch_sensor = patch_any_sensor(b);
 	auto period = [&](const bool more = false) -> saip_status {  // more: another period follows inside this call
 		if (scheduled && (st = apply_schedules(b))) return st;
 		// contact planes with the simulated sensor: the sensed wrench of this period's state, in front of the OTGs (which pass it on) and the cycle
-		if (contact && b->contact.sensor && (st = contact_launch(b, saip::CONTACT_SENSE, 0.0))) return st;
+		if (b->contact.attached && b->contact.sensor && (st = contact_launch(b, saip::CONTACT_SENSE, 0.0))) return st;
+		if (patch_sensor && (st = patch_launch(b, saip::CONTACT_SENSE, 0.0))) return st;
 		// no internal OTG in the stack: the cycle launch integrates the state itself when it can (eight-lane kernel, no slow path behind)
 		bool integrated = false;
 		saip_status s2 = launch_cycle(b, false, (!any_otg && b->model->n == 7 && !contact) ? &sim : nullptr, &integrated);

@@ -17,7 +17,10 @@
    --contact [--contact-planes P] [--contact-sensor] [--contact-stack 2|13] [--substeps S] times, interleaved in the same run, the
    closed-loop period without and with contact planes attached to the motion-force task (P planes: a table just under the control point
    and P - 1 far walls), and the integrate call alone both ways; --contact-stack 13 runs config 13's closed-loop force stack
-   (DESIGN.md 4.12).
+   (DESIGN.md 4.12).  With --contact-points N [--contact-patches 1|2] the same run also times a contact patch of N points (1..8) in place of
+   the single-point attachment, and the event-timed mean of 200 one-substep integrate calls plain, with the single point and with the
+   patch: the differences are the contact launches alone.  Two patches run on the dual-arm tree, one patch per flange, the single point
+   on the left one.
    --clearance [--clearance-spheres S] [--clearance-obstacles O] [--clearance-pairs P] times, interleaved in the same run, the closed-loop
    period without and with a clearance monitor of S link spheres, O batch-uniform obstacles (capsules, every fourth a half-space) and P self
    pairs, and prints the event-timed mean of 200 back-to-back evaluations alone."""
@@ -30,6 +33,34 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import workloads as W  # noqa: E402
 from sai_primitives_amd.controller import controller_from_specs  # noqa: E402
+
+
+def stream_timer(ctrl):
+    """timed_us(fn, reps, first=None): the mean, in microseconds, of `reps` back-to-back calls of fn between two HIP events recorded on the
+    engine stream, after one call of `first` (fn itself by default) and a synchronise; and the HIP runtime the events came from"""
+    import ctypes as C
+    hip = C.CDLL("libamdhip64.so")
+    vp = C.c_void_p
+    hip.hipEventCreate.argtypes, hip.hipEventRecord.argtypes, hip.hipEventSynchronize.argtypes = [C.POINTER(vp)], [vp, vp], [vp]
+    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), vp, vp]
+    stream = ctrl.devicePointers()["stream"]
+    ev = [vp(), vp()]
+    for e in ev:
+        assert hip.hipEventCreate(C.byref(e)) == 0
+
+    def timed_us(fn, reps=50, first=None):
+        (first or fn)()
+        ctrl.synchronize()
+        assert hip.hipEventRecord(ev[0], stream) == 0
+        for _ in range(reps):
+            fn()
+        assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
+        ms = C.c_float()
+        assert hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
+        return ms.value / reps * 1e3
+
+    return timed_us, hip
+
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--record-stride", type=int, default=None)
@@ -44,6 +75,8 @@ ap.add_argument("--contact", action="store_true")
 ap.add_argument("--contact-planes", type=int, default=1)
 ap.add_argument("--contact-sensor", action="store_true")
 ap.add_argument("--contact-stack", type=int, choices=(2, 13), default=2)
+ap.add_argument("--contact-points", type=int, default=None)
+ap.add_argument("--contact-patches", type=int, choices=(1, 2), default=1)
 ap.add_argument("--substeps", type=int, default=2)
 ap.add_argument("--clearance", action="store_true")
 ap.add_argument("--clearance-spheres", type=int, default=8)
@@ -53,13 +86,23 @@ args = ap.parse_args()
 record = args.record_stride is not None or args.record_channels is not None or args.record_summaries
 
 for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
-    d = W.make_inputs(args.contact_stack if args.contact else 2, B)
-    robot, ctrl, tasks = controller_from_specs(d["model"].name, d["tasks"], B, device=0, disable_otg=args.no_otg)
+    dual = args.contact and args.contact_points is not None and args.contact_patches == 2
+    if dual:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import trees as TR
+        desc = TR.dual_panda_torso()
+        model = W.RobotModel(desc)
+        d = dict(model=model, tasks=TR.dual_stack(model))
+        d["q"] = np.clip(np.random.default_rng(0).uniform(-0.8, 0.8, (B, model.dof)), model.q_lower + 0.1, model.q_upper - 0.1)
+        robot, ctrl, tasks = controller_from_specs(desc, d["tasks"], B, device=0, disable_otg=args.no_otg)
+    else:
+        d = W.make_inputs(args.contact_stack if args.contact else 2, B)
+        robot, ctrl, tasks = controller_from_specs(d["model"].name, d["tasks"], B, device=0, disable_otg=args.no_otg)
     robot.setQ(d["q"])
-    robot.setDq(np.zeros((B, 7)))
+    robot.setDq(np.zeros((B, d["model"].dof)))
     robot.updateModel()
     ctrl.reinitializeTasks()
-    mf, jt = tasks
+    mf, jt = tasks[0], tasks[-1]
     mf.setGoalPosition(mf.getGoalPosition() + np.array([0.05, -0.04, 0.03]))
     ctrl.updateControllerTaskModels()
     K = 400
@@ -73,16 +116,11 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
     ctrl.synchronize()
     if args.snapshot:
         import ctypes as C
-        hip = C.CDLL("libamdhip64.so")
+        timed_us, hip = stream_timer(ctrl)
         vp = C.c_void_p
         hip.hipMalloc.argtypes, hip.hipFree.argtypes = [C.POINTER(vp), C.c_size_t], [vp]
-        hip.hipEventCreate.argtypes, hip.hipEventRecord.argtypes, hip.hipEventSynchronize.argtypes = [C.POINTER(vp)], [vp, vp], [vp]
-        hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), vp, vp]
         hip.hipMemcpyAsync.argtypes = [vp, vp, C.c_size_t, C.c_int, vp]
         stream = ctrl.devicePointers()["stream"]
-        ev = [vp(), vp()]
-        for e in ev:
-            assert hip.hipEventCreate(C.byref(e)) == 0
         snap = ctrl.saveState()
         segs = snap.segments()
         ends = [s["offset"] for s in segs[1:]] + [snap.nbytes()]
@@ -97,17 +135,6 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
             for s, n in zip(segs, sizes):
                 assert hip.hipMemcpyAsync(bufs[0].value + s["offset"], bufs[1].value + s["offset"], n, 3, stream) == 0   # device to device
 
-        def timed_us(fn, reps=50):
-            fn()
-            ctrl.synchronize()
-            assert hip.hipEventRecord(ev[0], stream) == 0
-            for _ in range(reps):
-                fn()
-            assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
-            ms = C.c_float()
-            assert hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
-            return ms.value / reps * 1e3
-
         for _ in range(args.repeats):
             t = dict(save=timed_us(lambda: ctrl.saveState(snap)), identity=timed_us(lambda: ctrl.restoreState(snap)),
                      permutation=timed_us(lambda: ctrl.restoreState(snap, perm)), broadcast=timed_us(lambda: ctrl.restoreState(snap, bcast)),
@@ -120,28 +147,9 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
         snap.close()
         continue
     if args.sampler:
-        import ctypes as C
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
         import sampler_ref as SR
-        hip = C.CDLL("libamdhip64.so")
-        vp = C.c_void_p
-        hip.hipEventCreate.argtypes, hip.hipEventRecord.argtypes, hip.hipEventSynchronize.argtypes = [C.POINTER(vp)], [vp, vp], [vp]
-        hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), vp, vp]
-        stream = ctrl.devicePointers()["stream"]
-        ev = [vp(), vp()]
-        for e in ev:
-            assert hip.hipEventCreate(C.byref(e)) == 0
-
-        def timed_us(fn, reps=50):
-            fn()
-            ctrl.synchronize()
-            assert hip.hipEventRecord(ev[0], stream) == 0
-            for _ in range(reps):
-                fn()
-            assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
-            ms = C.c_float()
-            assert hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
-            return ms.value / reps * 1e3
+        timed_us, _ = stream_timer(ctrl)
 
         KF, sigma, T = 16, np.array([0.02, 0.02, 0.02, 0.05, 0.05, 0.05]), 0.05
         nominal = np.repeat(mf._get_goal()[0, :12][None], KF, axis=0)
@@ -198,6 +206,40 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
             ctrl.synchronize()
             return (time.perf_counter() - t0) / 200 * 1e6
 
+        if args.contact_points is not None:
+            timed_us, _ = stream_timer(ctrl)
+
+            def substep_us():
+                return timed_us(lambda: ctrl.integrate(5e-4, 1, gravity=(0, 0, 0)), 200)
+
+            N = args.contact_points
+            ang = 2.0 * np.pi * np.arange(N) / N
+            pts = np.column_stack([0.05 * np.cos(ang), 0.05 * np.sin(ang), np.zeros(N)]) if N > 1 else np.zeros((1, 3))
+            carriers = [(t, s["link"], tuple(s["pos_in_link"])) for t, s in zip(tasks[:args.contact_patches], d["tasks"])]
+            tables = []
+            for t, link, pos in carriers:       # per patch: a table 1 mm above its lowest point, and the far walls
+                pz = np.stack([robot.position(link, tuple(np.asarray(pos) + r))[:, 2] for r in pts]).min(axis=0)
+                tb = planes.copy()
+                tb[0, :, 3] = pz + 1e-3
+                tables.append(tb)
+            for _ in range(args.repeats):
+                plain, plain_i, plain_s = period_us(), integrate_us(), substep_us()
+                mf.attachContactPlanes(planes, sensor=args.contact_sensor, per_instance=True)
+                period_us()
+                one, one_i, one_s = period_us(), integrate_us(), substep_us()
+                mf.detachContactPlanes()
+                for (t, _, _), tb in zip(carriers, tables):
+                    t.attachContactPatch(pts, tb, sensor=args.contact_sensor, per_instance=True)
+                period_us()
+                pat, pat_i, pat_s = period_us(), integrate_us(), substep_us()
+                touching = int((mf.contactPatchReadout()["n_touch"] > 0).sum())
+                ctrl._call("saip_batch_contact_patch_detach", -1)
+                print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} {'dual-arm tree' if dual else f'cfg{args.contact_stack}'} otg "
+                      f"{'off' if args.no_otg else 'on'} substeps {sub}, {P} plane(s), sensor {'on' if args.contact_sensor else 'off'}: period / integrate / "
+                      f"one substep on the stream: unattached {plain:.1f} / {plain_i:.1f} / {plain_s:.2f} us; single point {one:.1f} / {one_i:.1f} / "
+                      f"{one_s:.2f} us; {args.contact_patches} patch(es) of {N} points {pat:.1f} / {pat_i:.1f} / {pat_s:.2f} us; launch alone: single point "
+                      f"{one_s - plain_s:.2f} us, patch {pat_s - plain_s:.2f} us ({touching} of {B} instances touching at the end)")
+            continue
         for _ in range(args.repeats):
             plain, plain_i = period_us(), integrate_us()
             mf.attachContactPlanes(planes, sensor=args.contact_sensor, per_instance=True)
@@ -210,7 +252,6 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
                   f"period {with_c:.1f} us, integrate {with_i:.1f} us ({touching} of {B} instances touching at the end)")
         continue
     if args.clearance:
-        import ctypes as C
         S, O, P = args.clearance_spheres, args.clearance_obstacles, args.clearance_pairs
         rng = np.random.default_rng(0)
         names = [f"link{i}" for i in range(1, 8)] + ["end-effector"]
@@ -221,14 +262,7 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
         obst[:, 7] = 0.03
         obst[3::4] = [1.0, 0.0, 0.0, 1.0, -0.2, 0.0, 0.0, 0.0]               # every fourth: a floor
         pairs = [(p % S, (p % S + 1 + p // S) % S) for p in range(P)]
-        hip = C.CDLL("libamdhip64.so")
-        vp = C.c_void_p
-        hip.hipEventCreate.argtypes, hip.hipEventRecord.argtypes, hip.hipEventSynchronize.argtypes = [C.POINTER(vp)], [vp, vp], [vp]
-        hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), vp, vp]
-        stream = ctrl.devicePointers()["stream"]
-        ev = [vp(), vp()]
-        for e in ev:
-            assert hip.hipEventCreate(C.byref(e)) == 0
+        timed_us, _ = stream_timer(ctrl)
 
         def period_us():
             t0 = time.perf_counter()
@@ -236,16 +270,8 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
             ctrl.synchronize()
             return (time.perf_counter() - t0) / K * 1e6
 
-        def evaluate_us(reps=200):
-            ctrl.evaluateClearance()
-            ctrl.synchronize()
-            assert hip.hipEventRecord(ev[0], stream) == 0
-            for _ in range(reps):
-                ctrl._call("saip_batch_clearance_evaluate")
-            assert hip.hipEventRecord(ev[1], stream) == 0 and hip.hipEventSynchronize(ev[1]) == 0
-            ms = C.c_float()
-            assert hip.hipEventElapsedTime(C.byref(ms), ev[0], ev[1]) == 0
-            return ms.value / reps * 1e3
+        def evaluate_us():
+            return timed_us(lambda: ctrl._call("saip_batch_clearance_evaluate"), 200, first=ctrl.evaluateClearance)
 
         for _ in range(args.repeats):
             plain = period_us()
