@@ -491,6 +491,65 @@ double* saip_batch_clearance_summary_device(saip_batch*);    /* [4][ld]; NULL wh
 saip_status saip_batch_clearance_summary_reset(saip_batch*);
 double* saip_batch_clearance_centres_device(saip_batch*);    /* [3 S][ld]; NULL unless keep_centres */
 saip_status saip_batch_clearance_add_cost(saip_batch*, double w_penalty, double w_collision, double d_safe);
+/* ---- plant model: what stands between the commanded torques and the integrator when the robot is not the controller's model --
+ * actuator gain, offset and saturation, viscous and Coulomb friction, penalty joint stops and external wrenches on links.  One attachment
+ * per batch.  Nothing in it is state: it is configuration plus a host-side period counter, not part of a state snapshot.
+ *   joints    SAIP_PLANT_JOINT_WORDS doubles per joint { gain, bias, tau_max, fv, fc, v_s, q_lo, q_hi, k_stop, c_stop }: `joint_table` is
+ *             [dof][10] (batch-uniform) or [dof][10][B] (per_instance_joints); NULL: neutral rows { 1, 0, +inf, 0, 0, 0, q_lo, q_hi, 0, 0 }
+ *             with q_lo, q_hi the model's joint limits.  With t the commanded torque of the joint:
+ *               u0 = t == t ? t : 0        u1 = gain u0 + bias        u2 = min(max(u1, -tau_max), tau_max)
+ *               fr = fv dq + (fc > 0 ? (fc dq) / max(|dq|, v_s) : 0)
+ *               st = q < q_lo ? max(0, k_stop (q_lo - q) - c_stop dq) : q > q_hi ? -max(0, k_stop (q - q_hi) + c_stop dq) : 0
+ *               tau_act = (u2 - fr) + st
+ *   wrenches  n_wrenches (0..SAIP_PLANT_MAX_WRENCHES), each with a batch-uniform site: links[k] a saip_model_link_index value, points[3 k ..]
+ *             a point in that link's frame, frames[k] SAIP_PLANT_FRAME_WORLD or _LINK, the frame F and M are given in (world: the frame
+ *             of the robot's base, as a task's pose is).  `wrench_table` is SAIP_PLANT_WRENCH_WORDS doubles per wrench { F[3], M[3],
+ *             p_start, p_end }, [W][8] or [W][8][B] (per_instance_wrenches).  A wrench acts in period p when p_start <= p < p_end (p_end =
+ *             +inf: for ever); it adds aw . ((p - o_j) x F + M) (revolute) or aw . F (prismatic) to tau_act of every ancestor joint j of
+ *             the link, the wrenches in table order.  F = (0, 0, -m g) for ever is the weight of a carried payload.
+ *   summaries [4][ld]: sum dt sum_j |fr_j dq_j|; the largest |u1 - u2| so far; substeps in which a joint clipped or a stop acted;
+ *             sum dt sum x dq_j over what the wrenches added (x) to the joints.
+ * Every product and sum is rounded once, in the order written; max and min return their first argument on a tie (csrc/saip_plant.h;
+ * tests/plant_ref.py restates it in NumPy bit for bit).
+ *   while attached, every integration substep of saip_batch_integrate and saip_batch_rollout_async is { plant launch, the contact or patch
+ *        APPLY launch if one is attached (reading tau_act in place of the commanded torques), integrate launch with one substep reading
+ *        the last buffer written }, and a rollout uses neither fused form.  The period counter starts at 0, advances once per
+ *        saip_batch_integrate call and once per rollout period, and is set by _set_period (pair it with a snapshot restore).  The
+ *        recorder keeps logging the commanded torques.
+ *   saip_batch_plant_randomize fills the per-instance tables on the device: word w (10 j + k of a joint, 8 k + e of a wrench) of instance
+ *        i is lo[w] + u (hi[w] - lo[w]), u = the first uniform of Philox4x32-10 at counter (i, w, table, round) (table 0 joints, 1
+ *        wrenches) under the key `seed`; lo == hi gives lo exactly; p_start and p_end are floored.  lo / hi are host tables [dof][10] and
+ *        [W][8]; a NULL pair leaves that table alone.  Both bounds must be valid tables, and so must what can be drawn between them.
+ *   _set_joints_host / _set_wrenches_host replace a table (same shape) and wait; _joints_device / _wrenches_device are the resident
+ *        tables ([dof][10] or [dof][10][ld], [W][8] or [W][8][ld]; what is written there is not checked); _torques_device is tau_act
+ *        [dof][ld] of the last substep.
+ * Without an attachment every entry point enqueues exactly what it did before.  SAIP_ERR_INVALID_ARGUMENT (the message names the entry,
+ * the joint or wrench and the word): a NaN anywhere; gain, bias, fv, fc, k_stop, c_stop, F or M not finite; tau_max, fv, fc, k_stop or
+ * c_stop below 0; fc > 0 with v_s <= 0; q_lo > q_hi; a link index out of range, a point that is not finite, an unknown frame, a count
+ * above the maximum; _randomize of a batch-uniform table.  SAIP_ERR_ORDER: before finalize, a model-only batch, a second _attach, any
+ * other entry without an attachment.  Argument and order errors are reported before the device is needed. */
+#define SAIP_PLANT_JOINT_WORDS 10
+#define SAIP_PLANT_WRENCH_WORDS 8
+#define SAIP_PLANT_MAX_WRENCHES 4
+#define SAIP_PLANT_SUMMARY_ROWS 4
+#define SAIP_PLANT_FRAME_WORLD 0
+#define SAIP_PLANT_FRAME_LINK 1
+saip_status saip_batch_plant_attach(saip_batch*, const double* joint_table /* NULL = neutral */, int per_instance_joints, int n_wrenches,
+                                    const int* links, const double* points /* [W][3] */, const int* frames, const double* wrench_table,
+                                    int per_instance_wrenches);
+saip_status saip_batch_plant_detach(saip_batch*);
+saip_status saip_batch_plant_info(saip_batch*, int* per_instance_joints, int* n_wrenches, int* per_instance_wrenches, long long* period);  /* any NULL */
+saip_status saip_batch_plant_set_joints_host(saip_batch*, const double* joint_table);
+saip_status saip_batch_plant_set_wrenches_host(saip_batch*, const double* wrench_table);
+saip_status saip_batch_plant_randomize(saip_batch*, unsigned long long seed, long long round, const double* joint_lo, const double* joint_hi,
+                                       const double* wrench_lo, const double* wrench_hi);
+saip_status saip_batch_plant_set_period(saip_batch*, long long period);
+saip_status saip_batch_plant_summary_host(saip_batch*, double* out /* [4][B] */);  /* synchronous */
+saip_status saip_batch_plant_summary_reset(saip_batch*);
+double* saip_batch_plant_joints_device(saip_batch*);    /* NULL when detached */
+double* saip_batch_plant_wrenches_device(saip_batch*);  /* NULL when detached or without wrenches */
+double* saip_batch_plant_torques_device(saip_batch*);   /* [dof][ld]; NULL when detached */
+double* saip_batch_plant_summary_device(saip_batch*);   /* [4][ld]; NULL when detached */
 /* ---- rollout recorder: a per-period trajectory log and running summaries of saip_batch_rollout_async, kept on the device (the
  * reference's example loops print or log the same quantities every period: state, torques, position / orientation error).  A recorder
  * is attached to a finalized batch and stays attached across rollout calls until detached.  It observes rollout periods only

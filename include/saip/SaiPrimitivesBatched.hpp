@@ -1255,6 +1255,96 @@ public:
 		check(saip_batch_clearance_add_cost(_batch, w_penalty, w_collision, d_safe));
 	}
 
+	// ---- plant model: actuator limits, friction, joint stops and external wrenches between the commanded torques and the resident
+	// simulator (saip.h).  While attached, integrate() and rolloutAsync() run it in front of every substep (and in front of the contact
+	// launch, if any); the period counter of the wrench windows advances once per integrate() and once per rollout period.
+	struct PlantWrench {
+		std::string link;
+		std::array<double, 3> point;   // in the link frame
+		bool link_frame;               // F and M are given in the link frame (else: the world)
+		std::vector<double> values;    // { F[3], M[3], p_start, p_end }: 8, or [8][B] with per_instance
+	};
+	struct PlantInfo {
+		int per_instance_joints = 0, n_wrenches = 0, per_instance_wrenches = 0;
+		long long period = 0;          // the period the next integration belongs to
+	};
+	// [dof][10] rows { gain, bias, tau_max, fv, fc, v_s, q_lo, q_hi, k_stop, c_stop } that change nothing, with the model's joint limits
+	std::vector<double> neutralPlantJoints() {
+		const int n = _robot->dof();
+		std::vector<double> lo(n), hi(n), t((size_t)n * SAIP_PLANT_JOINT_WORDS, 0.0);
+		check(saip_model_joint_limits(_robot->_model, lo.data(), hi.data(), nullptr, nullptr));
+		for (int j = 0; j < n; j++) {
+			double* w = t.data() + (size_t)j * SAIP_PLANT_JOINT_WORDS;
+			const bool limits = lo[j] <= hi[j];
+			w[0] = 1.0;
+			w[2] = std::numeric_limits<double>::infinity();
+			w[6] = limits ? lo[j] : -w[2];
+			w[7] = limits ? hi[j] : w[2];
+		}
+		return t;
+	}
+	// joints: [dof][10], or [dof][10][B] with per_instance; empty: the neutral rows.  wrenches: up to SAIP_PLANT_MAX_WRENCHES
+	void attachPlant(const std::vector<double>& joints = {}, const std::vector<PlantWrench>& wrenches = {}, bool per_instance = false) {
+		const size_t cols = per_instance ? (size_t)_robot->batchSize() : 1;
+		if (!joints.empty() && joints.size() != (size_t)_robot->dof() * SAIP_PLANT_JOINT_WORDS * cols)
+			throw std::invalid_argument("attachPlant: expected [dof][10] joints, or [dof][10][B] per instance");
+		std::vector<int> links, frames;
+		std::vector<double> points, table(wrenches.size() * SAIP_PLANT_WRENCH_WORDS * cols);
+		for (size_t k = 0; k < wrenches.size(); k++) {
+			const PlantWrench& w = wrenches[k];
+			if (w.values.size() != SAIP_PLANT_WRENCH_WORDS * cols) throw std::invalid_argument("attachPlant: expected 8 values per wrench, or [8][B] per instance");
+			links.push_back(_robot->linkIndex(w.link));
+			frames.push_back(w.link_frame ? SAIP_PLANT_FRAME_LINK : SAIP_PLANT_FRAME_WORLD);
+			points.insert(points.end(), w.point.begin(), w.point.end());
+			std::copy(w.values.begin(), w.values.end(), table.begin() + k * SAIP_PLANT_WRENCH_WORDS * cols);
+		}
+		check(saip_batch_plant_attach(_batch, joints.empty() ? nullptr : joints.data(), per_instance ? 1 : 0, (int)wrenches.size(), links.data(), points.data(),
+									  frames.data(), table.data(), per_instance ? 1 : 0));
+	}
+	void detachPlant() { check(saip_batch_plant_detach(_batch)); }
+	PlantInfo plantInfo() {
+		PlantInfo i;
+		check(saip_batch_plant_info(_batch, &i.per_instance_joints, &i.n_wrenches, &i.per_instance_wrenches, &i.period));
+		return i;
+	}
+	void setPlantJoints(const std::vector<double>& joints) {
+		const PlantInfo i = plantInfo();
+		if (joints.size() != (size_t)_robot->dof() * SAIP_PLANT_JOINT_WORDS * (i.per_instance_joints ? (size_t)_robot->batchSize() : 1))
+			throw std::invalid_argument("setPlantJoints: the shape of the attached joint table expected");
+		check(saip_batch_plant_set_joints_host(_batch, joints.data()));
+	}
+	void setPlantWrenches(const std::vector<double>& values) {
+		const PlantInfo i = plantInfo();
+		if (values.size() != (size_t)i.n_wrenches * SAIP_PLANT_WRENCH_WORDS * (i.per_instance_wrenches ? (size_t)_robot->batchSize() : 1))
+			throw std::invalid_argument("setPlantWrenches: the shape of the attached wrench table expected");
+		check(saip_batch_plant_set_wrenches_host(_batch, values.data()));
+	}
+	// per-instance tables drawn on the device, uniform between two batch-uniform tables ([dof][10], [W][8]); an empty pair leaves that table alone
+	void randomizePlant(unsigned long long seed, long long round, const std::vector<double>& joint_lo, const std::vector<double>& joint_hi,
+						const std::vector<double>& wrench_lo = {}, const std::vector<double>& wrench_hi = {}) {
+		const PlantInfo i = plantInfo();
+		const size_t jw = (size_t)_robot->dof() * SAIP_PLANT_JOINT_WORDS, ww = (size_t)i.n_wrenches * SAIP_PLANT_WRENCH_WORDS;
+		if ((!joint_lo.empty() || !joint_hi.empty()) && (joint_lo.size() != jw || joint_hi.size() != jw))
+			throw std::invalid_argument("randomizePlant: expected [dof][10] joint bounds");
+		if ((!wrench_lo.empty() || !wrench_hi.empty()) && (wrench_lo.size() != ww || wrench_hi.size() != ww))
+			throw std::invalid_argument("randomizePlant: expected [W][8] wrench bounds");
+		check(saip_batch_plant_randomize(_batch, seed, round, joint_lo.empty() ? nullptr : joint_lo.data(), joint_hi.empty() ? nullptr : joint_hi.data(),
+										 wrench_lo.empty() ? nullptr : wrench_lo.data(), wrench_hi.empty() ? nullptr : wrench_hi.data()));
+	}
+	// pair it with restoreState: the counter is not part of a snapshot
+	void setPlantPeriod(long long period) { check(saip_batch_plant_set_period(_batch, period)); }
+	// [4][B]: sum dt sum_j |fr_j dq_j|, the largest clipped torque, substeps in which a joint clipped or a stop acted, sum dt sum ext_j dq_j; waits for the stream
+	std::vector<double> plantSummary() {
+		std::vector<double> out((size_t)SAIP_PLANT_SUMMARY_ROWS * _robot->batchSize());
+		check(saip_batch_plant_summary_host(_batch, out.data()));
+		return out;
+	}
+	void resetPlantSummary() { check(saip_batch_plant_summary_reset(_batch)); }
+	double* plantJointsDevice() { return saip_batch_plant_joints_device(_batch); }      // [dof][10] or [dof][10][ld]
+	double* plantWrenchesDevice() { return saip_batch_plant_wrenches_device(_batch); }  // [W][8] or [W][8][ld]; nullptr without wrenches
+	double* plantTorquesDevice() { return saip_batch_plant_torques_device(_batch); }    // [dof][ld] actuated torques of the last substep
+	double* plantSummaryDevice() { return saip_batch_plant_summary_device(_batch); }    // [4][ld]
+
 private:
 	void restored(saip_status st) {
 		check(st);

@@ -1723,6 +1723,140 @@ class RobotController:
         cost is an invalid sample to updateSampler(), so the default w_collision makes collision a hard constraint"""
         self._call("saip_batch_clearance_add_cost", float(w_penalty), float(w_collision), float(d_safe))
 
+    # -- plant model: actuator limits, friction, joint stops and external wrenches in front of every integration substep (saip.h)
+    PLANT_JOINT_WORDS = ("gain", "bias", "tau_max", "fv", "fc", "v_s", "q_lo", "q_hi", "k_stop", "c_stop")
+
+    def neutralPlantJoints(self):
+        """the (dof, 10) joint table that changes nothing: gain 1, no offset, no limit, no friction, the model's joint limits as stops of
+        stiffness 0 -- a starting point for attachPlant(joints=...)"""
+        lim = self._robot.jointLimits()
+        lo, hi = lim["position_lower"], lim["position_upper"]
+        ok = lo <= hi
+        t = np.zeros((self._robot.dof(), capi.SAIP_PLANT_JOINT_WORDS))
+        t[:, 0], t[:, 2] = 1.0, np.inf
+        t[:, 6], t[:, 7] = np.where(ok, lo, -np.inf), np.where(ok, hi, np.inf)
+        return t
+
+    @staticmethod
+    def _plant_table(table, per_instance, B, rows, words, who, what):
+        a = np.asarray(table, float)
+        if per_instance:
+            if a.shape != (rows, B, words):
+                raise ValueError(f"{who}: per-instance {what} of shape ({rows}, {B}, {words}) expected, got {a.shape}")
+            return np.ascontiguousarray(a.transpose(0, 2, 1))
+        if a.shape != (rows, words):
+            raise ValueError(f"{who}: {what} of shape ({rows}, {words}) expected, got {a.shape}")
+        return np.ascontiguousarray(a)
+
+    def attachPlant(self, joints=None, wrenches=None, per_instance=False):
+        """put a plant model between the commanded torques and the resident simulator.  joints: (dof, 10) rows { gain, bias, tau_max, fv,
+        fc, v_s, q_lo, q_hi, k_stop, c_stop }, or (dof, B, 10) with per_instance; None: neutral rows with the model's joint limits and
+        k_stop = 0.  wrenches: up to 4 of (link name, point in the link frame (3), "world" or "link", values) with values { F[3], M[3],
+        p_start, p_end } of shape (8,), or (B, 8) with per_instance; six values act for ever.  A wrench acts in the periods
+        p_start <= p < p_end of plantInfo()["period"], which integrate() and every rollout period advance by one.  While attached,
+        integrate() and rolloutAsync() run the plant in front of every substep (and in front of the contact launch, if any)."""
+        B, who = self.batch_size, "attachPlant"
+        jt = None if joints is None else self._plant_table(joints, per_instance, B, self._robot.dof(), capi.SAIP_PLANT_JOINT_WORDS, who, "joints")
+        wrenches = [] if wrenches is None else list(wrenches)
+        Wn = len(wrenches)
+        links, frames = np.zeros(max(Wn, 1), np.int32), np.zeros(max(Wn, 1), np.int32)
+        points = np.zeros((max(Wn, 1), 3))
+        vals = []
+        for k, w in enumerate(wrenches):
+            if len(w) != 4:
+                raise ValueError(f"{who}: wrench {k}: (link, point, frame, values) expected")
+            links[k] = self._robot.linkIndex(w[0])
+            if links[k] < 0:
+                raise ValueError(f"{who}: wrench {k}: unknown link [{w[0]}]")
+            p = np.asarray(w[1], float).reshape(-1)
+            if p.shape != (3,):
+                raise ValueError(f"{who}: wrench {k}: a point of shape (3,) expected, got {p.shape}")
+            points[k] = p
+            if w[2] not in ("world", "link"):
+                raise ValueError(f"{who}: wrench {k}: frame 'world' or 'link' expected, got {w[2]!r}")
+            frames[k] = capi.SAIP_PLANT_FRAME_LINK if w[2] == "link" else capi.SAIP_PLANT_FRAME_WORLD
+            v = np.asarray(w[3], float)
+            if v.shape[-1:] == (6,):
+                v = np.concatenate([v, np.broadcast_to([-np.inf, np.inf], v.shape[:-1] + (2,))], axis=-1)
+            want = (B, capi.SAIP_PLANT_WRENCH_WORDS) if per_instance else (capi.SAIP_PLANT_WRENCH_WORDS,)
+            if v.shape != want:
+                raise ValueError(f"{who}: wrench {k}: values of shape {want} (or with 6 in place of 8) expected, got {v.shape}")
+            vals.append(v)
+        wt = None if Wn == 0 else self._plant_table(np.stack(vals), per_instance, B, Wn, capi.SAIP_PLANT_WRENCH_WORDS, who, "wrench values")
+        ip = C.POINTER(C.c_int)
+        self._call("saip_batch_plant_attach", None if jt is None else _dptr(jt), int(bool(per_instance)), Wn, links.ctypes.data_as(ip), _dptr(points),
+                   frames.ctypes.data_as(ip), None if wt is None else _dptr(wt), int(bool(per_instance)))
+
+    def plantInfo(self):
+        """dict per_instance_joints, n_wrenches, per_instance_wrenches, period (the period the next integration belongs to)"""
+        v = [C.c_int(0) for _ in range(3)]
+        per = C.c_longlong(0)
+        self._call("saip_batch_plant_info", C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(per))
+        return dict(per_instance_joints=bool(v[0].value), n_wrenches=v[1].value, per_instance_wrenches=bool(v[2].value), period=per.value)
+
+    def detachPlant(self):
+        self._call("saip_batch_plant_detach")
+
+    def setPlantJoints(self, joints):
+        """replace the joint table (same shape as attached); takes effect with the next launch"""
+        info = self.plantInfo()
+        a = self._plant_table(joints, info["per_instance_joints"], self.batch_size, self._robot.dof(), capi.SAIP_PLANT_JOINT_WORDS, "setPlantJoints", "joints")
+        self._call("saip_batch_plant_set_joints_host", _dptr(a))
+
+    def setPlantWrenches(self, values):
+        """replace the wrench values: (W, 8), or (W, B, 8) when attached per instance; the sites stay"""
+        info = self.plantInfo()
+        a = self._plant_table(values, info["per_instance_wrenches"], self.batch_size, info["n_wrenches"], capi.SAIP_PLANT_WRENCH_WORDS, "setPlantWrenches",
+                              "wrench values")
+        self._call("saip_batch_plant_set_wrenches_host", _dptr(a))
+
+    def randomizePlant(self, seed, round=0, joints=None, wrenches=None):
+        """draw the per-instance tables on the device: joints = (lo, hi), two (dof, 10) tables, wrenches = (lo, hi), two (W, 8) tables;
+        every word of every instance is uniform between its bounds (lo == hi: exactly lo), reproducibly for (seed, round); None leaves
+        that table alone.  Tables attached without per_instance are refused."""
+        info = self.plantInfo()
+
+        def pair(b, rows, words, what):
+            if b is None:
+                return None, None
+            lo, hi = (self._plant_table(x, False, 0, rows, words, "randomizePlant", what) for x in b)
+            return lo, hi
+        jl, jh = pair(joints, self._robot.dof(), capi.SAIP_PLANT_JOINT_WORDS, "joint bounds")
+        wl, wh = pair(wrenches, info["n_wrenches"], capi.SAIP_PLANT_WRENCH_WORDS, "wrench bounds")
+        self._call("saip_batch_plant_randomize", int(seed) & (2**64 - 1), int(round), *(None if x is None else _dptr(x) for x in (jl, jh, wl, wh)))
+
+    def setPlantPeriod(self, period):
+        """the plant's period counter (wrench windows); pair it with restoreState, since the counter is not part of a snapshot"""
+        self._call("saip_batch_plant_set_period", int(period))
+
+    def plantSummary(self):
+        """dict over the integrated substeps: friction_loss (B,) sum dt sum_j |fr_j dq_j|, max_clip (B,) the largest torque the actuator
+        limits cut off, substeps_limited (B,) substeps in which a joint clipped or a stop acted, external_work (B,) sum dt sum ext_j dq_j
+        (waits for the engine stream)"""
+        self.plantInfo()
+        out = np.empty((capi.SAIP_PLANT_SUMMARY_ROWS, self.batch_size))
+        self._call("saip_batch_plant_summary_host", _dptr(out))
+        return dict(friction_loss=out[0].copy(), max_clip=out[1].copy(), substeps_limited=out[2].astype(int), external_work=out[3].copy())
+
+    def resetPlantSummary(self):
+        self._call("saip_batch_plant_summary_reset")
+
+    def plantJointsDevice(self):
+        """device pointer of the resident joint table, (dof, 10) or (dof, 10, ld); None when detached"""
+        return capi.lib().saip_batch_plant_joints_device(self._h)
+
+    def plantWrenchesDevice(self):
+        """device pointer of the resident wrench values, (W, 8) or (W, 8, ld); None when detached or without wrenches"""
+        return capi.lib().saip_batch_plant_wrenches_device(self._h)
+
+    def plantTorquesDevice(self):
+        """device pointer of the (dof, ld) actuated torques of the last integrated substep; None when detached"""
+        return capi.lib().saip_batch_plant_torques_device(self._h)
+
+    def plantSummaryDevice(self):
+        """device pointer of the (4, ld) running summaries; None when detached"""
+        return capi.lib().saip_batch_plant_summary_device(self._h)
+
     def rewindGoalSchedules(self):
         """the period counter of the tasks' goal schedules (task.setGoalSchedule) back to 0: the next rollout starts at the first keyframe"""
         self._call("saip_batch_goal_schedule_rewind")

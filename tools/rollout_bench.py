@@ -23,7 +23,10 @@
    on the left one.
    --clearance [--clearance-spheres S] [--clearance-obstacles O] [--clearance-pairs P] times, interleaved in the same run, the closed-loop
    period without and with a clearance monitor of S link spheres, O batch-uniform obstacles (capsules, every fourth a half-space) and P self
-   pairs, and prints the event-timed mean of 200 back-to-back evaluations alone."""
+   pairs, and prints the event-timed mean of 200 back-to-back evaluations alone.
+   --plant [--plant-wrenches W] [--substeps S] times, interleaved in the same run, the closed-loop period without and with a per-instance
+   plant model (tight actuators, friction, stops at the model's limits and W payload-like wrenches, 0..4) and the event-timed mean of 200
+   one-substep integrate calls both ways: the difference is the plant launch alone."""
 import argparse
 import os
 import sys
@@ -82,6 +85,8 @@ ap.add_argument("--clearance", action="store_true")
 ap.add_argument("--clearance-spheres", type=int, default=8)
 ap.add_argument("--clearance-obstacles", type=int, default=4)
 ap.add_argument("--clearance-pairs", type=int, default=0)
+ap.add_argument("--plant", action="store_true")
+ap.add_argument("--plant-wrenches", type=int, choices=range(5), default=1)
 args = ap.parse_args()
 record = args.record_stride is not None or args.record_channels is not None or args.record_summaries
 
@@ -284,6 +289,43 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
             print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {args.substeps}: "
                   f"closed-loop period {plain:.1f} us; with a clearance monitor of {S} spheres, {O} obstacles, {P} pairs {with_c:.1f} us; without it again "
                   f"{again:.1f} us; one evaluation alone {alone:.2f} us ({under} of {B} instances under the margin)")
+        continue
+    if args.plant:
+        Wn = args.plant_wrenches
+        rng = np.random.default_rng(0)
+        table = np.repeat(ctrl.neutralPlantJoints()[:, None, :], B, axis=1)
+        table[..., 0], table[..., 1], table[..., 2] = rng.uniform(0.95, 1.05, (7, B)), rng.uniform(-0.1, 0.1, (7, B)), rng.uniform(20.0, 80.0, (7, B))
+        table[..., 3], table[..., 4], table[..., 5] = rng.uniform(0.0, 0.2, (7, B)), rng.uniform(0.0, 0.3, (7, B)), 0.05
+        table[..., 8], table[..., 9] = 500.0, 5.0
+        names = ["end-effector", "link6", "link4", "link2"]
+        wr = []
+        for w in range(Wn):
+            v = np.zeros((B, 8))
+            v[:, 2], v[:, 6:] = -9.81 * rng.uniform(0.2, 1.0, B), [-np.inf, np.inf]
+            wr.append((names[w], (0.0, 0.0, 0.05), "link" if w % 2 else "world", v))
+        timed_us, _ = stream_timer(ctrl)
+
+        def period_us():
+            t0 = time.perf_counter()
+            ctrl.rolloutAsync(K, 5e-4, args.substeps, gravity=(0, 0, 0))
+            ctrl.synchronize()
+            return (time.perf_counter() - t0) / K * 1e6
+
+        def substep_us():
+            return timed_us(lambda: ctrl.integrate(5e-4, 1, gravity=(0, 0, 0)), 200)
+
+        for _ in range(args.repeats):
+            plain, plain_s = period_us(), substep_us()
+            ctrl.attachPlant(table, wr, per_instance=True)
+            period_us()
+            with_p, with_s = period_us(), substep_us()
+            clipped = int((ctrl.plantSummary()["max_clip"] > 0).sum())
+            ctrl.detachPlant()
+            again = period_us()
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {args.substeps}: "
+                  f"closed-loop period {plain:.1f} us; with a per-instance plant model and {Wn} wrench(es) {with_p:.1f} us; without it again {again:.1f} us; "
+                  f"one substep on the stream {plain_s:.2f} us plain, {with_s:.2f} us with the plant: launch alone {with_s - plain_s:.2f} us "
+                  f"({clipped} of {B} instances clipped a torque)")
         continue
     if args.goal_schedule:
         def timed(calls, steps):
