@@ -194,7 +194,8 @@ __device__ __forceinline__ void oct_fk_frame(const ModelDev& md, const int rr, c
 
 // FULL: general control laws, partial motion-force tasks and the joint-limit-avoidance wrap compiled in; GJ: general joint task (<= 4 rows); the lean instantiation is the benchmarked default stack
 // (their mere presence costs it 1.7 % through register allocation)
-// DUO (the lean instantiation only): TWO wavefronts per group of eight instances, on two SIMDs of the CU.  Wavefront A (0) runs the inertia
+// DUO (described for the general instantiations; the lean one splits its closed form differently, see CF in the body): TWO wavefronts per
+// group of eight instances, on two SIMDs of the CU.  Wavefront A (0) runs the inertia
 // chain -- composite inertias, M(q), its factor, M^-1, T1, A, the factor of A -- and then the tail; wavefront B (1) runs, at the same
 // time, what does not need M: the branch predicate on G = J J^T and the motion-force control law, hands (singular, F) over through LDS
 // at the one workgroup barrier of the kernel and exits.  Each has its own LDS block; every other synchronisation point is
@@ -219,11 +220,19 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	constexpr bool DUO = ROLE != 0;
 	constexpr bool roleA = ROLE != 2, roleB = ROLE != 1;
 	constexpr int N = NN;
-	// Lean two-wavefront form: B does not wait where A takes the Jacobian from it -- A polls a flag in LDS instead of both meeting at a workgroup
-	// barrier (B was there 1.3 k clocks early) -- and B uses the time it gains to form the rows of A = T1 J^T from the T1 that A publishes
-	// (second flag), which takes the second half of the T1 / A phase off A's chain: 7.04 -> 6.91 us (same session).
-	// The flags live in LDS, are zeroed behind one early workgroup barrier, and every poll loop is bounded.
-	constexpr bool BROWS = DUO && !FULL && GJ == 0;
+	// Lean headline stack (full 6-dof task on 7 joints + full joint task, the non-singular branch): the torques in closed form, DESIGN.md 4.1.
+	// null(J) is a line spanned by z; with G = J J^T, w = J^T G^-1 F_um, p = M z, mu = z.p, s = M^-1 z and C the bounded-inertia clamp,
+	//   tau_1 = M_x (w - z (z^T M_x w) / (z^T M_x z)),  M_x = M | M + C  (impedance: J^T F_um),
+	//   tau   = tau_1 + p ((z.ddq_d - s.tau_1) + rho z.f) / |z|^2,  rho = 1 | |z|^2 / mu | mu / (mu - z^T C z + (C z)^T M_BIE^-1 (C z)).
+	// Nothing of T1 = J M^-1, A = J M^-1 J^T or its factor is needed: what depends on J alone (G, its factor, w, z) is wavefront B's, what
+	// depends on M (p, M_x w, s, the sums) wavefront A's.  Only the blended singularity strategies still want T1 and A: formed on request.
+	constexpr bool CF = !FULL && GJ == 0;
+	// Lean two-wavefront form: the wavefronts talk through three flags in LDS instead of meeting at workgroup barriers.  Flag 0: B's Jacobian
+	// and its Cholesky factor of G are in its block (A forms z with them while B goes on with w and the certificates); flag 1: B's hand-over
+	// (w, the branch predicate) -- value 2 when some instance of the wavefront enters the blended strategies, which tells A to form T1 and
+	// A for B (flag 2: they are in A's block) and to meet B at the one workgroup barrier behind the blended block; both wavefronts decide
+	// about that barrier from the same word.  The flags are zeroed behind one early workgroup barrier, and every poll loop is bounded.
+	constexpr bool BROWS = DUO && CF;
 	auto flag_wait = [&](const int k) {
 		int it = 0, v = 0;
 		while ((v = __hip_atomic_load(wgflags + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0 && ++it < 200000) __builtin_amdgcn_s_sleep(1);
@@ -495,10 +504,8 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			fi_pre = -jkp_r * e - jkv_r * (dq_r - jg_dq) - jki_r * ie;  // :342-345
 		}
 	}
-	if (BROWS) {
-		if (ROLE == 2) flag_set(0, 1);  // B: the Jacobian is in its block
-		oct_sync<DUO>();
-	} else if (DUO && !trunc_mode) __syncthreads();  // workgroup barrier: B's Jacobian is complete (A arrives ~1 k clocks after B)
+	if (BROWS) oct_sync<DUO>();  // (closed form: A does not take the Jacobian)
+	else if (DUO && !trunc_mode) __syncthreads();  // workgroup barrier: B's Jacobian is complete (A arrives ~1 k clocks after B)
 	else oct_sync<DUO>();                     // (reduced tasks: A waits further down, for the Jacobian B has reduced)
 	STAMP(3);
 	// ---------------------------------------------------------------- M^-1: Cholesky factor in every lane, own column of the inverse
@@ -541,13 +548,17 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			UNR for (int j = 0; j < N; j++) mb[j] = mi[j];
 		}
 	}
-	if (ROLE == 1) {
-		UNR for (int j = 0; j < N; j++) sm.N1[r][j] = mi[j];
-	}
 	const bool rank1_bie = P.any_bie && !general_bie;
-	if (roleA && rank1_bie && r == eclamp) {
-		UNR for (int j = 0; j < N; j++) sm.vec[3][j] = mi[j];  // column e of M^-1 for the whole instance (read after the next barrier)
-	}
+	// what the T1 / A phase and the blended block read of M^-1 through LDS (closed form: stored only when the blended block asks for T1 / A)
+	auto park_minv = [&]() {
+		if (ROLE == 1) {
+			UNR for (int j = 0; j < N; j++) sm.N1[r][j] = mi[j];
+		}
+		if (roleA && rank1_bie && r == eclamp) {
+			UNR for (int j = 0; j < N; j++) sm.vec[3][j] = mi[j];  // column e of M^-1 for the whole instance (read after the next barrier)
+		}
+	};
+	if (!CF) park_minv();
 	STAMP(4);
 	double Jf[6][N];
 	unsigned keep_bits_b = 0x3fu;
@@ -555,9 +566,10 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		__syncthreads();
 		keep_bits_b = (unsigned)smB.vec[6][7];
 	}
-	if (BROWS && ROLE == 1) lost = flag_wait(0) == 0;
-	UNR for (int a = 0; a < 6; a++)
-		UNR for (int j = 0; j < N; j++) Jf[a][j] = (ROLE == 1 ? smB : sm).J[a][j];
+	if (!(BROWS && ROLE == 1)) {  // (closed form: wavefront A needs the Jacobian only when the blended block asks it for T1 / A)
+		UNR for (int a = 0; a < 6; a++)
+			UNR for (int j = 0; j < N; j++) Jf[a][j] = (ROLE == 1 ? smB : sm).J[a][j];
+	}
 	double vw[6] = {0, 0, 0, 0, 0, 0};
 	if (roleB) {
 		double dqa[N];
@@ -572,12 +584,129 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		}
 	}
 	STAMP(5);
+	double Fum6[6], Ff6[6] = {0, 0, 0, 0, 0, 0};  // GJ == 0: the task forces, identical in every lane of the instance
 	STAMP(6);
 	// ---- SingularityHandler branch predicate on G = J J^T (N_prec = I for the first task), every lane of the instance alike
 	bool singular = false, truncated = false, blended_i = false;
 	const bool strategies_on = GJ == 0 && mf.sing_handling && mf.sing_strategies && mf.sh != nullptr;  // batch-uniform; the blended branch lives in the headline stack's tail
 	double G[6][6], U6[6][6];
 	bool keepm[6] = {true, true, true, true, true, true};
+	double LG[6][6], dG[6];  // closed form: the Cholesky factor of G itself (the certificates below factor shifted copies)
+	double zcf[N] = {}, wcf[N] = {}, zzcf = 0.0;  // closed form: z, w (impedance: tau_1 itself) in full in every lane, |z|^2
+	// closed form: z from the Euclidean projector Pn = I - J^T G^-1 J = z z^T / |z|^2, with this lane's column of J and the factor of G.  Pn is
+	// idempotent, so the squared norm of its row rr is its diagonal entry 1 - j_rr . G^-1 j_rr; the lane with the largest one broadcasts its
+	// solve, every lane forms its own entry of that row (= column: Pn is symmetric), and the entries are gathered.  (Run by the wavefront
+	// that goes on with M: the only one, or A with B's factor and Jacobian.  The whole Jacobian is not needed.)
+	auto form_z = [&](const double (&Lg)[6][6], const double (&dg)[6]) {
+		double jc6[6], x6[6], xb[6], prr = 1.0;
+		UNR for (int a = 0; a < 6; a++) jc6[a] = (ROLE == 1 ? smB : sm).J[a][rr];
+		oct_solve<6>(Lg, dg, jc6, x6);
+		UNR for (int a = 0; a < 6; a++) prr = fma(-jc6[a], x6[a], prr);
+		double bestw = act ? prr : -1.0;
+		int jbw = r;
+#define OCT_ARGMAX_STEP(CTRL)                                                                                   \
+	{                                                                                                           \
+		const double ob = oct_dpp<CTRL>(bestw);                                                                 \
+		const int oj = __builtin_amdgcn_update_dpp(0, jbw, CTRL, 0xF, 0xF, true);                               \
+		const bool take = ob > bestw || (ob == bestw && oj < jbw);                                              \
+		bestw = take ? ob : bestw;                                                                              \
+		jbw = take ? oj : jbw;                                                                                  \
+	}
+		OCT_ARGMAX_STEP(OCT_BFLY0)
+		OCT_ARGMAX_STEP(OCT_BFLY1)
+		OCT_ARGMAX_STEP(OCT_BFLY2)
+#undef OCT_ARGMAX_STEP
+		const int src = octl_src(lane, jbw);
+		UNR for (int a = 0; a < 6; a++) xb[a] = __shfl(x6[a], src);
+		double z_own = (rr == jbw) ? 1.0 : 0.0;
+		UNR for (int a = 0; a < 6; a++) z_own = fma(-jc6[a], xb[a], z_own);
+		UNR for (int j = 0; j < N; j++) {
+			zcf[j] = __shfl(z_own, octl_src(lane, j));
+			zzcf = fma(zcf[j], zcf[j], zzcf);
+		}
+	};
+	// ---- control law (MotionForceTask.cpp:286-509 with sigma_force = sigma_moment = 0, OTG off), every lane alike
+	auto run_law = [&]() {
+		double ip[3] = {0, 0, 0}, io[3] = {0, 0, 0}, Fum[6], G24[24];
+		UNR for (int e = 0; e < 24; e++) G24[e] = sm.vec[10 + (e >> 3)][e & 7];
+		if (track_mf) {
+			UNR for (int i = 0; i < 3; i++) {
+				ip[i] = sm.ist[i];
+				io[i] = sm.ist[3 + i];
+			}
+		}
+		if (FULL && mf.general_law) {
+			// velocity saturation and / or force & moment spaces (open-loop force control): the shared general law, MotionForceTask.cpp:306-487
+			double G30[30], Ff[6] = {0, 0, 0, 0, 0, 0};
+			UNR for (int e = 0; e < 24; e++) G30[e] = G24[e];
+			UNR for (int e = 0; e < 6; e++) G30[24 + e] = sm.vec[5][e];
+			law_motion_force_general<false>(&mf, vw, pw, Rc, G30, ip, io, (double*)nullptr, Fum, Ff);
+			UNR for (int a = 0; a < 6; a++) Ff6[a] = Ff[a];
+		} else if (FULL && !mf.bm_identity) {
+			// partial task: the short law with its projections (MotionForceTask.cpp:286-509 with sigma_force = sigma_moment = 0), then
+			// F in the basis of range(P): fhat = Bm^T F_um
+			double v[3], w[3], e3[3], tmp[3], Fw[6];
+			UNR for (int i = 0; i < 3; i++) {
+				v[i] = lawc[36 + 3 * i] * vw[0] + lawc[36 + 3 * i + 1] * vw[1] + lawc[36 + 3 * i + 2] * vw[2];
+				w[i] = lawc[45 + 3 * i] * vw[3] + lawc[45 + 3 * i + 1] * vw[4] + lawc[45 + 3 * i + 2] * vw[5];
+			}
+			UNR for (int i = 0; i < 3; i++) e3[i] = pw[i] - G24[i];
+			UNR for (int i = 0; i < 3; i++) ip[i] += (lawc[54 + 3 * i] * e3[0] + lawc[54 + 3 * i + 1] * e3[1] + lawc[54 + 3 * i + 2] * e3[2]) * mf.dt;
+			UNR for (int i = 0; i < 3; i++) tmp[i] = G24[18 + i] - lawc[72 + i] * e3[i] - lawc[75 + i] * (v[i] - G24[12 + i]) - lawc[78 + i] * ip[i];
+			UNR for (int i = 0; i < 3; i++) Fw[i] = lawc[54 + 3 * i] * tmp[0] + lawc[54 + 3 * i + 1] * tmp[1] + lawc[54 + 3 * i + 2] * tmp[2];
+			double oe[3] = {0, 0, 0};
+			UNR for (int c = 0; c < 3; c++) {
+				const double a0 = Rc[c], a1 = Rc[3 + c], a2 = Rc[6 + c], b0 = G24[3 + c], b1 = G24[6 + c], b2 = G24[9 + c];
+				oe[0] -= 0.5 * (a1 * b2 - a2 * b1);
+				oe[1] -= 0.5 * (a2 * b0 - a0 * b2);
+				oe[2] -= 0.5 * (a0 * b1 - a1 * b0);
+			}
+			double dphi[3];
+			UNR for (int i = 0; i < 3; i++) dphi[i] = lawc[63 + 3 * i] * oe[0] + lawc[63 + 3 * i + 1] * oe[1] + lawc[63 + 3 * i + 2] * oe[2];
+			UNR for (int i = 0; i < 3; i++) io[i] += dphi[i] * mf.dt;
+			UNR for (int i = 0; i < 3; i++) tmp[i] = G24[21 + i] - lawc[81 + i] * dphi[i] - lawc[84 + i] * (w[i] - G24[15 + i]) - lawc[87 + i] * io[i];
+			UNR for (int i = 0; i < 3; i++) Fw[3 + i] = lawc[63 + 3 * i] * tmp[0] + lawc[63 + 3 * i + 1] * tmp[1] + lawc[63 + 3 * i + 2] * tmp[2];
+			UNR for (int a = 0; a < 6; a++) {
+				double sf = 0.0;
+				UNR for (int e = 0; e < 6; e++) sf = fma(lawc[0 + e * 6 + a], Fw[e], sf);
+				Fum[a] = sf;
+			}
+		} else {
+		// full 6-dof task without force space: the task projections and sigma_position / sigma_orientation are identities (oct_eligible)
+		double e3[3];
+		UNR for (int i = 0; i < 3; i++) e3[i] = pw[i] - G24[i];
+		UNR for (int i = 0; i < 3; i++) ip[i] = fma(e3[i], mf.dt, ip[i]);
+		UNR for (int i = 0; i < 3; i++) Fum[i] = G24[18 + i] - mf.kp_pos[i] * e3[i] - mf.kv_pos[i] * (vw[i] - G24[12 + i]) - mf.ki_pos[i] * ip[i];
+		double oe[3] = {0, 0, 0};  // orientationError(desired, current) = -1/2 sum_c Rc[:,c] x Rd[:,c]
+		UNR for (int c = 0; c < 3; c++) {
+			const double a0 = Rc[c], a1 = Rc[3 + c], a2 = Rc[6 + c], b0 = G24[3 + c], b1 = G24[6 + c], b2 = G24[9 + c];
+			oe[0] -= 0.5 * (a1 * b2 - a2 * b1);
+			oe[1] -= 0.5 * (a2 * b0 - a0 * b2);
+			oe[2] -= 0.5 * (a0 * b1 - a1 * b0);
+		}
+		UNR for (int i = 0; i < 3; i++) io[i] = fma(oe[i], mf.dt, io[i]);
+		UNR for (int i = 0; i < 3; i++) Fum[3 + i] = G24[21 + i] - mf.kp_ori[i] * oe[i] - mf.kv_ori[i] * (vw[3 + i] - G24[15 + i]) - mf.ki_ori[i] * io[i];
+		}
+		if (track_mf && r == 0) {  // left in LDS: committed in the epilogue once the final status is known (the joint task may still flag the instance)
+			UNR for (int i = 0; i < 3; i++) {
+				sm.ist[i] = ip[i];
+				sm.ist[3 + i] = io[i];
+			}
+		}
+		if (trunc_mode) {  // task_range_ns^T F_um (SingularityHandler.cpp:321-322); the identity for instances that were not reduced
+			double fh[6];
+			UNR for (int a = 0; a < 6; a++) {
+				double sf = 0.0;
+				UNR for (int i = 0; i < 6; i++) sf = fma(U6[i][a], Fum[i], sf);
+				fh[a] = keepm[a] ? sf : 0.0;
+			}
+			UNR for (int a = 0; a < 6; a++) Fum[a] = fh[a];
+		}
+		UNR for (int a = 0; a < 6; a++) Fum6[a] = Fum[a];
+	};
+	// (closed form: the law does not depend on G -- it runs here, one basic block with G, the certificate and the factor of G, so that its
+	// loads and short chains fill the issue slots the factorisations leave)
+	if (roleB && CF) run_law();
 	if (roleB) {
 		double tr = 0.0;
 		UNR for (int a = 0; a < 6; a++)
@@ -588,6 +717,40 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 				G[c][a] = s;
 				if (a == c) tr += s;
 			}
+		if (CF) {
+			// the factor of G, w and (one-wavefront form) z here: with the law above they are one basic block with the certificate's LDL^T
+			// below -- independent dependent chains that fill each other's waits.  (Pinned: left alone, the compiler sinks all of it behind
+			// the certificate's branches, next to its first use.)
+			UNR for (int a = 0; a < 6; a++)
+				UNR for (int c = 0; c <= a; c++) LG[a][c] = G[a][c];
+			oct_cholesky<6>(LG, dG);
+			if (ROLE == 2) {  // two-wavefront form: A forms z with this factor while B goes on with w and the certificates
+				if (r == 0) {
+					UNR for (int a = 0; a < 6; a++) {
+						UNR for (int c = 0; c <= a; c++) sm.Lam[a][c] = LG[a][c];
+						sm.Lam[6][a] = dG[a];
+					}
+				}
+				flag_set(0, 1);
+			}
+			double y6[6];
+			if (mf_dec == DEC_IMPEDANCE) {
+				UNR for (int a = 0; a < 6; a++) y6[a] = Fum6[a];
+			} else {
+				oct_solve<6>(LG, dG, Fum6, y6);
+			}
+			UNR for (int j = 0; j < N; j++) {
+				double s = 0.0;
+				UNR for (int a = 0; a < 6; a++) s = fma(Jf[a][j], y6[a], s);
+				wcf[j] = s;
+			}
+			if (ROLE == 0) form_z(LG, dG);
+			UNR for (int j = 0; j < N; j++) {
+				if (ROLE == 0) asm volatile("" : "+v"(zcf[j]));
+				asm volatile("" : "+v"(wcf[j]));
+			}
+			if (ROLE == 0) asm volatile("" : "+v"(zzcf));
+		}
 		const double itr = oct_rcp(tr);
 		const double smax2 = mf.s_max * mf.s_max, tol2 = mf.s_abs_tol * mf.s_abs_tol;
 		auto ldl_positive = [&](const double shift) {
@@ -753,7 +916,8 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	const int ra = r < 6 ? r : 5;
 	UNR for (int a = 0; a < 6; a++) keep_ra = (a == ra) ? (keepm[a] && a < kmf) : keep_ra;
 	double t1c[6] = {0, 0, 0, 0, 0, 0};
-	if (roleA) {
+	// (closed form: not part of the ordinary path -- run by wavefront A / the one wavefront only when the blended block wants T1 and A)
+	auto form_t1_a = [&]() {
 		double tbc[6];
 		UNR for (int a = 0; a < 6; a++) {
 			double s1 = 0.0, s2 = 0.0;
@@ -768,8 +932,6 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			sm.T1[a][r] = t1c[a];
 			if (general_bie) sm.Lam[a][r] = tbc[a];
 		}
-		const bool rows_by_b = BROWS && ROLE == 1 && !general_bie;
-		if (BROWS && ROLE == 1) flag_set(1, general_bie ? 2 : 1);
 		oct_sync<DUO>();
 		if (rank1_bie) {
 			double mee = 0.0;
@@ -784,7 +946,6 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			t1[j] = sm.T1[ra][j];
 			tb[j] = general_bie ? sm.Lam[ra][j] : 0.0;
 		}
-		if (!rows_by_b) {
 		UNR for (int c = 0; c < 6; c++) {
 			double s = 0.0, s2 = 0.0;
 			UNR for (int j = 0; j < N; j++) {
@@ -794,7 +955,6 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			const bool padrow = FULL && !keep_ra && c == ra;  // zero row of a partial / reduced task: keep the factorisation regular
 			sm.A[r][c] = padrow ? 1.0 : s;
 			if (general_bie) sm.Am[r][c] = padrow ? 1.0 : s2;
-		}
 		}
 		if (ROLE == 1) {  // what the blended block (run by B) wants from this wavefront besides A, T1, M and the columns of M^-1
 			if (general_bie) {
@@ -807,14 +967,15 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			}
 		}
 		oct_sync<DUO>();
-	}
+	};
+	if (roleA && !CF) form_t1_a();
 	STAMP(8);
 	double lam[6], lmod[6];
 	// headline stack (GJ == 0): nobody needs Lambda itself, only its action on three vectors -- every lane keeps the Cholesky factor of
 	// A = J M^-1 J^T and solves (no row of the inverse, no exchange of Lambda between the lanes)
 	double L6[6][6], dinv6[6];
 	if (GJ == 0) {
-		if (!DUO) {
+		if (!DUO && !CF) {
 			UNR for (int i = 0; i < 6; i++)
 				UNR for (int j = 0; j <= i; j++) L6[i][j] = sm.A[i][j];
 			oct_cholesky<6>(L6, dinv6);
@@ -857,87 +1018,8 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		UNR for (int c = 0; c < 6; c++) sm.Lam[r][c] = lam[c];
 	}
 	STAMP(9);
-	double Fum6[6], Ff6[6] = {0, 0, 0, 0, 0, 0};  // GJ == 0: the task forces, identical in every lane of the instance
-	// ---- control law (MotionForceTask.cpp:286-509 with sigma_force = sigma_moment = 0, OTG off), every lane alike
-	if (roleB) {
-		double ip[3] = {0, 0, 0}, io[3] = {0, 0, 0}, Fum[6], G24[24];
-		UNR for (int e = 0; e < 24; e++) G24[e] = sm.vec[10 + (e >> 3)][e & 7];
-		if (track_mf) {
-			UNR for (int i = 0; i < 3; i++) {
-				ip[i] = sm.ist[i];
-				io[i] = sm.ist[3 + i];
-			}
-		}
-		if (FULL && mf.general_law) {
-			// velocity saturation and / or force & moment spaces (open-loop force control): the shared general law, MotionForceTask.cpp:306-487
-			double G30[30], Ff[6] = {0, 0, 0, 0, 0, 0};
-			UNR for (int e = 0; e < 24; e++) G30[e] = G24[e];
-			UNR for (int e = 0; e < 6; e++) G30[24 + e] = sm.vec[5][e];
-			law_motion_force_general<false>(&mf, vw, pw, Rc, G30, ip, io, (double*)nullptr, Fum, Ff);
-			UNR for (int a = 0; a < 6; a++) Ff6[a] = Ff[a];
-		} else if (FULL && !mf.bm_identity) {
-			// partial task: the short law with its projections (MotionForceTask.cpp:286-509 with sigma_force = sigma_moment = 0), then
-			// F in the basis of range(P): fhat = Bm^T F_um
-			double v[3], w[3], e3[3], tmp[3], Fw[6];
-			UNR for (int i = 0; i < 3; i++) {
-				v[i] = lawc[36 + 3 * i] * vw[0] + lawc[36 + 3 * i + 1] * vw[1] + lawc[36 + 3 * i + 2] * vw[2];
-				w[i] = lawc[45 + 3 * i] * vw[3] + lawc[45 + 3 * i + 1] * vw[4] + lawc[45 + 3 * i + 2] * vw[5];
-			}
-			UNR for (int i = 0; i < 3; i++) e3[i] = pw[i] - G24[i];
-			UNR for (int i = 0; i < 3; i++) ip[i] += (lawc[54 + 3 * i] * e3[0] + lawc[54 + 3 * i + 1] * e3[1] + lawc[54 + 3 * i + 2] * e3[2]) * mf.dt;
-			UNR for (int i = 0; i < 3; i++) tmp[i] = G24[18 + i] - lawc[72 + i] * e3[i] - lawc[75 + i] * (v[i] - G24[12 + i]) - lawc[78 + i] * ip[i];
-			UNR for (int i = 0; i < 3; i++) Fw[i] = lawc[54 + 3 * i] * tmp[0] + lawc[54 + 3 * i + 1] * tmp[1] + lawc[54 + 3 * i + 2] * tmp[2];
-			double oe[3] = {0, 0, 0};
-			UNR for (int c = 0; c < 3; c++) {
-				const double a0 = Rc[c], a1 = Rc[3 + c], a2 = Rc[6 + c], b0 = G24[3 + c], b1 = G24[6 + c], b2 = G24[9 + c];
-				oe[0] -= 0.5 * (a1 * b2 - a2 * b1);
-				oe[1] -= 0.5 * (a2 * b0 - a0 * b2);
-				oe[2] -= 0.5 * (a0 * b1 - a1 * b0);
-			}
-			double dphi[3];
-			UNR for (int i = 0; i < 3; i++) dphi[i] = lawc[63 + 3 * i] * oe[0] + lawc[63 + 3 * i + 1] * oe[1] + lawc[63 + 3 * i + 2] * oe[2];
-			UNR for (int i = 0; i < 3; i++) io[i] += dphi[i] * mf.dt;
-			UNR for (int i = 0; i < 3; i++) tmp[i] = G24[21 + i] - lawc[81 + i] * dphi[i] - lawc[84 + i] * (w[i] - G24[15 + i]) - lawc[87 + i] * io[i];
-			UNR for (int i = 0; i < 3; i++) Fw[3 + i] = lawc[63 + 3 * i] * tmp[0] + lawc[63 + 3 * i + 1] * tmp[1] + lawc[63 + 3 * i + 2] * tmp[2];
-			UNR for (int a = 0; a < 6; a++) {
-				double sf = 0.0;
-				UNR for (int e = 0; e < 6; e++) sf = fma(lawc[0 + e * 6 + a], Fw[e], sf);
-				Fum[a] = sf;
-			}
-		} else {
-		// full 6-dof task without force space: the task projections and sigma_position / sigma_orientation are identities (oct_eligible)
-		double e3[3];
-		UNR for (int i = 0; i < 3; i++) e3[i] = pw[i] - G24[i];
-		UNR for (int i = 0; i < 3; i++) ip[i] = fma(e3[i], mf.dt, ip[i]);
-		UNR for (int i = 0; i < 3; i++) Fum[i] = G24[18 + i] - mf.kp_pos[i] * e3[i] - mf.kv_pos[i] * (vw[i] - G24[12 + i]) - mf.ki_pos[i] * ip[i];
-		double oe[3] = {0, 0, 0};  // orientationError(desired, current) = -1/2 sum_c Rc[:,c] x Rd[:,c]
-		UNR for (int c = 0; c < 3; c++) {
-			const double a0 = Rc[c], a1 = Rc[3 + c], a2 = Rc[6 + c], b0 = G24[3 + c], b1 = G24[6 + c], b2 = G24[9 + c];
-			oe[0] -= 0.5 * (a1 * b2 - a2 * b1);
-			oe[1] -= 0.5 * (a2 * b0 - a0 * b2);
-			oe[2] -= 0.5 * (a0 * b1 - a1 * b0);
-		}
-		UNR for (int i = 0; i < 3; i++) io[i] = fma(oe[i], mf.dt, io[i]);
-		UNR for (int i = 0; i < 3; i++) Fum[3 + i] = G24[21 + i] - mf.kp_ori[i] * oe[i] - mf.kv_ori[i] * (vw[3 + i] - G24[15 + i]) - mf.ki_ori[i] * io[i];
-		}
-		if (track_mf && r == 0) {  // left in LDS: committed in the epilogue once the final status is known (the joint task may still flag the instance)
-			UNR for (int i = 0; i < 3; i++) {
-				sm.ist[i] = ip[i];
-				sm.ist[3 + i] = io[i];
-			}
-		}
-		if (trunc_mode) {  // task_range_ns^T F_um (SingularityHandler.cpp:321-322); the identity for instances that were not reduced
-			double fh[6];
-			UNR for (int a = 0; a < 6; a++) {
-				double sf = 0.0;
-				UNR for (int i = 0; i < 6; i++) sf = fma(U6[i][a], Fum[i], sf);
-				fh[a] = keepm[a] ? sf : 0.0;
-			}
-			UNR for (int a = 0; a < 6; a++) Fum[a] = fh[a];
-		}
-		UNR for (int a = 0; a < 6; a++) Fum6[a] = Fum[a];
-	}
-	if (DUO) {
+	if (roleB && !CF) run_law();
+	if (DUO && !CF) {
 		// first workgroup barrier: B publishes the task force (and, for the stacks whose tail it does not share, the branch predicate); A has
 		// left A = J M^-1 J^T, T1 and M^-1 in its block
 		if (ROLE == 2) {
@@ -951,19 +1033,6 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 				sm.vec[5][r] = ffo;
 			}
 			if (r == 6) sm.vec[6][6] = (singular ? 1.0 : 0.0) + (truncated ? 2.0 : 0.0);
-		}
-		if (BROWS && ROLE == 2) {
-			const int f1 = flag_wait(1);
-			lost = f1 == 0;
-			if (f1 == 1) {  // the rows of A = T1 J^T, into A's block
-				double t1[N];
-				UNR for (int j = 0; j < N; j++) t1[j] = smA.T1[ra][j];
-				UNR for (int c = 0; c < 6; c++) {
-					double s = 0.0;
-					UNR for (int j = 0; j < N; j++) s = fma(t1[j], Jf[c][j], s);
-					smA.A[r][c] = s;
-				}
-			}
 		}
 		STAMP(29);
 		__syncthreads();
@@ -1014,6 +1083,106 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		double g[6];
 		double wr = 0.0;
 		tau_r = 0.0;
+		double v[N] = {}, zr = 0.0, v_own = 0.0, zz = 0.0, zv = 0.0;
+		double fi = 0.0;
+		double tvo = 0.0;
+		bool ovr = false;
+		int hand = 1;  // two-wavefront closed form: the word of B's hand-over (2: the blended block runs)
+		if (CF) {
+			// ---- closed form (see the top of the body).  v = z in full in every lane, wv = w (impedance: tau_1 itself)
+			double wv[N] = {};
+			if (roleB) {  // (formed next to G, ahead of the certificates)
+				UNR for (int j = 0; j < N; j++) wv[j] = wcf[j];
+			}
+			if (ROLE == 2) {
+				// B's hand-over: one flag, no barrier.  The blended block needs T1 and A = J M^-1 J^T from A: asked for with the same word
+				hand = (strategies_on && __any(singular)) ? 2 : 1;
+				if (r == 0) {
+					UNR for (int j = 0; j < N; j++) sm.vec[8][j] = wv[j];
+				}
+				sm.vec[2][r] = singular ? 2.0 : 0.0;
+				STAMP(29);
+				flag_set(1, hand);
+			}
+			if (ROLE == 1) {  // z from B's factor of G and B's Jacobian, while B forms w
+				double Lg[6][6], dg[6];
+				if (flag_wait(0) == 0) lost = true;
+				STAMP(12);
+				UNR for (int a = 0; a < 6; a++) {
+					UNR for (int c = 0; c <= a; c++) Lg[a][c] = smB.Lam[a][c];
+					dg[a] = smB.Lam[6][a];
+				}
+				form_z(Lg, dg);
+			}
+			// what needs z only
+			double mrow[N], pr = 0.0, sr = 0.0, z_r = 0.0, mrr = 0.0, mi_rr = 0.0, c_r = 0.0, cm = 0.0, mxz = 0.0, s2 = 1.0, mu = 1.0, rho = 1.0;
+			if (roleA) {
+				UNR for (int j = 0; j < N; j++) v[j] = zcf[j];
+				zz = zzcf;
+				UNR for (int j = 0; j < N; j++) mrow[j] = (j <= rr) ? sm.M[rr][j] : sm.M[j][rr];  // row rr of the symmetric M (lower triangle stored)
+				UNR for (int j = 0; j < N; j++) {
+					pr = fma(mrow[j], v[j], pr);   // p_r = (M z)_r
+					sr = fma(mi[j], v[j], sr);     // s_r = (M^-1 z)_r
+					z_r = (j == rr) ? v[j] : z_r;
+					mrr = (j == rr) ? mrow[j] : mrr;
+					mi_rr = (j == rr) ? mi[j] : mi_rr;
+				}
+				c_r = P.any_bie ? fmax(P.bie_thr - mrr, 0.0) : 0.0;  // the bounded-inertia clamp of this joint: M_BIE = M + C
+				cm = (mf_dec == DEC_BIE) ? c_r : 0.0;
+				mxz = fma(cm, z_r, pr);
+				const double zl = act ? z_r : 0.0;
+				s2 = octl_sum(zl * mxz);
+				mu = octl_sum(zl * pr);
+				if (jt_dec == DEC_IMPEDANCE) {
+					rho = zz * oct_rcp(mu);
+				} else if (jt_dec == DEC_BIE) {
+					if (general_bie) {  // several clamped entries somewhere in the wavefront: (C z)^T M_BIE^-1 (C z) from this lane's column of M_BIE^-1
+						double zcz = 0.0, mbcz = 0.0;
+						UNR for (int j = 0; j < N; j++) {
+							const double czj = fmax(P.bie_thr - sm.M[j][j], 0.0) * v[j];
+							zcz = fma(czj, v[j], zcz);
+							mbcz = fma(mb[j], czj, mbcz);
+						}
+						const double qb = octl_sum(act ? c_r * z_r * mbcz : 0.0);
+						rho = mu * oct_rcp(mu - zcz + qb);
+					} else {  // at most one clamped entry e: z^T C z - (C z)^T M_BIE^-1 (C z) = beta z_e^2, beta = c / (1 + c (M^-1)_ee)
+						const double mee = __shfl(mi_rr, octl_src(lane, eclamp));
+						const double bcf = cclamp * oct_rcp(fma(cclamp, mee, 1.0));
+						double ze = 0.0;
+						UNR for (int j = 0; j < N; j++) ze = (j == eclamp) ? v[j] : ze;
+						rho = mu * oct_rcp(fma(-bcf * ze, ze, mu));
+					}
+				}
+			}
+			if (ROLE == 1) {
+				STAMP(13);
+				hand = __builtin_amdgcn_readfirstlane(flag_wait(1));
+				STAMP(30);
+				lost = lost || hand == 0;
+				UNR for (int j = 0; j < N; j++) wv[j] = smB.vec[8][j];
+				singular = ((int)smB.vec[2][r] & 2) != 0;
+				if (__builtin_expect(hand == 2, 0)) {  // today's T1 / A phase, for the blended block that B runs; in addition to the closed form
+					UNR for (int a = 0; a < 6; a++)
+						UNR for (int j = 0; j < N; j++) Jf[a][j] = smB.J[a][j];
+					park_minv();
+					form_t1_a();
+					flag_set(2, 1);
+				}
+			}
+			if (roleA) {
+				double mw = 0.0, w_r = 0.0;
+				UNR for (int j = 0; j < N; j++) {
+					mw = fma(mrow[j], wv[j], mw);  // (M w)_r
+					w_r = (j == rr) ? wv[j] : w_r;
+				}
+				const double mxw = fma(cm, w_r, mw);
+				const double s1 = octl_sum(act ? z_r * mxw : 0.0);
+				tau_r = (mf_dec == DEC_IMPEDANCE) ? w_r : fma(-mxz, s1 * oct_rcp(s2), mxw);
+				fi = fi_pre;  // (the joint control law ran behind M(q), see fi_pre)
+				const double sj = octl_sum(act ? fma(rho * z_r, fi, fma(z_r, jg_ddq, -sr * tau_r)) : 0.0);
+				tv = fma(pr * oct_rcp(zz), sj, tau_r);
+			}
+		} else {
 		if (roleA) {
 		if (mf_dec == DEC_IMPEDANCE) {
 			UNR for (int a = 0; a < 6; a++) g[a] = Fum6[a] + Ff6[a];
@@ -1062,7 +1231,6 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		//   tau_joint = Jh^T (Lambda a1 + Lambda_mod b1) = v / |z'|^2 (z'.a + rho z'.f),   a = ddq_d - M^-1 tau_prec, f = the PD(I) force,
 		// rho = Lambda_mod / Lambda: 1 (full decoupling), |z'|^2 / z'.v (impedance), z'.v / (z'.v - beta z'_e^2) (bounded inertia, one
 		// clamped entry e: M_BIE^-1 = M^-1 - beta m m^T and m^T M z' = z'_e), z'.v / (v^T M_BIE^-1 v) (several clamped entries).
-		double v[N] = {}, zr = 0.0, v_own = 0.0, zz = 0.0, zv = 0.0;
 		if (roleB) {
 		double x6[6], rowv[N], nr = 0.0;
 		oct_solve<6>(L6, dinv6, t1c, x6);
@@ -1096,12 +1264,9 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		zz = octl_sum(zr * zr);
 		zv = octl_sum(zr * v_own);
 		}  // roleB
-		double fi = 0.0;
 		if (roleA) {
 		fi = fi_pre;  // (the joint control law ran behind M(q), see fi_pre)
 		}
-		double tvo = 0.0;
-		bool ovr = false;
 		if (ROLE == 0) {
 		const double ai = jg_ddq - wr;
 		const double za = octl_sum(zr * ai);
@@ -1125,6 +1290,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		}
 		tv = fma(v_own * oct_rcp(zz), fma(rho, zf, za), tau_r);  // tau += Jh^T g
 		}
+		}  // !CF
 		// ------------------------------------------------------------------------------------------------------------------------------
 		// Blended singularity strategies, in this kernel (SingularityHandler.cpp:100-121, 146-228, 230-295, 310-367; the reference's default
 		// whenever the task is inside its singularity bounds).  Only wavefronts that hold such an instance come here.  Everything happens
@@ -1134,9 +1300,17 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		//   posture Jacobian V_s^T N_ns = D^-1 (J_S - A_SK Lambda_ns J_K), its op-space inertia = D^-1 (Schur complement of A_u) D^-1,
 		//   N = N_js N_ns projects onto null(J) again, so the joint task behind keeps its closed rank-one form with z from U.
 		if (ROLE != 1 && __builtin_expect(strategies_on && __any(singular), 0)) {
+			if (CF && ROLE == 0) {  // closed form: T1 and A = J M^-1 J^T exist only for this block
+				park_minv();
+				form_t1_a();
+			}
 			if (ROLE == 2) {
 				// wavefront B runs the block in the two-wavefront form (it is off A's critical path and A's registers stay out of it): what the
 				// ordinary path left in A's block, and the joint task's goal and control law once more (no shadow integrator store here: A's)
+				if (CF) {  // (closed form: A forms T1 and A on B's request and says when they are there)
+					if (flag_wait(2) == 0) lost = true;
+					UNR for (int j = 0; j < N; j++) mi[j] = smA.N1[r][j];
+				}
 				eclamp = (int)smA.vec[9][1];
 				general_bie = smA.vec[9][2] != 0.0;
 				beta = smA.vec[9][0];
@@ -1545,7 +1719,28 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 				}
 			}
 		}
-		if (DUO) {
+		if (DUO && CF) {
+			// closed form: B is done at its hand-over unless the blended block ran -- then, and only then, the two meet at a workgroup barrier
+			// (both read the decision from the hand-over word) and A takes what the block decided
+			if (hand == 2) {
+				if (ROLE == 2) {
+					sm.vec[1][r] = tvo;
+					sm.vec[2][r] = (ovr ? 1.0 : 0.0) + (singular ? 2.0 : 0.0) + (truncated ? 4.0 : 0.0) + (blended_i ? 8.0 : 0.0) + (lost ? 16.0 : 0.0);
+				}
+				STAMP(31);
+				__syncthreads();
+				if (ROLE == 1) {
+					tvo = smB.vec[1][r];
+					const int fl = (int)smB.vec[2][r];
+					ovr = (fl & 1) != 0;
+					singular = (fl & 2) != 0;
+					truncated = (fl & 4) != 0;
+					blended_i = (fl & 8) != 0;
+					lost = lost || (fl & 16) != 0;
+				}
+			}
+			if (ROLE == 2) return false;
+		} else if (DUO) {
 			// second workgroup barrier: B hands over the nullspace direction (z', v = M z up to scale, |z'|^2, z'.v) and exits
 			if (ROLE == 2) {
 				sm.vec[7][r] = zr;
@@ -1575,7 +1770,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 				lost = lost || (fl & 16) != 0;
 			}
 		}
-		if (ROLE == 1) {
+		if (ROLE == 1 && !CF) {
 		const double ai = jg_ddq - wr;
 		const double za = octl_sum(zr * ai);
 		const double zf = octl_sum(zr * fi);
@@ -2042,10 +2237,10 @@ __global__ void __launch_bounds__(DUO ? 128 : 64) saip_cycle_oct(const CyclePara
 	__shared__ OctInst smem[DUO ? 16 : 8];
 	static_assert(sizeof(OctInst) >= sizeof(OctDynInst), "the integration step reuses the cycle's LDS blocks");
 	const bool wave_b = DUO && __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 1;
-	__shared__ int wgflags[2];
+	__shared__ int wgflags[3];
 	__shared__ double lawc[FULL ? 96 : 1];  // batch-uniform constants of the partial task's control law (the one wavefront of the workgroup that runs it)
 	if (DUO && !FULL && GJ == 0) {
-		if (threadIdx.x == 0) wgflags[0] = wgflags[1] = 0;
+		if (threadIdx.x == 0) wgflags[0] = wgflags[1] = wgflags[2] = 0;
 		__syncthreads();
 	}
 	bool flagged = false;

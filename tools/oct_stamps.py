@@ -47,5 +47,10 @@ if (sB[:, 29] > 0).all():
           f"  A waits at the barrier (stamp 9 -> 30): median {np.median(s[:, 30] - s[:, 9]):.0f};  B start - A start: median {np.median(sB[:, 0] - s[:, 0]):.0f}")
     if (s[:, 31] > 0).all():
         print(f"  second barrier: A arrives {np.median(s[:, 31] - s[:, 30]):.0f} after the first one, B {np.median(sB[:, 31] - s[:, 30]):.0f};  A: second barrier -> end of the tail {np.median(s[:, 14] - s[:, 31]):.0f}")
+if (s[:, 12] > 0).all() and (s[:, 30] > 0).all():  # lean closed form, two-wavefront form: A's waits for B (stamps 12, 13, 30)
+    med = lambda x: float(np.median(x))
+    print(f"closed form, wavefront A: chol7 done -> B's factor of G taken {med(s[:, 12] - s[:, 4]):.0f} (of which before the poll {med(s[:, 10] - s[:, 4]):.0f});"
+          f"  z + what needs z only {med(s[:, 13] - s[:, 12]):.0f};  wait for B's hand-over {med(s[:, 30] - s[:, 13]):.0f};  hand-over -> end of the tail {med(s[:, 14] - s[:, 30]):.0f}")
+    print(f"closed form, wavefront B: start -> hand-over {med(sB[:, 29] - sB[:, 0]):.0f};  A: start -> hand-over taken {med(s[:, 30] - s[:, 0]):.0f}")
 if (s[:, 11] > 0).all():  # general joint task (GJ != 0): the tail split at stamp 11
     print(f"general joint task: tau + column of N1 (10 -> 11) median {np.median(s[:, 11] - s[:, 10]):.0f}; joint task proper (11 -> 14) median {np.median(s[:, 14] - s[:, 11]):.0f}")
