@@ -17,7 +17,7 @@ struct alignas(256) JointRec {
 };
 static_assert(sizeof(JointRec) == 256, "JointRec must be exactly four cache lines");
 
-// the movable bodies of one robot (fixed links already merged on the host, saip_engine.cpp: saip_model_create_tree)
+// the movable bodies of one robot (fixed links already merged on the host, saip_engine_model.cpp: saip_model_create_tree)
 struct ModelDev {
 	int n;
 	int all_axis_z;              // every joint axis == (0,0,1) (the usual URDF convention): the eight-lane kernels build R0 Rz(q) from two columns
