@@ -550,6 +550,55 @@ double* saip_batch_plant_joints_device(saip_batch*);    /* NULL when detached */
 double* saip_batch_plant_wrenches_device(saip_batch*);  /* NULL when detached or without wrenches */
 double* saip_batch_plant_torques_device(saip_batch*);   /* [dof][ld]; NULL when detached */
 double* saip_batch_plant_summary_device(saip_batch*);   /* [4][ld]; NULL when detached */
+/* ---- plant inertia: the inertial parameters of the SIMULATED robot, per instance.  While attached, the resident integrator (and nothing
+ * else: the cycle kernels, the model queries and everything the controller computes keep the batch-uniform model) reads mass, centre of
+ * mass and inertia of every movable body from a resident table.  One attachment per batch; configuration only, not part of a state
+ * snapshot, so every instance keeps its robot across a restore.
+ *   rows      SAIP_INERTIA_ROW_WORDS doubles per movable body, in the model's body order { m, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Ixz, Iyz }:
+ *             the centre of mass in the body frame, the inertia about it in body axes.  [dof][10] (batch-uniform) or [dof][10][B]
+ *             (per_instance); NULL: the model's own rows.
+ *   parts     _set_parts_host composes the rows on the device from scaled links plus payloads.  A body's part is SAIP_INERTIA_BODY_WORDS
+ *             doubles { s, dx, dy, dz }: m' = s m, I' = s I, c' = c + d (m, c, I the model's); `bodies` is [dof][4] or [dof][4][B]
+ *             (per_instance_bodies), NULL: { 1, 0, 0, 0 }.  A payload is SAIP_INERTIA_PAYLOAD_WORDS doubles { m_p, c_p[3], hx, hy, hz }, a
+ *             uniform box of half-extents h aligned with the frame of its site link and centred at c_p in it, I_p = m_p / 3 diag(hy^2 +
+ *             hz^2, hx^2 + hz^2, hx^2 + hy^2); `payloads` is [P][7] or [P][7][B] (per_instance_payloads), NULL: no mass.  The sites are
+ *             fixed by _attach: payload_links[p] a saip_model_link_index value (batch-uniform); a link welded to a movable body is
+ *             composed with its fixed transform (p_f, R_f) into that body's frame.  With PA(d) = (d.d) 1 - d d^T, over the payloads
+ *             with m_p > 0 on the body in table order:
+ *               m = m' + sum m_p     c = (m' c' + sum m_p (p_f + R_f c_p)) / m
+ *               I = I' + m' PA(c' - c) + sum (R_f I_p R_f^T + m_p PA(p_f + R_f c_p - c))
+ *             A body without such a payload takes m', c', I' as they are.  Every product, sum and quotient is rounded once, in the order
+ *             written (csrc/saip_inertia.h; tests/inertia_ref.py restates it in NumPy bit for bit).
+ *   saip_batch_inertia_randomize draws the parts on the device and composes them: word w (4 j + k of a body, 7 p + e of a payload) of
+ *             instance i is lo[w] + u (hi[w] - lo[w]) clamped to the interval, u = the first uniform of Philox4x32-10 at counter (i, w,
+ *             table, round) (table 2 bodies, 3 payloads) under the key `seed`; lo == hi gives lo exactly.  lo / hi are host tables
+ *             [dof][4] and [P][7]; a NULL pair stands for the neutral words.  Per-instance tables only.
+ *   while attached, saip_batch_integrate and every rollout period pass the table to the integrate launch (on the per-substep sequence
+ *             behind a plant or contact attachment too), and a rollout uses neither fused form.  A payload in the table carries its own
+ *             weight: no plant wrench is needed for it.
+ *   _set_rows_host replaces the table (same shape) and waits; _rows_host reads it back ([dof][10] or [dof][10][B], synchronous);
+ *             _rows_device is the resident table ([dof][10] or [dof][10][ld]; what is written there is not checked).
+ * Without an attachment every entry point enqueues exactly what it did before.  SAIP_ERR_INVALID_ARGUMENT (the message names the entry,
+ * the body or payload, the word and the instance; nothing is written): a value that is not finite; m < 0; an inertia whose smallest
+ * eigenvalue is below -1e-12 max(1, trace) (the triangle inequality is not enforced); s <= 0, m_p < 0 or a half-extent < 0, in a table or
+ * in a bound; a body whose mass can come out as 0 where the model's is positive; more than SAIP_INERTIA_MAX_PAYLOADS payloads, a link index
+ * out of range or a link welded to the fixed base; per-instance parts or a draw onto a batch-uniform table.  SAIP_ERR_ORDER: before
+ * finalize, a model-only batch, a second _attach, any other entry without an attachment.  Argument and order errors are reported before
+ * the device is needed. */
+#define SAIP_INERTIA_ROW_WORDS 10
+#define SAIP_INERTIA_BODY_WORDS 4
+#define SAIP_INERTIA_PAYLOAD_WORDS 7
+#define SAIP_INERTIA_MAX_PAYLOADS 2
+saip_status saip_batch_inertia_attach(saip_batch*, const double* rows /* NULL = the model's */, int per_instance, int n_payloads, const int* payload_links);
+saip_status saip_batch_inertia_detach(saip_batch*);
+saip_status saip_batch_inertia_info(saip_batch*, int* per_instance, int* n_payloads, int* payload_bodies /* [P] movable body of each site */,
+                                    double* payload_frames /* [P][12]: p_f (3), R_f (9, row-major) of each site link in that body */);  /* any NULL */
+saip_status saip_batch_inertia_set_rows_host(saip_batch*, const double* rows);
+saip_status saip_batch_inertia_set_parts_host(saip_batch*, const double* bodies, int per_instance_bodies, const double* payloads, int per_instance_payloads);
+saip_status saip_batch_inertia_randomize(saip_batch*, unsigned long long seed, long long round, const double* body_lo, const double* body_hi,
+                                         const double* payload_lo, const double* payload_hi);
+saip_status saip_batch_inertia_rows_host(saip_batch*, double* out /* [dof][10] or [dof][10][B] */);  /* synchronous */
+double* saip_batch_inertia_rows_device(saip_batch*);     /* NULL when detached */
 /* ---- rollout recorder: a per-period trajectory log and running summaries of saip_batch_rollout_async, kept on the device (the
  * reference's example loops print or log the same quantities every period: state, torques, position / orientation error).  A recorder
  * is attached to a finalized batch and stays attached across rollout calls until detached.  It observes rollout periods only

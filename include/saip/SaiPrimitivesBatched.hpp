@@ -1345,6 +1345,74 @@ public:
 	double* plantTorquesDevice() { return saip_batch_plant_torques_device(_batch); }    // [dof][ld] actuated torques of the last substep
 	double* plantSummaryDevice() { return saip_batch_plant_summary_device(_batch); }    // [4][ld]
 
+	// ---- plant inertia: the masses, centres of mass and inertias the resident integrator reads in place of the model's (saip.h).  While
+	// attached, integrate() and rolloutAsync() integrate with the table; everything the controller computes keeps the model.
+	struct InertiaInfo {
+		int per_instance = 0, n_payloads = 0;
+		std::vector<int> payload_bodies;       // the movable body of every payload site
+		std::vector<double> payload_frames;    // [P][12]: position (3) and rotation (9, row-major) of every site link in that body
+	};
+	// rows: [dof][10] of { m, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Ixz, Iyz }, or [dof][10][B] with per_instance; empty: the model's own rows.
+	// payload_links: up to SAIP_INERTIA_MAX_PAYLOADS sites of the payloads of setInertiaParts() / randomizeInertia()
+	void attachInertia(const std::vector<double>& rows = {}, bool per_instance = false, const std::vector<std::string>& payload_links = {}) {
+		const size_t cols = per_instance ? (size_t)_robot->batchSize() : 1;
+		if (!rows.empty() && rows.size() != (size_t)_robot->dof() * SAIP_INERTIA_ROW_WORDS * cols)
+			throw std::invalid_argument("attachInertia: expected [dof][10] rows, or [dof][10][B] per instance");
+		std::vector<int> links;
+		for (const std::string& l : payload_links) {
+			links.push_back(_robot->linkIndex(l));
+			if (links.back() < 0) throw std::invalid_argument("attachInertia: unknown link [" + l + "]");
+		}
+		check(saip_batch_inertia_attach(_batch, rows.empty() ? nullptr : rows.data(), per_instance ? 1 : 0, (int)links.size(), links.data()));
+	}
+	void detachInertia() { check(saip_batch_inertia_detach(_batch)); }
+	InertiaInfo inertiaInfo() {
+		InertiaInfo i;
+		int bodies[SAIP_INERTIA_MAX_PAYLOADS] = {};
+		double frames[SAIP_INERTIA_MAX_PAYLOADS * 12] = {};
+		check(saip_batch_inertia_info(_batch, &i.per_instance, &i.n_payloads, bodies, frames));
+		i.payload_bodies.assign(bodies, bodies + i.n_payloads);
+		i.payload_frames.assign(frames, frames + 12 * i.n_payloads);
+		return i;
+	}
+	void setInertiaRows(const std::vector<double>& rows) {
+		const InertiaInfo i = inertiaInfo();
+		if (rows.size() != (size_t)_robot->dof() * SAIP_INERTIA_ROW_WORDS * (i.per_instance ? (size_t)_robot->batchSize() : 1))
+			throw std::invalid_argument("setInertiaRows: the shape of the attached table expected");
+		check(saip_batch_inertia_set_rows_host(_batch, rows.data()));
+	}
+	// the table composed on the device from scaled links plus payloads.  bodies: [dof][4] of { s, dx, dy, dz } or [dof][4][B]; empty: { 1, 0, 0, 0 }.
+	// payloads: [P][7] of { m_p, c_p[3], hx, hy, hz } or [P][7][B]; empty: no mass
+	void setInertiaParts(const std::vector<double>& bodies, const std::vector<double>& payloads = {}) {
+		const InertiaInfo i = inertiaInfo();
+		const size_t B = (size_t)_robot->batchSize(), nb = (size_t)_robot->dof() * SAIP_INERTIA_BODY_WORDS, np = (size_t)i.n_payloads * SAIP_INERTIA_PAYLOAD_WORDS;
+		if (!bodies.empty() && bodies.size() != nb && bodies.size() != nb * B) throw std::invalid_argument("setInertiaParts: expected [dof][4] bodies, or [dof][4][B]");
+		if (!payloads.empty() && payloads.size() != np && payloads.size() != np * B) throw std::invalid_argument("setInertiaParts: expected [P][7] payloads, or [P][7][B]");
+		check(saip_batch_inertia_set_parts_host(_batch, bodies.empty() ? nullptr : bodies.data(), B > 1 && bodies.size() == nb * B ? 1 : 0,
+												payloads.empty() ? nullptr : payloads.data(), B > 1 && payloads.size() == np * B ? 1 : 0));
+	}
+	// the parts of every instance drawn on the device, uniform between two batch-uniform tables ([dof][4], [P][7]), and composed; an empty
+	// pair stands for the neutral words
+	void randomizeInertia(unsigned long long seed, long long round, const std::vector<double>& body_lo, const std::vector<double>& body_hi,
+						  const std::vector<double>& payload_lo = {}, const std::vector<double>& payload_hi = {}) {
+		const InertiaInfo i = inertiaInfo();
+		const size_t nb = (size_t)_robot->dof() * SAIP_INERTIA_BODY_WORDS, np = (size_t)i.n_payloads * SAIP_INERTIA_PAYLOAD_WORDS;
+		if ((!body_lo.empty() || !body_hi.empty()) && (body_lo.size() != nb || body_hi.size() != nb))
+			throw std::invalid_argument("randomizeInertia: expected [dof][4] body bounds");
+		if ((!payload_lo.empty() || !payload_hi.empty()) && (payload_lo.size() != np || payload_hi.size() != np))
+			throw std::invalid_argument("randomizeInertia: expected [P][7] payload bounds");
+		check(saip_batch_inertia_randomize(_batch, seed, round, body_lo.empty() ? nullptr : body_lo.data(), body_hi.empty() ? nullptr : body_hi.data(),
+										   payload_lo.empty() ? nullptr : payload_lo.data(), payload_hi.empty() ? nullptr : payload_hi.data()));
+	}
+	// the resident table read back: [dof][10], or [dof][10][B] when attached per instance; waits for the stream
+	std::vector<double> inertiaRows() {
+		const InertiaInfo i = inertiaInfo();
+		std::vector<double> out((size_t)_robot->dof() * SAIP_INERTIA_ROW_WORDS * (i.per_instance ? (size_t)_robot->batchSize() : 1));
+		check(saip_batch_inertia_rows_host(_batch, out.data()));
+		return out;
+	}
+	double* inertiaRowsDevice() { return saip_batch_inertia_rows_device(_batch); }      // [dof][10] or [dof][10][ld]; nullptr when detached
+
 private:
 	void restored(saip_status st) {
 		check(st);

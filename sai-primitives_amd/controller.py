@@ -1857,6 +1857,92 @@ class RobotController:
         """device pointer of the (4, ld) running summaries; None when detached"""
         return capi.lib().saip_batch_plant_summary_device(self._h)
 
+    # -- plant inertia: the masses, centres of mass and inertias the resident integrator reads in place of the model's (saip.h)
+    INERTIA_ROW_WORDS = ("m", "cx", "cy", "cz", "Ixx", "Iyy", "Izz", "Ixy", "Ixz", "Iyz")
+
+    def attachInertia(self, rows=None, per_instance=False, payload_links=()):
+        """give the simulated robot inertial parameters of its own: rows (dof, 10) of { m, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Ixz, Iyz } per
+        movable body (COM in the body frame, inertia about it in body axes), or (dof, B, 10) with per_instance; None: the model's own rows.
+        payload_links: up to 2 link names, the sites of the payloads of setInertiaParts() / randomizeInertia().  While attached,
+        integrate() and rolloutAsync() integrate with the table; the controller keeps computing with the model."""
+        who = "attachInertia"
+        rt = None if rows is None else self._plant_table(rows, per_instance, self.batch_size, self._robot.dof(), capi.SAIP_INERTIA_ROW_WORDS, who, "rows")
+        names = list(payload_links)
+        links = np.zeros(max(len(names), 1), np.int32)
+        for p, name in enumerate(names):
+            links[p] = self._robot.linkIndex(name)
+            if links[p] < 0:
+                raise ValueError(f"{who}: payload {p}: unknown link [{name}]")
+        self._call("saip_batch_inertia_attach", None if rt is None else _dptr(rt), int(bool(per_instance)), len(names), links.ctypes.data_as(C.POINTER(C.c_int)))
+
+    def inertiaInfo(self):
+        """dict per_instance, n_payloads, payload_bodies (the movable body of every payload site), payload_positions (P, 3) and
+        payload_rotations (P, 3, 3): the site links' frames in those bodies"""
+        v = [C.c_int(0), C.c_int(0)]
+        bodies = (C.c_int * capi.SAIP_INERTIA_MAX_PAYLOADS)()
+        frames = np.zeros((capi.SAIP_INERTIA_MAX_PAYLOADS, 12))
+        self._call("saip_batch_inertia_info", C.byref(v[0]), C.byref(v[1]), bodies, _dptr(frames))
+        P = v[1].value
+        return dict(per_instance=bool(v[0].value), n_payloads=P, payload_bodies=[bodies[p] for p in range(P)],
+                    payload_positions=frames[:P, :3].copy(), payload_rotations=frames[:P, 3:].reshape(P, 3, 3).copy())
+
+    def detachInertia(self):
+        self._call("saip_batch_inertia_detach")
+
+    def setInertiaRows(self, rows):
+        """replace the table (same shape as attached); takes effect with the next integration"""
+        info = self.inertiaInfo()
+        a = self._plant_table(rows, info["per_instance"], self.batch_size, self._robot.dof(), capi.SAIP_INERTIA_ROW_WORDS, "setInertiaRows", "rows")
+        self._call("saip_batch_inertia_set_rows_host", _dptr(a))
+
+    def _inertia_parts(self, x, rows, words, who, what):
+        """(array in the C-ABI layout or None, per-instance flag) of a part table (rows, words) or (rows, B, words)"""
+        if x is None:
+            return None, 0
+        a = np.asarray(x, float)
+        per = a.ndim == 3
+        return self._plant_table(a, per, self.batch_size, rows, words, who, what), int(per)
+
+    def setInertiaParts(self, bodies=None, payloads=None):
+        """compose the table on the device from scaled links plus payloads.  bodies: (dof, 4) of { s, dx, dy, dz } -- m' = s m, I' = s I,
+        c' = c + d of the model's values -- or (dof, B, 4); None: { 1, 0, 0, 0 }.  payloads: (P, 7) of { m_p, c_p (3), hx, hy, hz }, a
+        uniform box of half-extents h in the frame of its site link (attachInertia(payload_links=...)), or (P, B, 7); None: no mass."""
+        info = self.inertiaInfo()
+        bt, perb = self._inertia_parts(bodies, self._robot.dof(), capi.SAIP_INERTIA_BODY_WORDS, "setInertiaParts", "bodies")
+        pt, perp = self._inertia_parts(payloads, info["n_payloads"], capi.SAIP_INERTIA_PAYLOAD_WORDS, "setInertiaParts", "payloads")
+        self._call("saip_batch_inertia_set_parts_host", None if bt is None else _dptr(bt), perb, None if pt is None else _dptr(pt), perp)
+
+    def randomizeInertia(self, seed, round=0, bodies=None, payloads=None):
+        """draw the parts of every instance on the device and compose them: bodies = (lo, hi), two (dof, 4) tables, payloads = (lo, hi),
+        two (P, 7) tables; every word is uniform between its bounds (lo == hi: exactly lo), reproducibly for (seed, round); None stands
+        for the neutral words.  A table attached without per_instance is refused."""
+        info = self.inertiaInfo()
+
+        def pair(b, rows, words, what):
+            if b is None:
+                return None, None
+            lo, hi = (self._plant_table(x, False, 0, rows, words, "randomizeInertia", what) for x in b)
+            return lo, hi
+        bl, bh = pair(bodies, self._robot.dof(), capi.SAIP_INERTIA_BODY_WORDS, "body bounds")
+        pl, ph = pair(payloads, info["n_payloads"], capi.SAIP_INERTIA_PAYLOAD_WORDS, "payload bounds")
+        self._call("saip_batch_inertia_randomize", int(seed) & (2**64 - 1), int(round), *(None if x is None else _dptr(x) for x in (bl, bh, pl, ph)))
+
+    def inertiaRows(self):
+        """the resident table read back: (dof, 10), or (dof, B, 10) when attached per instance (waits for the engine stream)"""
+        info = self.inertiaInfo()
+        n, W = self._robot.dof(), capi.SAIP_INERTIA_ROW_WORDS
+        if not info["per_instance"]:
+            out = np.empty((n, W))
+            self._call("saip_batch_inertia_rows_host", _dptr(out))
+            return out
+        out = np.empty((n, W, self.batch_size))
+        self._call("saip_batch_inertia_rows_host", _dptr(out))
+        return np.ascontiguousarray(out.transpose(0, 2, 1))
+
+    def inertiaRowsDevice(self):
+        """device pointer of the resident table, (dof, 10) or (dof, 10, ld); None when detached"""
+        return capi.lib().saip_batch_inertia_rows_device(self._h)
+
     def rewindGoalSchedules(self):
         """the period counter of the tasks' goal schedules (task.setGoalSchedule) back to 0: the next rollout starts at the first keyframe"""
         self._call("saip_batch_goal_schedule_rewind")

@@ -174,6 +174,11 @@ struct SimParams {
 	double* dq;            // [n][ld] in/out
 	const double* tau;     // [n][ld] joint torques held over the call (NaN = coast)
 	double* ddq;           // optional [n][ld] joint accelerations of the last substep
+	// the resident inertia table (saip_inertia.h), read by the INERTIA instantiations of the integrators only: ten words { m, c (3), I (6) }
+	// per movable body in place of the model's; word k of body j is inertia[(10 j + k) inertia_stride + column], a batch-uniform table
+	// [n][10] has stride 1 and column 0, a per-instance table [n][10][ld] stride ld and the instance as its column.  nullptr: none.
+	const double* inertia = nullptr;
+	long long inertia_stride = 0;
 };
 
 // one observed rollout period (saip_rollout_record.hip).  Passed to the kernel by value.

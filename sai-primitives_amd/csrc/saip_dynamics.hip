@@ -21,11 +21,18 @@ namespace saip {
 
 // TREE: kinematic trees (ModelDev::is_tree) -- the same step with the tree traversals of saip_rbd.h; every integrate path of the engine lands
 // here for them, whatever the dof
-template <int NMAX, bool TREE>
+// INERTIA: mass, centre of mass and inertia of every body from the lane's column of the resident table SimParams::inertia instead of the model
+template <int NMAX, bool TREE, bool INERTIA>
 __global__ void __launch_bounds__(64) saip_integrate_kernel(const SimParams S) {
 	const int b = blockIdx.x * blockDim.x + threadIdx.x;
 	if (b >= S.B) return;
 	const ModelDev& md = *S.model;
+	using IN = typename InertialSource<INERTIA>::type;
+	IN in;
+	if constexpr (INERTIA) {
+		in.w = S.inertia + (S.inertia_stride == 1 ? 0 : (long long)b);
+		in.stride = S.inertia_stride;
+	}
 	const int n = S.n;
 	double q[NMAX], dq[NMAX], tau[NMAX], h[NMAX], ddq[NMAX], e[NMAX];
 	double M[NMAX][NMAX];
@@ -41,12 +48,12 @@ __global__ void __launch_bounds__(64) saip_integrate_kernel(const SimParams S) {
 	const V3 a0 = v3(-S.gravity[0], -S.gravity[1], -S.gravity[2]);
 	Chain<NMAX> K;
 	for (int step = 0; step < S.substeps; step++) {
-		if constexpr (TREE) chain_fk_tree<NMAX>(md, n, q, K);
-		else chain_fk<NMAX>(md, n, q, K);
-		if constexpr (TREE) rnea_tree<NMAX>(md, n, K, dq, e, a0, true, h);  // b(q, dq) + g(q)
-		else rnea<NMAX>(md, n, K, dq, e, a0, true, h);
-		if constexpr (TREE) mass_matrix_crb_tree<NMAX>(md, n, K, M);
-		else mass_matrix_crb<NMAX>(md, n, K, M);
+		if constexpr (TREE) chain_fk_tree<NMAX>(md, n, q, K, in);
+		else chain_fk<NMAX>(md, n, q, K, in);
+		if constexpr (TREE) rnea_tree<NMAX>(md, n, K, dq, e, a0, true, h, in);  // b(q, dq) + g(q)
+		else rnea<NMAX>(md, n, K, dq, e, a0, true, h, in);
+		if constexpr (TREE) mass_matrix_crb_tree<NMAX>(md, n, K, M, in);
+		else mass_matrix_crb<NMAX>(md, n, K, M, in);
 		// Cholesky M = L L^T (lower, in place), then two triangular solves
 #pragma unroll
 		for (int k = 0; k < n; k++) {
@@ -100,20 +107,25 @@ __global__ void __launch_bounds__(64) saip_integrate_kernel(const SimParams S) {
 
 hipError_t launch_integrate_oct(const SimParams& S, hipStream_t stream);  // saip_dynamics_oct.hip: eight lanes per instance, 7-dof chains
 
-hipError_t launch_integrate(const SimParams& S, bool tree, hipStream_t stream) {
+template <bool INERTIA>
+static hipError_t launch_integrate_lanes(const SimParams& S, bool tree, hipStream_t stream) {
+	const int grid = (S.B + 63) / 64;
 	if (tree) {
-		const int grid = (S.B + 63) / 64;
-		if (S.n <= 8) hipLaunchKernelGGL((saip_integrate_kernel<8, true>), dim3(grid), dim3(64), 0, stream, S);
-		else hipLaunchKernelGGL((saip_integrate_kernel<32, true>), dim3(grid), dim3(64), 0, stream, S);
-		return hipGetLastError();
+		if (S.n <= 8) hipLaunchKernelGGL((saip_integrate_kernel<8, true, INERTIA>), dim3(grid), dim3(64), 0, stream, S);
+		else hipLaunchKernelGGL((saip_integrate_kernel<32, true, INERTIA>), dim3(grid), dim3(64), 0, stream, S);
+	} else {
+		if (S.n <= 8) hipLaunchKernelGGL((saip_integrate_kernel<8, false, INERTIA>), dim3(grid), dim3(64), 0, stream, S);
+		else hipLaunchKernelGGL((saip_integrate_kernel<32, false, INERTIA>), dim3(grid), dim3(64), 0, stream, S);
 	}
+	return hipGetLastError();
+}
+
+// S.inertia (the resident inertia table) selects the INERTIA instantiation of whichever kernel the model takes
+hipError_t launch_integrate(const SimParams& S, bool tree, hipStream_t stream) {
 	// 7-dof chains: the eight-lanes-per-instance kernel is faster at every batch size measured (8.7 vs 33.4 us at 4096, 46.8 vs 81.1 us at
 	// 65 536, 166 vs 218 us at 262 144 per two substeps)
-	if (S.n == 7) return launch_integrate_oct(S, stream);
-	const int grid = (S.B + 63) / 64;
-	if (S.n <= 8) hipLaunchKernelGGL((saip_integrate_kernel<8, false>), dim3(grid), dim3(64), 0, stream, S);
-	else hipLaunchKernelGGL((saip_integrate_kernel<32, false>), dim3(grid), dim3(64), 0, stream, S);
-	return hipGetLastError();
+	if (!tree && S.n == 7) return launch_integrate_oct(S, stream);
+	return S.inertia ? launch_integrate_lanes<true>(S, tree, stream) : launch_integrate_lanes<false>(S, tree, stream);
 }
 
 }  // namespace saip

@@ -13,14 +13,17 @@
 
 namespace saip {
 
+// INERTIA: the resident inertia table in place of the model's inertial parameters (SimParams::inertia)
+template <bool INERTIA>
 __global__ void __launch_bounds__(64) saip_integrate_oct(const SimParams S) {
 	__shared__ OctDynInst smem[8];
-	integrate_oct_body(S, smem, blockIdx.x, threadIdx.x);
+	integrate_oct_body<INERTIA>(S, smem, blockIdx.x, threadIdx.x);
 }
 
 hipError_t launch_integrate_oct(const SimParams& S, hipStream_t stream) {
 	const dim3 grid((S.B + 7) / 8), block(64);
-	hipLaunchKernelGGL(saip_integrate_oct, grid, block, 0, stream, S);
+	if (S.inertia) hipLaunchKernelGGL(saip_integrate_oct<true>, grid, block, 0, stream, S);
+	else hipLaunchKernelGGL(saip_integrate_oct<false>, grid, block, 0, stream, S);
 	return hipGetLastError();
 }
 

@@ -48,6 +48,9 @@ __device__ __forceinline__ void oct_suffix_sum(double (&x)[K]) {
 // one group of eight instances (block8 = its index) by the calling wavefront; smem = that wavefront's eight LDS blocks.  All
 // synchronisation is wavefront-local (LDS operations of one wavefront execute in order), so the body can sit in workgroups of any
 // number of wavefronts -- saip_integrate_oct (one) and the fused integrate + next-period OTG launch of saip_otg.hip (four).
+// INERTIA: the body's mass, centre of mass and inertia come from the resident table SimParams::inertia (the lane's ten words, loaded once
+// in front of the substep loop) instead of the model; everything else, the kinematics included, stays the model's.
+template <bool INERTIA = false>
 __device__ __forceinline__ void integrate_oct_body(const SimParams& S, OctDynInst* smem, const int block8, const int lane) {
 	constexpr int N = 7;
 	const int r = octl_r(lane), grp = octl_grp(lane);
@@ -69,9 +72,19 @@ __device__ __forceinline__ void integrate_oct_body(const SimParams& S, OctDynIns
 	const double R0[9] = {md.R0[rr][0], md.R0[rr][1], md.R0[rr][2], md.R0[rr][3], md.R0[rr][4], md.R0[rr][5], md.R0[rr][6], md.R0[rr][7], md.R0[rr][8]};
 	const double p0[3] = {md.p0[rr][0], md.p0[rr][1], md.p0[rr][2]};
 	const double ax[3] = {md.axis[rr][0], md.axis[rr][1], md.axis[rr][2]};
-	const double cl[3] = {md.com[rr][0], md.com[rr][1], md.com[rr][2]};
-	const double I6[6] = {md.inertia[rr][0], md.inertia[rr][1], md.inertia[rr][2], md.inertia[rr][3], md.inertia[rr][4], md.inertia[rr][5]};
-	const double mass = act ? md.mass[rr] : 0.0;
+	double cl[3], I6[6], mass;
+	if constexpr (INERTIA) {
+		// (a lane beyond B reads the last instance's column, like its state: in bounds, never stored)
+		const long long st = S.inertia_stride;
+		const double* w = S.inertia + (long long)rr * 10 * st + (st == 1 ? 0 : (long long)b);
+		mass = act ? w[0] : 0.0;
+		UNR for (int e = 0; e < 3; e++) cl[e] = w[(1 + e) * st];
+		UNR for (int e = 0; e < 6; e++) I6[e] = w[(4 + e) * st];
+	} else {
+		UNR for (int e = 0; e < 3; e++) cl[e] = md.com[rr][e];
+		UNR for (int e = 0; e < 6; e++) I6[e] = md.inertia[rr][e];
+		mass = act ? md.mass[rr] : 0.0;
+	}
 
 	for (int step = 0; step < S.substeps; step++) {
 		// ---- kinematics: local transform, prefix product over the chain (DPP)

@@ -134,6 +134,7 @@ extern "C" void saip_batch_destroy(saip_batch* b) {
 		while (b->n_patch > 0) patch_free(b, b->n_patch - 1);
 		clearance_free(b);
 		plant_free(b);
+		inertia_free(b);
 		if (b->stream) (void)hipStreamDestroy(b->stream);
 	}
 	delete b;

@@ -22,6 +22,7 @@
 #include "saip_contact_patch.h"
 #include "saip_clearance.h"
 #include "saip_plant.h"
+#include "saip_inertia.h"
 
 namespace saip {
 hipError_t launch_cycle_wg(const CycleParams& P, bool tree, hipStream_t stream);
@@ -55,6 +56,7 @@ hipError_t launch_clearance_add_cost(int B, int ld, const double* summary, doubl
 hipError_t launch_clearance_summary_reset(int B, int ld, double* summary, hipStream_t stream);
 hipError_t launch_plant_apply(const PlantParams& P, bool tree, hipStream_t stream);
 hipError_t launch_plant_randomize(const PlantRandomParams& P, hipStream_t stream);
+hipError_t launch_inertia_compose(const InertiaComposeParams& P, hipStream_t stream);
 }  // namespace saip
 
 using saip::CycleParams;
@@ -227,6 +229,17 @@ struct saip_batch {
 		double* summary = nullptr;           // [4][ld]
 		double* bounds = nullptr;            // joint lo [n][10], joint hi, wrench lo [W][8], wrench hi of saip_batch_plant_randomize (per-instance tables only)
 	} plant;
+	// saip_batch_inertia_attach: the inertial parameters of the simulated robot (saip_inertia.hip), at most one per batch: the table the
+	// resident integrator reads in place of the model's masses, centres of mass and inertias.  Configuration only: its arrays are its own
+	// (freed by _detach), not part of `allocs` or of a snapshot.
+	struct Inertia {
+		bool attached = false;
+		int per_instance = 0, n_payloads = 0;
+		saip::InertiaSite site[saip::INERTIA_MAX_PAYLOADS] = {};
+		double* rows = nullptr;              // [n][10] (batch-uniform) or [n][10][ld]
+		double* parts = nullptr;             // staging of _set_parts_host: bodies [n][4] or [n][4][ld], then payloads [P][7] or [P][7][ld]
+		double* bounds = nullptr;            // body lo [n][4], body hi, payload lo [P][7], payload hi of _randomize (per-instance tables only)
+	} inertia;
 };
 
 namespace saip {
@@ -280,6 +293,8 @@ saip_status clearance_launch(saip_batch* b, int mode, double dt);
 // ---- saip_engine_plant.cpp
 void plant_free(saip_batch* b);
 saip_status plant_launch(saip_batch* b, double dt);
+// ---- saip_engine_inertia.cpp
+void inertia_free(saip_batch* b);
 // ---- saip_engine_rollout.cpp
 void record_free(saip_batch* b);
 void schedule_release(saip_batch* b, int task);

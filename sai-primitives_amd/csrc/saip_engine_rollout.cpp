@@ -15,6 +15,9 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 	S.dq = b->dq;
 	S.tau = commanded_tau(b);
 	S.ddq = nullptr;
+	// the inertia table of the simulated robot, on every path below but the fused one (which is not taken while it is attached)
+	S.inertia = b->inertia.attached ? b->inertia.rows : nullptr;
+	S.inertia_stride = b->inertia.attached && b->inertia.per_instance ? b->ld : 1;
 	hipError_t e;
 	const bool tree = b->model->dev.is_tree != 0;  // trees: the lane-per-instance tree kernel, whatever the dof (the eight-lane step is chain-only)
 	if (b->contact.attached || b->n_patch > 0 || b->plant.attached) {
@@ -39,7 +42,7 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 		b->state_epoch++;
 		return SAIP_OK;
 	}
-	if (with_next_otg && S.n == 7 && !tree && otg_pair_ready(b)) {
+	if (with_next_otg && S.n == 7 && !tree && !b->inertia.attached && otg_pair_ready(b)) {
 		// rollouts: this integration and the NEXT period's trajectory generation in one launch (they are independent)
 		e = saip::launch_integrate_otg_pair(S, b->tasks[0].otg, b->tasks[1].otg, b->B, b->ld, b->stream);
 		b->otg_prelaunched = true;
@@ -384,7 +387,8 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 	// with contact planes attached neither fused form is used: the contact force sits between the cycle and every integration substep
 	// (contact patches: the same, with their kernel)
 	// a plant model does the same: it sits between the cycle and every integration substep
-	const bool contact = b->contact.attached || b->n_patch > 0 || b->plant.attached;
+	// an inertia table rules out both fused forms as well: they integrate with the model's inertial parameters
+	const bool contact = b->contact.attached || b->n_patch > 0 || b->plant.attached || b->inertia.attached;
 	const bool patch_sensor = patch_any_sensor(b);
 	auto period = [&](const bool more = false) -> saip_status {  // more: another period follows inside this call
 		if (scheduled && (st = apply_schedules(b))) return st;

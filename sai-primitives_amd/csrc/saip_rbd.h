@@ -27,6 +27,33 @@ __device__ __forceinline__ V3 mulRt(const double* R, V3 v) {
 	return V3{R[0] * v.x + R[3] * v.y + R[6] * v.z, R[1] * v.x + R[4] * v.y + R[7] * v.z, R[2] * v.x + R[5] * v.y + R[8] * v.z};
 }
 
+// Where a body's inertial parameters come from.  ModelInertials: the batch-uniform model (what every kernel reads but the INERTIA
+// instantiations of the integrator).  TableInertials: the lane's column of the resident inertia table (saip_inertia.h) -- word k of body j is
+// w[(10 j + k) stride].  `in` is a name in the scope of every traversal below, beside md.
+struct ModelInertials {
+	__device__ __forceinline__ double mass(const ModelDev& md, int j) const { return md.mass[j]; }
+	__device__ __forceinline__ double com(const ModelDev& md, int j, int e) const { return md.com[j][e]; }
+	__device__ __forceinline__ const double* inertia(const ModelDev& md, int j, double*) const { return md.inertia[j]; }
+};
+struct TableInertials {
+	const double* w;
+	long long stride;
+	__device__ __forceinline__ double mass(const ModelDev&, int j) const { return w[(long long)j * 10 * stride]; }
+	__device__ __forceinline__ double com(const ModelDev&, int j, int e) const { return w[((long long)j * 10 + 1 + e) * stride]; }
+	__device__ __forceinline__ const double* inertia(const ModelDev&, int j, double* I6) const {
+		for (int e = 0; e < 6; e++) I6[e] = w[((long long)j * 10 + 4 + e) * stride];
+		return I6;
+	}
+};
+template <bool TABLE>
+struct InertialSource {
+	using type = ModelInertials;
+};
+template <>
+struct InertialSource<true> {
+	using type = TableInertials;
+};
+
 template <int NMAX>
 struct Chain {  // world-frame kinematics of the movable bodies of one instance
 	double R[NMAX][9];
@@ -34,7 +61,7 @@ struct Chain {  // world-frame kinematics of the movable bodies of one instance
 };
 
 // One joint j of the forward kinematics, expanded in place in both traversals: R, o come in as the rotation and joint origin of the parent body
-// (the base: identity, zero) and leave as those of body j, which are stored in K with the world axis and the centre of mass.  md, q, j and K
+// (the base: identity, zero) and leave as those of body j, which are stored in K with the world axis and the centre of mass.  md, in, q, j and K
 // are names in the caller's scope.  A macro rather than a function for the reason given at SAIP_FK_JOINT_STEP (saip_fk.h): as a function,
 // force-inlined or not, it changes the schedule of the chain kernels.
 #define RBD_FK_JOINT_STEP \
@@ -59,10 +86,10 @@ struct Chain {  // world-frame kinematics of the movable bodies of one instance
 	for (int e = 0; e < 9; e++) K.R[j][e] = R[e]; \
 	K.o[j] = o; \
 	K.z[j] = mulR(R, v3(ax, ay, az)); \
-	K.c[j] = o + mulR(R, v3(md.com[j][0], md.com[j][1], md.com[j][2]));
+	K.c[j] = o + mulR(R, v3(in.com(md, j, 0), in.com(md, j, 1), in.com(md, j, 2)));
 
-template <int NMAX>
-__device__ void chain_fk(const ModelDev& md, int n, const double* q, Chain<NMAX>& K) {
+template <int NMAX, class IN = ModelInertials>
+__device__ void chain_fk(const ModelDev& md, int n, const double* q, Chain<NMAX>& K, const IN in = IN()) {
 	double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 	V3 o = v3(0, 0, 0);
 #pragma unroll
@@ -99,14 +126,16 @@ __device__ __forceinline__ V3 inertia_mul(const double* R, const double* I6, V3 
 	const V3 rc = K.c[j] - K.o[j]; \
 	V3 ac = a + cross(al, rc); \
 	if (with_velocity) ac = ac + cross(w, cross(w, rc)); \
-	f_ = md.mass[j] * ac; \
-	nn_ = inertia_mul(K.R[j], md.inertia[j], al); \
-	if (with_velocity) nn_ = nn_ + cross(w, inertia_mul(K.R[j], md.inertia[j], w));
+	f_ = in.mass(md, j) * ac; \
+	double I6s_[6]; \
+	const double* const I6_ = in.inertia(md, j, I6s_); \
+	nn_ = inertia_mul(K.R[j], I6_, al); \
+	if (with_velocity) nn_ = nn_ + cross(w, inertia_mul(K.R[j], I6_, w));
 
 // Recursive Newton-Euler in world coordinates: joint torques for (dq, ddq) with base acceleration a0 (= -gravity).
 // with_velocity = false drops every velocity-product term (used for the columns of M).
-template <int NMAX>
-__device__ void rnea(const ModelDev& md, int n, const Chain<NMAX>& K, const double* dq, const double* ddq, V3 a0, bool with_velocity, double* tau) {
+template <int NMAX, class IN = ModelInertials>
+__device__ void rnea(const ModelDev& md, int n, const Chain<NMAX>& K, const double* dq, const double* ddq, V3 a0, bool with_velocity, double* tau, const IN in = IN()) {
 	V3 f[NMAX], nn[NMAX];  // net force on body j, net moment about its centre of mass
 	V3 w = v3(0, 0, 0), al = v3(0, 0, 0), a = a0, op = v3(0, 0, 0);
 #pragma unroll
@@ -127,8 +156,8 @@ __device__ void rnea(const ModelDev& md, int n, const Chain<NMAX>& K, const doub
 }
 
 // kinematic tree: body j starts from its parent's frame (ModelDev::parent, the base when -1)
-template <int NMAX>
-__device__ void chain_fk_tree(const ModelDev& md, int n, const double* q, Chain<NMAX>& K) {
+template <int NMAX, class IN = ModelInertials>
+__device__ void chain_fk_tree(const ModelDev& md, int n, const double* q, Chain<NMAX>& K, const IN in = IN()) {
 	for (int j = 0; j < n; j++) {
 		const int pa = md.parent[j];
 		double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
@@ -143,8 +172,8 @@ __device__ void chain_fk_tree(const ModelDev& md, int n, const double* q, Chain<
 
 // Recursive Newton-Euler on a kinematic tree: the forward pass keeps w, alpha, a (at the joint origin) per body and starts each body from its
 // parent's; the backward pass adds each body's transmitted wrench, shifted from o_j to o_parent, into its parent.
-template <int NMAX>
-__device__ void rnea_tree(const ModelDev& md, int n, const Chain<NMAX>& K, const double* dq, const double* ddq, V3 a0, bool with_velocity, double* tau) {
+template <int NMAX, class IN = ModelInertials>
+__device__ void rnea_tree(const ModelDev& md, int n, const Chain<NMAX>& K, const double* dq, const double* ddq, V3 a0, bool with_velocity, double* tau, const IN in = IN()) {
 	V3 W[NMAX], AL[NMAX], A[NMAX];  // per body: angular velocity, angular acceleration, linear acceleration of the joint origin
 	V3 F[NMAX], N[NMAX];            // force / moment (about o_j) transmitted through joint j
 	for (int j = 0; j < n; j++) {
@@ -182,8 +211,8 @@ __device__ void rnea_tree(const ModelDev& md, int n, const Chain<NMAX>& K, const
 // Spatial inertia about the world origin O: mass m, first moment hm = m c, rotational inertia Io = R I R^T + m (c.c 1 - c c^T).
 // Column j: momentum of the composite body j.. under the unit motion of joint j, (p, L_O) = Ic_j s_j with s_j = (z_j, o_j x z_j) for a
 // revolute and (0, z_j) for a prismatic joint; M_ij = s_i . (L_O, p) for i <= j.
-template <int NMAX>
-__device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, const int n, const Chain<NMAX>& K, double (&M)[NMAX][NMAX]) {
+template <int NMAX, class IN = ModelInertials>
+__device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, const int n, const Chain<NMAX>& K, double (&M)[NMAX][NMAX], const IN in = IN()) {
 	double cm = 0.0;
 	V3 ch = v3(0, 0, 0);
 	double cI[6] = {0, 0, 0, 0, 0, 0};  // xx yy zz xy xz yz
@@ -191,10 +220,11 @@ __device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, const int n,
 	for (int jj = 0; jj < n; jj++) {
 		const int j = n - 1 - jj;
 		// add body j to the composite
-		const double m = md.mass[j];
+		const double m = in.mass(md, j);
 		const V3 c = K.c[j];
 		const double* R = K.R[j];
-		const double* I6 = md.inertia[j];
+		double I6s[6];
+		const double* I6 = in.inertia(md, j, I6s);
 		// R I R^T
 		double RI[9];
 #pragma unroll
@@ -234,15 +264,16 @@ __device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, const int n,
 
 // mass_matrix_crb of a kinematic tree: the composite of body j sums its subtree (ModelDev::desc) and M_ij, i < j, is nonzero only for i an
 // ancestor of j (ModelDev::anc)
-template <int NMAX>
-__device__ void mass_matrix_crb_tree(const ModelDev& md, const int n, const Chain<NMAX>& K, double (&M)[NMAX][NMAX]) {
+template <int NMAX, class IN = ModelInertials>
+__device__ void mass_matrix_crb_tree(const ModelDev& md, const int n, const Chain<NMAX>& K, double (&M)[NMAX][NMAX], const IN in = IN()) {
 	double bm[NMAX], bI[NMAX][6];
 	V3 bh[NMAX];
 	for (int j = 0; j < n; j++) {  // spatial inertia of body j about the world origin
-		const double m = md.mass[j];
+		const double m = in.mass(md, j);
 		const V3 c = K.c[j];
 		const double* R = K.R[j];
-		const double* I6 = md.inertia[j];
+		double I6s[6];
+		const double* I6 = in.inertia(md, j, I6s);
 		double RI[9];
 		for (int r = 0; r < 3; r++) {
 			RI[3 * r + 0] = R[3 * r] * I6[0] + R[3 * r + 1] * I6[3] + R[3 * r + 2] * I6[4];

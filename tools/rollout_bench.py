@@ -26,7 +26,10 @@
    pairs, and prints the event-timed mean of 200 back-to-back evaluations alone.
    --plant [--plant-wrenches W] [--substeps S] times, interleaved in the same run, the closed-loop period without and with a per-instance
    plant model (tight actuators, friction, stops at the model's limits and W payload-like wrenches, 0..4) and the event-timed mean of 200
-   one-substep integrate calls both ways: the difference is the plant launch alone."""
+   one-substep integrate calls both ways: the difference is the plant launch alone.
+   --inertia [--inertia-payloads P] [--substeps S] times, interleaved in the same run, the closed-loop period without and with a per-instance
+   inertia table (link masses within 20 %, centres of mass within 2 cm, P box payloads of up to 3 kg, 0..2, drawn on the device), the
+   event-timed mean of 200 integrate calls both ways and of 50 draws of the whole table."""
 import argparse
 import os
 import sys
@@ -87,6 +90,8 @@ ap.add_argument("--clearance-obstacles", type=int, default=4)
 ap.add_argument("--clearance-pairs", type=int, default=0)
 ap.add_argument("--plant", action="store_true")
 ap.add_argument("--plant-wrenches", type=int, choices=range(5), default=1)
+ap.add_argument("--inertia", action="store_true")
+ap.add_argument("--inertia-payloads", type=int, choices=range(3), default=1)
 args = ap.parse_args()
 record = args.record_stride is not None or args.record_channels is not None or args.record_summaries
 
@@ -326,6 +331,39 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
                   f"closed-loop period {plain:.1f} us; with a per-instance plant model and {Wn} wrench(es) {with_p:.1f} us; without it again {again:.1f} us; "
                   f"one substep on the stream {plain_s:.2f} us plain, {with_s:.2f} us with the plant: launch alone {with_s - plain_s:.2f} us "
                   f"({clipped} of {B} instances clipped a torque)")
+        continue
+    if args.inertia:
+        Pn = args.inertia_payloads
+        lo, hi = np.tile([0.8, -0.02, -0.02, -0.02], (7, 1)), np.tile([1.2, 0.02, 0.02, 0.02], (7, 1))
+        plo, phi = np.zeros((Pn, 7)), np.tile([3.0, 0.05, 0.05, 0.05, 0.08, 0.08, 0.08], (Pn, 1))
+        timed_us, _ = stream_timer(ctrl)
+
+        def period_us():
+            t0 = time.perf_counter()
+            ctrl.rolloutAsync(K, 5e-4, args.substeps, gravity=(0, 0, 0))
+            ctrl.synchronize()
+            return (time.perf_counter() - t0) / K * 1e6
+
+        def integrate_us():
+            return timed_us(lambda: ctrl.integrate(5e-4, args.substeps, gravity=(0, 0, 0)), 200)
+
+        def draw(rnd=0):
+            ctrl.randomizeInertia(1, rnd, bodies=(lo, hi), payloads=(plo, phi) if Pn else None)
+
+        for _ in range(args.repeats):
+            plain, plain_i = period_us(), integrate_us()
+            ctrl.attachInertia(per_instance=True, payload_links=["end-effector", "link4"][:Pn])
+            draw()
+            period_us()
+            with_t, with_i = period_us(), integrate_us()
+            draw_us = timed_us(draw, 50)
+            heaviest = float(ctrl.inertiaRows()[6, :, 0].max())
+            ctrl.detachInertia()
+            again = period_us()
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {args.substeps}: "
+                  f"closed-loop period {plain:.1f} us; with a per-instance inertia table and {Pn} payload(s) {with_t:.1f} us; without it again {again:.1f} us; "
+                  f"integrate on the stream {plain_i:.2f} us plain, {with_i:.2f} us with the table; one draw of the table {draw_us:.2f} us, uploads "
+                  f"of the bounds included (the heaviest last body has {heaviest:.2f} kg)")
         continue
     if args.goal_schedule:
         def timed(calls, steps):
