@@ -261,6 +261,9 @@ saip_status dev_alloc(saip_batch* b, Tp** p, size_t count) {
 	void* v = nullptr;
 	HIP_TRY(hipMalloc(&v, count * sizeof(Tp)));
 	HIP_TRY(hipMemset(v, 0, count * sizeof(Tp)));
+	// the fill runs on the null stream and need not be done when the call returns; the batch's stream is non-blocking and does not wait for
+	// it: without this a kernel launched on it right away (the first model query into a grown scratch) had its results zeroed now and then
+	HIP_TRY(hipStreamSynchronize(nullptr));
 	b->allocs.push_back(v);
 	*p = (Tp*)v;
 	return SAIP_OK;

@@ -127,6 +127,7 @@ extern "C" saip_status saip_batch_rollout_recorder_attach(saip_batch* b, int cap
 	auto alloc_zero = [&](void** p, size_t bytes) -> saip_status {
 		HIP_TRY(hipMalloc(p, bytes));
 		HIP_TRY(hipMemset(*p, 0, bytes));
+		HIP_TRY(hipStreamSynchronize(nullptr));  // (the null-stream fill is done before the rollout writes on the batch's non-blocking stream: see dev_alloc)
 		return SAIP_OK;
 	};
 	if (channels) {

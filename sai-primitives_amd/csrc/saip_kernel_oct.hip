@@ -30,15 +30,8 @@
 #include "saip_fk.h"
 #include "saip_law.h"
 #include "saip_oct_common.h"
-// the general kernel's body as this kernel's slow tail: one wavefront plays the 64-thread workgroup, so its synchronisation points are
-// wavefront-local (the other wavefront of a two-wavefront workgroup has left by then)
-#define SAIP_WG_SYNC()                                          \
-	do {                                                        \
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  \
-		__builtin_amdgcn_wave_barrier();                        \
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  \
-	} while (0)
-#include "saip_wg_cycle.h"
+#include "saip_oct_joint_tails.h"
+#include "saip_oct_slow_tail.h"  // the general kernel's body as this kernel's slow tail, shared with saip_kernel_octjf.hip
 
 namespace saip {
 
@@ -54,114 +47,6 @@ __device__ unsigned long long saip_stamps_oct[1024 * 64];  // [workgroup][wavefr
 #else
 #define STAMP(i)
 #endif
-
-struct OctInst {
-	union {  // the kinematics scratch is dead before the task matrices are written
-		double X[8][12];     // world frame per joint: R (9, row-major) + o (3)
-		struct {
-			double T1[6][8], A[8][8], Am[8][8], Lam[8][8];  // Lam also carries J M_BIE^-1 until Lambda exists; rows 6, 7: padding lanes' scratch
-			double N1[8][8];
-		};
-	};
-	double M[8][8];      // lower triangle of M(q), row r by lane r; kept to the end (the blended singularity strategies want M z)
-	double zo[8][6];     // joint motion vector about the world origin S_r = (w, v): revolute (z, o x z), prismatic (0, z)
-	double J[6][8];
-	double vec[13][8];   // 0 dq, 1 tau, 2 g, 3 / 4 row and scalar exchanges, 5 goal force + moment (general laws), 7 u, 8 d, 9 flags, 10..12 motion-force goal (24)
-	double ist[10];      // integrator state, fetched with the inputs: 0..5 motion-force task (position, orientation), 6..9 the rows of a Gram-path joint
-	                     // task; the control law leaves the advanced motion-force values here for the epilogue.  (Also the padding that makes the
-	                     // instance stride = 2 (mod 32) doubles: the eight instances of a wavefront hit different LDS banks.)
-};
-static_assert(sizeof(OctInst) % 256 == 16, "instance stride must be 2 (mod 32) doubles");
-static_assert(sizeof(OctInst) * 8 * 4 <= 160 * 1024, "four wavefronts per CU (one LDS block each, also with two wavefronts per instance group)");
-
-// eigen-decomposition of a symmetric R x R matrix (R = 4, 6) held, identically, by all eight lanes of an instance: round-robin Jacobi.
-// The R/2 rotations of a round touch disjoint index pairs, so they are computed at the same time in different lanes (lane m of each
-// quad takes pair m; the reciprocal / rsqrt chains are most of a rotation's cost), broadcast inside the quad by DPP quad_perm and applied
-// by every lane to its copy of A; the eigenvector matrix is distributed (lane i < R keeps row i: 4 instead of 4 R operations per
-// rotation) and gathered at the end.  Wave-uniform convergence test per sweep.  Eigenvalues on the diagonal of A, eigenvectors in the
-// columns of V (all lanes alike).  (The row-cyclic form this replaces computed every rotation in every lane: 92 instructions per pair
-// against ~49 now; config 14: 37 k clocks of the blended block's 100 k.)
-template <int R>
-__device__ __forceinline__ void oct_jacobi_n(double (&A)[R][R], double (&V)[R][R], const int lane) {
-	static_assert(R == 4 || R == 6, "even sizes with at most three pairs per round");
-	constexpr int NP = R / 2, RM = R - 1;
-	// which pair of a round this lane computes.  A quad holds joints 2 q, 2 q + 1 of two instances -- even joints take pair 0, odd joints pair 1
-	// (quad_perm [0,1,0,1] / [2,3,2,3] hands them to the quad's lanes of the same instance), and the third pair of a 6 x 6 round is computed by
-	// every lane itself (fetching all three by ds_bpermute from joints 0, 1, 2 measured the same or slower: config 12 27.4 vs 26.7 us).
-	const int r = octl_r(lane), m = r & 1;
-	// t = tan of the rotation angle: sign(theta) / (|theta| + sqrt(theta^2 + 1)), theta = (aqq - app) / (2 apq), written without the
-	// division by apq; hardware reciprocal / rsqrt estimates + Newton steps (arguments are positive and in range)
-	auto rotation = [](const double apq, const double app, const double aqq, double& cs, double& sn, double& tn) {
-		const double d = aqq - app, b2 = 2.0 * apq;
-		const double x = fma(d, d, b2 * b2);
-		const bool rot = x > 1e-300;
-		const double h = rot ? x * oct_rsqrt(x) : 1.0;
-		const double tm = fabs(b2) * oct_rcp(fabs(d) + h);
-		tn = rot ? (((d >= 0.0) == (b2 >= 0.0)) ? tm : -tm) : 0.0;
-		cs = oct_rsqrt(fma(tn, tn, 1.0));
-		sn = tn * cs;
-	};
-	double vrow[R];
-	UNR for (int j = 0; j < R; j++) vrow[j] = (j == r) ? 1.0 : 0.0;
-	for (int sweep = 0; sweep < 12; sweep++) {
-		double off = 0.0, dg = 0.0;
-		UNR for (int p = 0; p < R; p++) {
-			dg = fma(A[p][p], A[p][p], dg);
-			UNR for (int q = p + 1; q < R; q++) off = fma(A[p][q], A[p][q], off);
-		}
-		if (!__any(off > 1e-32 * dg)) break;  // every instance of the wavefront has converged (quadratic convergence: 3 - 6 sweeps)
-		UNR for (int t = 0; t < RM; t++) {
-			// tournament round t: (t, R-1) and ((t + j) mod (R-1), (t - j) mod (R-1)), j = 1 .. R/2 - 1
-			double apq = 0.0, app = 0.0, aqq = 0.0;
-			UNR for (int j = 0; j < NP; j++) {
-				const int a_ = j == 0 ? t : (t + j) % RM, b_ = j == 0 ? RM : (t + RM - j) % RM;
-				const int p = a_ < b_ ? a_ : b_, q = a_ < b_ ? b_ : a_;
-				const bool mine = m == j;
-				apq = mine ? A[p][q] : apq;
-				app = mine ? A[p][p] : app;
-				aqq = mine ? A[q][q] : aqq;
-			}
-			double cs, sn, tn, cs2 = 1.0, sn2 = 0.0, tn2 = 0.0;
-			rotation(apq, app, aqq, cs, sn, tn);
-			if (NP == 3) {  // the third pair of the round, in every lane
-				const int a_ = (t + 2) % RM, b_ = (t + RM - 2) % RM;
-				const int p = a_ < b_ ? a_ : b_, q = a_ < b_ ? b_ : a_;
-				rotation(A[p][q], A[p][p], A[q][q], cs2, sn2, tn2);
-			}
-			UNR for (int j = 0; j < NP; j++) {
-				const int a_ = j == 0 ? t : (t + j) % RM, b_ = j == 0 ? RM : (t + RM - j) % RM;
-				const int p = a_ < b_ ? a_ : b_, q = a_ < b_ ? b_ : a_;
-				double c, s_, tj;
-				if (j == 0) { c = oct_dpp<0x44>(cs); s_ = oct_dpp<0x44>(sn); tj = oct_dpp<0x44>(tn); }
-				else if (j == 1) { c = oct_dpp<0xEE>(cs); s_ = oct_dpp<0xEE>(sn); tj = oct_dpp<0xEE>(tn); }
-				else { c = cs2; s_ = sn2; tj = tn2; }
-				const double apq_j = A[p][q];
-				UNR for (int k = 0; k < R; k++) {
-					if (k != p && k != q) {
-						const double akp = A[k][p], akq = A[k][q];
-						const double np_ = c * akp - s_ * akq, nq_ = s_ * akp + c * akq;
-						A[k][p] = np_;
-						A[p][k] = np_;
-						A[k][q] = nq_;
-						A[q][k] = nq_;
-					}
-				}
-				A[p][p] = fma(-tj, apq_j, A[p][p]);
-				A[q][q] = fma(tj, apq_j, A[q][q]);
-				A[p][q] = 0.0;
-				A[q][p] = 0.0;
-				const double vp = vrow[p], vq = vrow[q];
-				vrow[p] = c * vp - s_ * vq;
-				vrow[q] = s_ * vp + c * vq;
-			}
-		}
-	}
-	UNR for (int i = 0; i < R; i++)
-		UNR for (int c = 0; c < R; c++) V[i][c] = __shfl(vrow[c], octl_src(lane, i));
-}
-__device__ __forceinline__ void oct_jacobi4(double (&A)[4][4], double (&V)[4][4], const int lane) { oct_jacobi_n<4>(A, V, lane); }
-__device__ __forceinline__ void oct_spd_inverse4(const double (&A)[4][4], double (&Ainv)[4][4]) { oct_spd_inverse_n<4>(A, Ainv); }
-
 
 // world frame of this lane's joint for posture q (one joint angle per lane of the instance): local transform, then the three-step
 // prefix product over the chain by DPP row_shr (the same arithmetic as the kernel's own kinematics; used by the singularity
@@ -200,16 +85,48 @@ __device__ __forceinline__ void oct_fk_frame(const ModelDev& md, const int rr, c
 // time, what does not need M: the branch predicate on G = J J^T and the motion-force control law, hands (singular, F) over through LDS
 // at the one workgroup barrier of the kernel and exits.  Each has its own LDS block; every other synchronisation point is
 // wavefront-local (LDS operations of one wavefront execute in order).
-template <bool DUO>
-__device__ __forceinline__ void oct_sync() {
-	if (DUO) {
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-	} else {
-		__syncthreads();
+// The word wavefront B hands its per-instance decisions over with (a double in LDS next to the values it decided): the torque is overridden
+// (blended strategies, pass-through of a fully singular task), the instance is outside the non-singular branch, its task was reduced, it
+// was blended, a bounded poll ran out.  (Macros: the lean instantiations must compile to what the written-out text compiled to.)
+enum { OCT_FL_OVR = 1, OCT_FL_SINGULAR = 2, OCT_FL_TRUNCATED = 4, OCT_FL_BLENDED = 8, OCT_FL_LOST = 16 };
+#define OCT_FLAGS_PACK(ovr, singular, truncated, blended, lost)                                                                              \
+	(((ovr) ? (double)OCT_FL_OVR : 0.0) + ((singular) ? (double)OCT_FL_SINGULAR : 0.0) + ((truncated) ? (double)OCT_FL_TRUNCATED : 0.0) + \
+	 ((blended) ? (double)OCT_FL_BLENDED : 0.0) + ((lost) ? (double)OCT_FL_LOST : 0.0))
+#define OCT_FLAGS_UNPACK(word, ovr, singular, truncated, blended, lost) \
+	{                                                                   \
+		const int fl = (int)(word);                                     \
+		ovr = (fl & OCT_FL_OVR) != 0;                                   \
+		singular = (fl & OCT_FL_SINGULAR) != 0;                         \
+		truncated = (fl & OCT_FL_TRUNCATED) != 0;                       \
+		blended = (fl & OCT_FL_BLENDED) != 0;                           \
+		lost = lost || (fl & OCT_FL_LOST) != 0;                         \
 	}
-}
+
+// The end of the full joint task in the rank-one nullspace of a 6-dof task (derivation: "JointTask (S = I) in the nullspace" in the body):
+// tv = tau_r + v_own / zz (z.a + rho z.f) with zr = this lane's entry of z', v_own = its entry of v = M z (up to scale), zz = |z'|^2,
+// zv = z'.v, VJ = entry j of v (an expression in j), ai / fi = this joint's a and PD(I) force, rho = Lambda_mod / Lambda by the joint task's
+// decoupling type.  Reads jt_dec, general_bie, mb, beta, eclamp, act, r of the body.  (A macro: as a function the one-wavefront general
+// instantiations needed 8 to 12 bytes more scratch, and the blended block's use is live in the lean ones.)
+#define OCT_JOINT_RANK1_TAIL(tv, zr, v_own, zz, zv, VJ, ai, fi, tau_r)                            \
+	{                                                                                             \
+		const double za = octl_sum(zr * ai);                                                      \
+		const double zf = octl_sum(zr * fi);                                                      \
+		double rho = 1.0;                                                                         \
+		if (jt_dec == DEC_IMPEDANCE) {                                                            \
+			rho = zz * oct_rcp(zv);                                                               \
+		} else if (jt_dec == DEC_BIE) {                                                           \
+			if (general_bie) {                                                                    \
+				double mbv = 0.0;                                                                 \
+				UNR for (int j = 0; j < N; j++) mbv = fma(mb[j], VJ, mbv); /* (M_BIE^-1 v)_rr */  \
+				const double qb = octl_sum(act ? v_own * mbv : 0.0);                              \
+				rho = zv * oct_rcp(qb);                                                           \
+			} else {                                                                              \
+				const double ze = octl_sum((act && r == eclamp) ? zr : 0.0);                      \
+				rho = zv * oct_rcp(fma(-beta * ze, ze, zv));                                      \
+			}                                                                                     \
+		}                                                                                         \
+		tv = fma(v_own * oct_rcp(zz), fma(rho, zf, za), tau_r); /* tau += Jh^T g */               \
+	}
 
 // ROLE 0: the whole cycle in one wavefront; 1 / 2: wavefront A / B of the two-wavefront form (compile-time, so that neither carries the
 // other's registers: as run-time branches of one body the merged live ranges spilled)
@@ -604,18 +521,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		UNR for (int a = 0; a < 6; a++) prr = fma(-jc6[a], x6[a], prr);
 		double bestw = act ? prr : -1.0;
 		int jbw = r;
-#define OCT_ARGMAX_STEP(CTRL)                                                                                   \
-	{                                                                                                           \
-		const double ob = oct_dpp<CTRL>(bestw);                                                                 \
-		const int oj = __builtin_amdgcn_update_dpp(0, jbw, CTRL, 0xF, 0xF, true);                               \
-		const bool take = ob > bestw || (ob == bestw && oj < jbw);                                              \
-		bestw = take ? ob : bestw;                                                                              \
-		jbw = take ? oj : jbw;                                                                                  \
-	}
-		OCT_ARGMAX_STEP(OCT_BFLY0)
-		OCT_ARGMAX_STEP(OCT_BFLY1)
-		OCT_ARGMAX_STEP(OCT_BFLY2)
-#undef OCT_ARGMAX_STEP
+		OCT_ARGMAX(bestw, jbw)
 		const int src = octl_src(lane, jbw);
 		UNR for (int a = 0; a < 6; a++) xb[a] = __shfl(x6[a], src);
 		double z_own = (rr == jbw) ? 1.0 : 0.0;
@@ -1032,7 +938,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 				sm.vec[6][r] = fo;
 				sm.vec[5][r] = ffo;
 			}
-			if (r == 6) sm.vec[6][6] = (singular ? 1.0 : 0.0) + (truncated ? 2.0 : 0.0);
+			if (r == 6) sm.vec[6][6] = (singular ? (double)OCT_FL_SINGULAR : 0.0) + (truncated ? (double)OCT_FL_TRUNCATED : 0.0);  // (the two bits this stack has)
 		}
 		STAMP(29);
 		__syncthreads();
@@ -1045,8 +951,8 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			}
 			if (GJ != 0) {  // (headline stack: the final flags arrive at the second barrier)
 				const int fl = (int)smB.vec[6][6];
-				singular = (fl & 1) != 0;
-				truncated = (fl & 2) != 0;
+				singular = (fl & OCT_FL_SINGULAR) != 0;
+				truncated = (fl & OCT_FL_TRUNCATED) != 0;
 			}
 		}
 		if (GJ == 0) {
@@ -1183,113 +1089,83 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 				tv = fma(pr * oct_rcp(zz), sj, tau_r);
 			}
 		} else {
-		if (roleA) {
-		if (mf_dec == DEC_IMPEDANCE) {
-			UNR for (int a = 0; a < 6; a++) g[a] = Fum6[a] + Ff6[a];
-		} else if (mf_dec == DEC_BIE && general_bie) {
-			double Lb[6][6], dinvb[6], y[6];
-			UNR for (int i = 0; i < 6; i++)
-				UNR for (int j = 0; j <= i; j++) Lb[i][j] = sm.Am[i][j];
-			oct_cholesky<6>(Lb, dinvb);
-			oct_solve<6>(Lb, dinvb, Fum6, y);
-			UNR for (int a = 0; a < 6; a++) g[a] = y[a] + Ff6[a];
-		} else {
-			double y1[6];
-			oct_solve<6>(L6, dinv6, Fum6, y1);
-			if (mf_dec == DEC_BIE) {  // rank-one form (beta = 0 when nothing is clamped)
-				double t[6], y2[6], ty1 = 0.0, ty2 = 0.0;
-				UNR for (int a = 0; a < 6; a++) {
-					double sacc = 0.0;
-					UNR for (int l = 0; l < N; l++) sacc = fma(Jf[a][l], mcol[l], sacc);
-					t[a] = sacc;
+			if (roleA) {
+				if (mf_dec == DEC_IMPEDANCE) {
+					UNR for (int a = 0; a < 6; a++) g[a] = Fum6[a] + Ff6[a];
+				} else if (mf_dec == DEC_BIE && general_bie) {
+					double Lb[6][6], dinvb[6], y[6];
+					UNR for (int i = 0; i < 6; i++)
+						UNR for (int j = 0; j <= i; j++) Lb[i][j] = sm.Am[i][j];
+					oct_cholesky<6>(Lb, dinvb);
+					oct_solve<6>(Lb, dinvb, Fum6, y);
+					UNR for (int a = 0; a < 6; a++) g[a] = y[a] + Ff6[a];
+				} else {
+					double y1[6];
+					oct_solve<6>(L6, dinv6, Fum6, y1);
+					if (mf_dec == DEC_BIE) {  // rank-one form (beta = 0 when nothing is clamped)
+						double t[6], y2[6], ty1 = 0.0, ty2 = 0.0;
+						UNR for (int a = 0; a < 6; a++) {
+							double sacc = 0.0;
+							UNR for (int l = 0; l < N; l++) sacc = fma(Jf[a][l], mcol[l], sacc);
+							t[a] = sacc;
+						}
+						oct_solve<6>(L6, dinv6, t, y2);
+						UNR for (int a = 0; a < 6; a++) {
+							ty1 = fma(t[a], y1[a], ty1);
+							ty2 = fma(t[a], y2[a], ty2);
+						}
+						const double gamma = beta * oct_rcp(fma(-beta, ty2, 1.0));
+						UNR for (int a = 0; a < 6; a++) g[a] = fma(gamma * ty1, y2[a], y1[a]) + Ff6[a];
+					} else {
+						UNR for (int a = 0; a < 6; a++) g[a] = y1[a] + Ff6[a];
+					}
 				}
-				oct_solve<6>(L6, dinv6, t, y2);
-				UNR for (int a = 0; a < 6; a++) {
-					ty1 = fma(t[a], y1[a], ty1);
-					ty2 = fma(t[a], y2[a], ty2);
+				double tau1[N];
+				UNR for (int j = 0; j < N; j++) {
+					double s = 0.0;
+					UNR for (int a = 0; a < 6; a++) s = fma(Jf[a][j], g[a], s);
+					tau1[j] = s;
+					wr = fma(mi[j], s, wr);  // (M^-1 tau_prec)_rr: M^-1 symmetric, mi = its column rr
 				}
-				const double gamma = beta * oct_rcp(fma(-beta, ty2, 1.0));
-				UNR for (int a = 0; a < 6; a++) g[a] = fma(gamma * ty1, y2[a], y1[a]) + Ff6[a];
-			} else {
-				UNR for (int a = 0; a < 6; a++) g[a] = y1[a] + Ff6[a];
+				UNR for (int j = 0; j < N; j++) tau_r = (j == rr) ? tau1[j] : tau_r;
+			}  // roleA
+			// ---- JointTask (S = I) in the nullspace of the 6-dof task, JointTask.cpp:218-356.  N_1 = I - M^-1 J^T Lambda J has rank one:
+			// N_1 = z z^T M / (z^T M z), z spanning null(J).  Its ROW rr, e_rr - J^T (A^-1 t1c) with t1c = this lane's column of T1 = J M^-1,
+			// needs nothing from the other lanes and is z_rr (M z)^T / (z^T M z).  The row of largest norm (largest |z_rr|) is broadcast:
+			// v ~ M z, then z'_rr = (M^-1 v)_rr from this lane's column of M^-1.  With the range basis U = z' / |z'| (matrixRangeBasis of
+			// Jp = N_1, one direction) the task reduces to scalars: Jh = U^T Jp = v^T / (|z'| s'), Lambda = (Jh M^-1 Jh^T)^-1 = z'.v / |z'|^2, and
+			//   tau_joint = Jh^T (Lambda a1 + Lambda_mod b1) = v / |z'|^2 (z'.a + rho z'.f),   a = ddq_d - M^-1 tau_prec, f = the PD(I) force,
+			// rho = Lambda_mod / Lambda: 1 (full decoupling), |z'|^2 / z'.v (impedance), z'.v / (z'.v - beta z'_e^2) (bounded inertia, one
+			// clamped entry e: M_BIE^-1 = M^-1 - beta m m^T and m^T M z' = z'_e), z'.v / (v^T M_BIE^-1 v) (several clamped entries).
+			if (roleB) {
+				double x6[6], rowv[N], nr = 0.0;
+				oct_solve<6>(L6, dinv6, t1c, x6);
+				UNR for (int j = 0; j < N; j++) {
+					double acc = (j == rr) ? 1.0 : 0.0;
+					UNR for (int a = 0; a < 6; a++) acc = fma(-Jf[a][j], x6[a], acc);
+					rowv[j] = acc;
+					nr = fma(acc, acc, nr);
+				}
+				double bestw = act ? nr : -1.0;
+				int jbw = r;
+				OCT_ARGMAX(bestw, jbw)
+				const int src = octl_src(lane, jbw);
+				UNR for (int j = 0; j < N; j++) {
+					v[j] = __shfl(rowv[j], src);
+					zr = fma(mi[j], v[j], zr);
+					v_own = (j == rr) ? v[j] : v_own;
+				}
+				zr = act ? zr : 0.0;
+				zz = octl_sum(zr * zr);
+				zv = octl_sum(zr * v_own);
+			}  // roleB
+			if (roleA) {
+				fi = fi_pre;  // (the joint control law ran behind M(q), see fi_pre)
 			}
-		}
-		double tau1[N];
-		UNR for (int j = 0; j < N; j++) {
-			double s = 0.0;
-			UNR for (int a = 0; a < 6; a++) s = fma(Jf[a][j], g[a], s);
-			tau1[j] = s;
-			wr = fma(mi[j], s, wr);  // (M^-1 tau_prec)_rr: M^-1 symmetric, mi = its column rr
-		}
-		UNR for (int j = 0; j < N; j++) tau_r = (j == rr) ? tau1[j] : tau_r;
-		}  // roleA
-		// ---- JointTask (S = I) in the nullspace of the 6-dof task, JointTask.cpp:218-356.  N_1 = I - M^-1 J^T Lambda J has rank one:
-		// N_1 = z z^T M / (z^T M z), z spanning null(J).  Its ROW rr, e_rr - J^T (A^-1 t1c) with t1c = this lane's column of T1 = J M^-1,
-		// needs nothing from the other lanes and is z_rr (M z)^T / (z^T M z).  The row of largest norm (largest |z_rr|) is broadcast:
-		// v ~ M z, then z'_rr = (M^-1 v)_rr from this lane's column of M^-1.  With the range basis U = z' / |z'| (matrixRangeBasis of
-		// Jp = N_1, one direction) the task reduces to scalars: Jh = U^T Jp = v^T / (|z'| s'), Lambda = (Jh M^-1 Jh^T)^-1 = z'.v / |z'|^2, and
-		//   tau_joint = Jh^T (Lambda a1 + Lambda_mod b1) = v / |z'|^2 (z'.a + rho z'.f),   a = ddq_d - M^-1 tau_prec, f = the PD(I) force,
-		// rho = Lambda_mod / Lambda: 1 (full decoupling), |z'|^2 / z'.v (impedance), z'.v / (z'.v - beta z'_e^2) (bounded inertia, one
-		// clamped entry e: M_BIE^-1 = M^-1 - beta m m^T and m^T M z' = z'_e), z'.v / (v^T M_BIE^-1 v) (several clamped entries).
-		if (roleB) {
-		double x6[6], rowv[N], nr = 0.0;
-		oct_solve<6>(L6, dinv6, t1c, x6);
-		UNR for (int j = 0; j < N; j++) {
-			double acc = (j == rr) ? 1.0 : 0.0;
-			UNR for (int a = 0; a < 6; a++) acc = fma(-Jf[a][j], x6[a], acc);
-			rowv[j] = acc;
-			nr = fma(acc, acc, nr);
-		}
-		double bestw = act ? nr : -1.0;
-		int jbw = r;
-#define OCT_ARGMAX_STEP(CTRL)                                                                                   \
-	{                                                                                                           \
-		const double ob = oct_dpp<CTRL>(bestw);                                                                 \
-		const int oj = __builtin_amdgcn_update_dpp(0, jbw, CTRL, 0xF, 0xF, true);                               \
-		const bool take = ob > bestw || (ob == bestw && oj < jbw);                                              \
-		bestw = take ? ob : bestw;                                                                              \
-		jbw = take ? oj : jbw;                                                                                  \
-	}
-		OCT_ARGMAX_STEP(OCT_BFLY0)
-		OCT_ARGMAX_STEP(OCT_BFLY1)
-		OCT_ARGMAX_STEP(OCT_BFLY2)
-#undef OCT_ARGMAX_STEP
-		const int src = octl_src(lane, jbw);
-		UNR for (int j = 0; j < N; j++) {
-			v[j] = __shfl(rowv[j], src);
-			zr = fma(mi[j], v[j], zr);
-			v_own = (j == rr) ? v[j] : v_own;
-		}
-		zr = act ? zr : 0.0;
-		zz = octl_sum(zr * zr);
-		zv = octl_sum(zr * v_own);
-		}  // roleB
-		if (roleA) {
-		fi = fi_pre;  // (the joint control law ran behind M(q), see fi_pre)
-		}
-		if (ROLE == 0) {
-		const double ai = jg_ddq - wr;
-		const double za = octl_sum(zr * ai);
-		const double zf = octl_sum(zr * fi);
-		double rho = 1.0;
-		if (jt_dec == DEC_IMPEDANCE) {
-			rho = zz * oct_rcp(zv);
-		} else if (jt_dec == DEC_BIE) {
-			if (general_bie) {
-				if (DUO) {
-					UNR for (int j = 0; j < N; j++) v[j] = smB.vec[4][j];
-				}
-				double mbv = 0.0;
-				UNR for (int j = 0; j < N; j++) mbv = fma(mb[j], v[j], mbv);  // (M_BIE^-1 v)_rr
-				const double qb = octl_sum(act ? v_own * mbv : 0.0);
-				rho = zv * oct_rcp(qb);
-			} else {
-				const double ze = octl_sum((act && r == eclamp) ? zr : 0.0);
-				rho = zv * oct_rcp(fma(-beta * ze, ze, zv));
+			if (ROLE == 0) {
+				const double ai = jg_ddq - wr;
+				OCT_JOINT_RANK1_TAIL(tv, zr, v_own, zz, zv, v[j], ai, fi, tau_r)
 			}
-		}
-		tv = fma(v_own * oct_rcp(zz), fma(rho, zf, za), tau_r);  // tau += Jh^T g
-		}
 		}  // !CF
 		// ------------------------------------------------------------------------------------------------------------------------------
 		// Blended singularity strategies, in this kernel (SingularityHandler.cpp:100-121, 146-228, 230-295, 310-367; the reference's default
@@ -1668,18 +1544,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 				}
 				double bestw = zn;
 				int jbw = r;
-	#define OCT_ARGMAX_STEP(CTRL)                                                                                   \
-		{                                                                                                           \
-		const double ob = oct_dpp<CTRL>(bestw);                                                                 \
-		const int oj = __builtin_amdgcn_update_dpp(0, jbw, CTRL, 0xF, 0xF, true);                               \
-		const bool take = ob > bestw || (ob == bestw && oj < jbw);                                              \
-		bestw = take ? ob : bestw;                                                                              \
-		jbw = take ? oj : jbw;                                                                                  \
-		}
-				OCT_ARGMAX_STEP(OCT_BFLY0)
-				OCT_ARGMAX_STEP(OCT_BFLY1)
-				OCT_ARGMAX_STEP(OCT_BFLY2)
-	#undef OCT_ARGMAX_STEP
+				OCT_ARGMAX(bestw, jbw)
 				const int srcp = octl_src(lane, jbw);
 				double zb = (r == jbw) ? 1.0 : 0.0;
 				UNR for (int c = 0; c < 6; c++) zb = fma(-vown[c], __shfl(vown[c], srcp), zb);
@@ -1694,23 +1559,9 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 				}
 				const double aib = jg_ddq - wq;
 				const double zzb = octl_sum(zb * zb), sb = octl_sum(act ? zb * mz : 0.0);
-				const double zab = octl_sum(zb * aib), zfb = octl_sum(zb * fi);
-				double rhob = 1.0;  // rho |z|^2 in the notation above: tau = (M z)_r / |z|^2 (z.a + rho' z.f), rho' = Lambda_mod / Lambda
-				if (jt_dec == DEC_IMPEDANCE) {
-					rhob = zzb * oct_rcp(sb);
-				} else if (jt_dec == DEC_BIE) {
-					if (general_bie) {
-						double mbv = 0.0;
-						UNR for (int j = 0; j < N; j++) mbv = fma(mb[j], __shfl(mz, octl_src(lane, j)), mbv);
-						const double qb = octl_sum(act ? mz * mbv : 0.0);
-						rhob = sb * oct_rcp(qb);
-					} else {
-						const double ze = octl_sum((act && r == eclamp) ? zb : 0.0);
-						rhob = sb * oct_rcp(fma(-beta * ze, ze, sb));
-					}
-				}
+				double tvb;  // tau = (M z)_r / |z|^2 (z.a + rho z.f): the same end as the ordinary path's, with v = M z itself
+				OCT_JOINT_RANK1_TAIL(tvb, zb, mz, zzb, sb, __shfl(mz, octl_src(lane, j)), aib, fi, tmf)
 				STAMP(28);
-				const double tvb = fma(mz * oct_rcp(zzb), fma(rhob, zfb, zab), tmf);
 				if (blend) {
 					tvo = tvb;
 					ovr = true;
@@ -1725,18 +1576,13 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			if (hand == 2) {
 				if (ROLE == 2) {
 					sm.vec[1][r] = tvo;
-					sm.vec[2][r] = (ovr ? 1.0 : 0.0) + (singular ? 2.0 : 0.0) + (truncated ? 4.0 : 0.0) + (blended_i ? 8.0 : 0.0) + (lost ? 16.0 : 0.0);
+					sm.vec[2][r] = OCT_FLAGS_PACK(ovr, singular, truncated, blended_i, lost);
 				}
 				STAMP(31);
 				__syncthreads();
 				if (ROLE == 1) {
 					tvo = smB.vec[1][r];
-					const int fl = (int)smB.vec[2][r];
-					ovr = (fl & 1) != 0;
-					singular = (fl & 2) != 0;
-					truncated = (fl & 4) != 0;
-					blended_i = (fl & 8) != 0;
-					lost = lost || (fl & 16) != 0;
+					OCT_FLAGS_UNPACK(smB.vec[2][r], ovr, singular, truncated, blended_i, lost)
 				}
 			}
 			if (ROLE == 2) return false;
@@ -1746,7 +1592,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 				sm.vec[7][r] = zr;
 				sm.vec[8][r] = v_own;
 				sm.vec[1][r] = tvo;
-				sm.vec[2][r] = (ovr ? 1.0 : 0.0) + (singular ? 2.0 : 0.0) + (truncated ? 4.0 : 0.0) + (blended_i ? 8.0 : 0.0) + (lost ? 16.0 : 0.0);
+				sm.vec[2][r] = OCT_FLAGS_PACK(ovr, singular, truncated, blended_i, lost);
 				if (r == 0) {
 					sm.vec[3][0] = zz;
 					sm.vec[3][1] = zv;
@@ -1762,371 +1608,53 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			zv = smB.vec[3][1];
 			{
 				tvo = smB.vec[1][r];
-				const int fl = (int)smB.vec[2][r];
-				ovr = (fl & 1) != 0;
-				singular = (fl & 2) != 0;
-				truncated = (fl & 4) != 0;
-				blended_i = (fl & 8) != 0;
-				lost = lost || (fl & 16) != 0;
+				OCT_FLAGS_UNPACK(smB.vec[2][r], ovr, singular, truncated, blended_i, lost)
 			}
 		}
 		if (ROLE == 1 && !CF) {
-		const double ai = jg_ddq - wr;
-		const double za = octl_sum(zr * ai);
-		const double zf = octl_sum(zr * fi);
-		double rho = 1.0;
-		if (jt_dec == DEC_IMPEDANCE) {
-			rho = zz * oct_rcp(zv);
-		} else if (jt_dec == DEC_BIE) {
-			if (general_bie) {
-				if (DUO) {
-					UNR for (int j = 0; j < N; j++) v[j] = smB.vec[4][j];
-				}
-				double mbv = 0.0;
-				UNR for (int j = 0; j < N; j++) mbv = fma(mb[j], v[j], mbv);  // (M_BIE^-1 v)_rr
-				const double qb = octl_sum(act ? v_own * mbv : 0.0);
-				rho = zv * oct_rcp(qb);
-			} else {
-				const double ze = octl_sum((act && r == eclamp) ? zr : 0.0);
-				rho = zv * oct_rcp(fma(-beta * ze, ze, zv));
+			if (jt_dec == DEC_BIE && general_bie) {  // (the one form of rho that wants v in full: B left it in its block)
+				UNR for (int j = 0; j < N; j++) v[j] = smB.vec[4][j];
 			}
-		}
-		tv = fma(v_own * oct_rcp(zz), fma(rho, zf, za), tau_r);  // tau += Jh^T g
+			const double ai = jg_ddq - wr;
+			OCT_JOINT_RANK1_TAIL(tv, zr, v_own, zz, zv, v[j], ai, fi, tau_r)
 		}
 		if (ovr) tv = tvo;  // the blended strategies / the pass-through of a fully singular task decided this instance's torque
 		if (BROWS && lost) singular = true;
-
 	} else {
-	{
-		double g[6], t3[6], jc[6];
-		UNR for (int a = 0; a < 6; a++) {
-			g[a] = sm.vec[2][a];
-			jc[a] = (ROLE == 1 ? smB : sm).J[a][rr];
-		}
-		double s = 0.0;
-		UNR for (int a = 0; a < 6; a++) s = fma(jc[a], g[a], s);
-		tau_r = s;
-		UNR for (int a = 0; a < 6; a++) {
-			double acc = 0.0;
-			UNR for (int c = 0; c < 6; c++) acc = fma(sm.Lam[a][c], jc[c], acc);
-			t3[a] = acc;
-		}
-		UNR for (int i = 0; i < N; i++) {
-			double acc = (i == rr) ? 1.0 : 0.0;
-			UNR for (int a = 0; a < 6; a++) acc = fma(-sm.T1[a][i], t3[a], acc);
-			cj[i] = acc;
-			cn = fma(acc, acc, cn);
-		}
-		UNR for (int i = 0; i < N; i++) sm.N1[r][i] = cj[i];  // transposed storage: row r = column r of N_1
-		sm.vec[1][r] = tau_r;
-	}
-	STAMP(11);
-	// ---------------------------------------------------------------- JointTask, general path (GJ): any selection matrix with m <= 4 rows behind any
-	// motion-force task.  Lane j holds column j of Jp = S N_1 (m x 7).  Left singular vectors / squared singular values of Jp = eigen-pairs
-	// of its 4 x 4 Gram matrix (sums over the lanes by DPP), by an unrolled Jacobi solve in registers; matrixRangeBasis keeps the directions
-	// with sigma_i / sigma_0 >= 1e-3 (JointTask.cpp:233); the rest of the task algebra is r x r with dropped directions padded.
-	if (GJ == 1) {
-		double cp[4];
-		UNR for (int i = 0; i < 4; i++) {
-			double sc = 0.0;
-			UNR for (int l = 0; l < N; l++) sc = fma(jt.S[i * N + l], cj[l], sc);  // rows >= m of the stored S are zero
-			cp[i] = act ? sc : 0.0;
-		}
-		double Gp[4][4], V4[4][4], trp = 0.0;
-		UNR for (int i = 0; i < 4; i++)
-			UNR for (int k = 0; k <= i; k++) {
-				const double gs = octl_sum(cp[i] * cp[k]);
-				Gp[i][k] = gs;
-				Gp[k][i] = gs;
-				if (i == k) trp += gs;
-			}
-		// Usual case: Jp has full row rank, matrixRangeBasis returns the identity (sai-model: task_dof == rows) and no eigen-solve is needed.
-		// Certificate (the one of the motion-force branch predicate): lambda_max <= trace, so a positive definite  Gp - 1e-6 trace I  on
-		// the m task rows proves sigma_min / sigma_max > 1e-3; trace / m >= 1e-6 proves sigma_max >= 1e-3.  Only wavefronts that hold an
-		// instance it cannot decide run the register Jacobi solve (measured, config 3: 19 k of 40 k clocks per wavefront were this solve).
-		bool full_rank = trp * 0.25 >= 1e-6;
 		{
-			double Gs[4][4];
-			const double sh = 1e-6 * trp;
-			UNR for (int i = 0; i < 4; i++)
-				UNR for (int k = 0; k <= i; k++) Gs[i][k] = Gp[i][k];
-			UNR for (int i = 0; i < 4; i++) Gs[i][i] = (i < mj) ? Gs[i][i] - sh : 1.0;
-			UNR for (int kk = 0; kk < 4; kk++) {
-				const double d = Gs[kk][kk];
-				full_rank = full_rank && (d > 1e-13 * trp);
-				const double id = oct_rcp(d);
-				UNR for (int i = kk + 1; i < 4; i++) {
-					const double lik = Gs[i][kk] * id;
-					UNR for (int k = kk + 1; k <= i; k++) Gs[i][k] = fma(-lik, Gs[k][kk], Gs[i][k]);
-				}
+			double g[6], t3[6], jc[6];
+			UNR for (int a = 0; a < 6; a++) {
+				g[a] = sm.vec[2][a];
+				jc[a] = (ROLE == 1 ? smB : sm).J[a][rr];
 			}
+			double s = 0.0;
+			UNR for (int a = 0; a < 6; a++) s = fma(jc[a], g[a], s);
+			tau_r = s;
+			UNR for (int a = 0; a < 6; a++) {
+				double acc = 0.0;
+				UNR for (int c = 0; c < 6; c++) acc = fma(sm.Lam[a][c], jc[c], acc);
+				t3[a] = acc;
+			}
+			UNR for (int i = 0; i < N; i++) {
+				double acc = (i == rr) ? 1.0 : 0.0;
+				UNR for (int a = 0; a < 6; a++) acc = fma(-sm.T1[a][i], t3[a], acc);
+				cj[i] = acc;
+				cn = fma(acc, acc, cn);
+			}
+			UNR for (int i = 0; i < N; i++) sm.N1[r][i] = cj[i];  // transposed storage: row r = column r of N_1
+			sm.vec[1][r] = tau_r;
 		}
-#if defined(SAIP_OCT_FORCE_EXACT)
-		full_rank = false;
-#endif
-		bool keep[4];
-		double jh[4];
-		UNR for (int i = 0; i < 4; i++)
-			UNR for (int k = 0; k < 4; k++) V4[i][k] = (i == k) ? 1.0 : 0.0;
-		UNR for (int c = 0; c < 4; c++) {
-			keep[c] = c < mj;
-			jh[c] = keep[c] ? cp[c] : 0.0;
+		STAMP(11);
+		// the joint task behind a motion-force task that leaves it more than one direction (saip_oct_joint_tails.h)
+		if (GJ == 1) {
+			const double jg[3] = {jg_q, jg_dq, jg_ddq};
+			tv = oct_joint_tail_gram<DUO, N>(P, sm, lane, cj, mi, mb, mcol, beta, general_bie, jt_dec, q_r, jg, tau_r, jt_ie_new);
+		} else if (GJ == 2) {
+			const int rmax = trunc_mode ? 5 : N - kmf;  // wave-uniform bound; a reduced task leaves rank 7 - ns <= 5, found by the clean-gap rule
+			bool bad;
+			tv = oct_joint_tail_pivoted<DUO, N>(sm, lane, cj, mi, mb, mcol, beta, general_bie, jt_dec, rmax, fi_pre, jg_ddq, tau_r, bad);
+			if (bad) singular = true;
 		}
-		if (__any(!full_rank)) {
-			double Ve[4][4];
-			oct_jacobi4(Gp, Ve, lane);
-			double lmaxp = 0.0;
-			UNR for (int c = 0; c < 4; c++) lmaxp = fmax(lmaxp, Gp[c][c]);
-			const bool any_range = (sqrt(fmax(trp, 0.0)) >= 1e-3) && (sqrt(lmaxp) >= 1e-3);
-			UNR for (int c = 0; c < 4; c++) {
-				const bool kc = any_range && (sqrt(fmax(Gp[c][c], 0.0) / lmaxp) >= 1e-3);
-				double sj = 0.0;
-				UNR for (int i = 0; i < 4; i++) sj = fma(Ve[i][c], cp[i], sj);
-				if (!full_rank) {
-					keep[c] = kc;
-					jh[c] = kc ? sj : 0.0;  // own column of Jh = U^T Jp
-					UNR for (int i = 0; i < 4; i++) V4[i][c] = Ve[i][c];
-				}
-			}
-		}
-		// gather Jh, q, the joint-task goal rows and w = M^-1 tau_prec for the whole instance
-		double tauv[N];
-		UNR for (int j = 0; j < N; j++) tauv[j] = sm.vec[1][j];
-		double wr = 0.0;
-		UNR for (int l = 0; l < N; l++) wr = fma(mi[l], tauv[l], wr);
-		UNR for (int c = 0; c < 4; c++) sm.T1[c][r] = jh[c];
-		sm.vec[4][r] = wr;
-		sm.vec[6][r] = q_r;
-		sm.vec[7][r] = jg_q;
-		sm.vec[8][r] = jg_dq;
-		sm.vec[3][r] = jg_ddq;
-		oct_sync<DUO>();
-		double Jh[4][N];
-		UNR for (int c = 0; c < 4; c++)
-			UNR for (int j = 0; j < N; j++) Jh[c][j] = sm.T1[c][j];
-		double t1v[4], A4[4][4], Lam4[4][4], Lmod4[4][4];
-		UNR for (int c = 0; c < 4; c++) {
-			double st = 0.0;
-			UNR for (int l = 0; l < N; l++) st = fma(Jh[c][l], mi[l], st);  // (Jh M^-1)[c][rr]: M^-1 symmetric
-			t1v[c] = act ? st : 0.0;
-		}
-		UNR for (int c = 0; c < 4; c++)
-			UNR for (int k = 0; k <= c; k++) {
-				const double gs = octl_sum(t1v[c] * jh[k]);
-				A4[c][k] = (c == k && !keep[c]) ? 1.0 : gs;
-			}
-		oct_spd_inverse4(A4, Lam4);
-		if (jt_dec == DEC_FULL) {
-			UNR for (int c = 0; c < 4; c++)
-				UNR for (int k = 0; k < 4; k++) Lmod4[c][k] = Lam4[c][k];
-		} else if (jt_dec == DEC_IMPEDANCE) {
-			UNR for (int c = 0; c < 4; c++)
-				UNR for (int k = 0; k < 4; k++) Lmod4[c][k] = (c == k) ? 1.0 : 0.0;
-		} else if (general_bie) {
-			double tbv[4];
-			UNR for (int c = 0; c < 4; c++) {
-				double st = 0.0;
-				UNR for (int l = 0; l < N; l++) st = fma(Jh[c][l], mb[l], st);
-				tbv[c] = act ? st : 0.0;
-			}
-			UNR for (int c = 0; c < 4; c++)
-				UNR for (int k = 0; k <= c; k++) {
-					const double gs = octl_sum(tbv[c] * jh[k]);
-					A4[c][k] = (c == k && !keep[c]) ? 1.0 : gs;
-				}
-			oct_spd_inverse4(A4, Lmod4);
-		} else {  // rank-one bounded-inertia form: Lambda_mod = Lambda + gamma (Lambda t)(Lambda t)^T, t = Jh m
-			double t[4], lt[4], qq = 0.0;
-			UNR for (int c = 0; c < 4; c++) {
-				double st = 0.0;
-				UNR for (int l = 0; l < N; l++) st = fma(Jh[c][l], mcol[l], st);
-				t[c] = st;
-			}
-			UNR for (int c = 0; c < 4; c++) {
-				double sl = 0.0;
-				UNR for (int k = 0; k < 4; k++) sl = fma(Lam4[c][k], t[k], sl);
-				lt[c] = sl;
-				qq = fma(t[c], sl, qq);
-			}
-			const double gamma = beta * oct_rcp(fma(-beta, qq, 1.0));
-			UNR for (int c = 0; c < 4; c++)
-				UNR for (int k = 0; k < 4; k++) Lmod4[c][k] = fma(gamma * lt[c], lt[k], Lam4[c][k]);
-		}
-		// control law of the (at most four) task rows, every lane alike (JointTask.cpp:285-356)
-		double qa[N], dqa[N], wa[N];
-		UNR for (int j = 0; j < N; j++) {
-			qa[j] = sm.vec[6][j];
-			dqa[j] = sm.vec[0][j];
-			wa[j] = sm.vec[4][j];
-		}
-		const bool track = (jt.has_ki || P.integ_always);
-		double a1[4] = {0, 0, 0, 0}, b1[4] = {0, 0, 0, 0};
-		UNR for (int i = 0; i < 4; i++) {
-			double cur = 0.0, vel = 0.0, sw = 0.0;
-			UNR for (int l = 0; l < N; l++) {
-				const double sil = jt.S[i * N + l];
-				cur = fma(sil, qa[l], cur);
-				vel = fma(sil, dqa[l], vel);
-				sw = fma(sil, wa[l], sw);
-			}
-			const bool row = i < mj;
-			const double gq = row ? sm.vec[7][i] : 0.0, gdq = row ? sm.vec[8][i] : 0.0, gddq = row ? sm.vec[3][i] : 0.0;
-			const double e = cur - gq;
-			double ie = (track && row) ? sm.ist[6 + i] : 0.0;
-			ie += e * jt.dt;  // :323-324
-			jt_ie_new = (r == i) ? ie : jt_ie_new;  // lane i keeps row i for the epilogue
-			double fi;
-			if (jt.vel_sat) {  // :327-341
-				double vdes = -jt.kp[i] * jt.kvinv[i] * e - jt.ki[i] * jt.kvinv[i] * ie;
-				vdes = fmin(fmax(vdes, -jt.sat[i]), jt.sat[i]);
-				fi = -jt.kv[i] * (vel - vdes);
-			} else {
-				fi = -jt.kp[i] * e - jt.kv[i] * (vel - gdq) - jt.ki[i] * ie;  // :342-345
-			}
-			const double ai = gddq - sw;
-			UNR for (int c = 0; c < 4; c++) {
-				a1[c] = fma(V4[i][c], row ? ai : 0.0, a1[c]);
-				b1[c] = fma(V4[i][c], row ? fi : 0.0, b1[c]);
-			}
-		}
-		double tj = tau_r;
-		UNR for (int c = 0; c < 4; c++) {
-			double gc = 0.0;
-			UNR for (int k = 0; k < 4; k++) gc = fma(Lam4[c][k], a1[k], fma(Lmod4[c][k], b1[k], gc));  // :348-351
-			tj = fma(jh[c], keep[c] ? gc : 0.0, tj);  // tau += Jh^T g
-		}
-		tv = tj;
-	} else if (GJ == 2) {
-		// ------------------------------------------------------------ full joint task (S = I) behind a motion-force task of rank k < 6: Jp = N_1 has
-		// rank 7 - k (2..5).  Column-pivoted Gram-Schmidt over the instance's lanes (lane j owns column j): arg-max of the column norms by
-		// a DPP butterfly carrying the index, the pivot column travels by ds_bpermute, the deflation coefficients are the rows of
-		// Jh = U^T Jp (the same clean-gap rule as the lane kernel; an ambiguous gap is reported as status 1, never silently truncated).
-		const int rmax = trunc_mode ? 5 : N - kmf;  // wave-uniform bound; a reduced task leaves rank 7 - ns <= 5, found by the clean-gap rule
-		double Wc[N], jh[5], uown[5];
-		UNR for (int i = 0; i < N; i++) Wc[i] = act ? cj[i] : 0.0;
-		UNR for (int s5 = 0; s5 < 5; s5++) jh[s5] = uown[s5] = 0.0;
-		double c0 = 1.0;
-		bool going = true, bad = false;
-		int rank = 0;
-		UNR for (int s5 = 0; s5 <= 5; s5++) {
-			if (s5 <= rmax) {
-				double cnw = 0.0;
-				UNR for (int i = 0; i < N; i++) cnw = fma(Wc[i], Wc[i], cnw);
-				double bestw = act ? cnw : -1.0;
-				int jbw = r;
-#define OCT_ARGMAX_STEP(CTRL)                                                                                   \
-	{                                                                                                           \
-		const double ob = oct_dpp<CTRL>(bestw);                                                                 \
-		const int oj = __builtin_amdgcn_update_dpp(0, jbw, CTRL, 0xF, 0xF, true);                               \
-		const bool take = ob > bestw || (ob == bestw && oj < jbw);                                              \
-		bestw = take ? ob : bestw;                                                                              \
-		jbw = take ? oj : jbw;                                                                                  \
-	}
-				OCT_ARGMAX_STEP(OCT_BFLY0)
-				OCT_ARGMAX_STEP(OCT_BFLY1)
-				OCT_ARGMAX_STEP(OCT_BFLY2)
-#undef OCT_ARGMAX_STEP
-				if (s5 == 0) {
-					const double frob2 = octl_sum(act ? cnw : 0.0);
-					c0 = bestw;
-					if (frob2 < 1e-6) going = false;  // ||Jp||_F < 1e-3: empty range
-					else if (bestw < 1e-5) { going = false; bad = true; }
-				} else if (going) {
-					const double ratio = bestw / c0;
-					if (ratio < 1e-20) going = false;                         // numerically exact rank below the bound
-					else if (ratio < 1e-4 || s5 == rmax) { going = false; bad = true; }  // ambiguous gap, or more directions than 7 - k
-				}
-				if (s5 < rmax && s5 < 5) {
-					const int src = octl_src(lane, jbw);
-					const double inv = going ? oct_rsqrt(bestw) : 0.0;
-					double u[N], dd = 0.0;
-					UNR for (int i = 0; i < N; i++) {
-						u[i] = __shfl(Wc[i], src) * inv;
-						dd = fma(u[i], Wc[i], dd);
-					}
-					UNR for (int i = 0; i < N; i++) Wc[i] = fma(-u[i], dd, Wc[i]);
-					double uo = 0.0;
-					UNR for (int i = 0; i < N; i++) uo = (i == rr) ? u[i] : uo;
-					jh[s5 < 5 ? s5 : 0] = act ? dd : 0.0;
-					uown[s5 < 5 ? s5 : 0] = act ? uo : 0.0;
-					if (going) rank = s5 + 1;
-				}
-			}
-		}
-		if (bad) singular = true;
-		// Lambda = (Jh M^-1 Jh^T)^-1 (rank x rank, padded to 5): gather Jh, own column of T1, sums over the lanes
-		double tauv[N];
-		UNR for (int j = 0; j < N; j++) tauv[j] = sm.vec[1][j];
-		UNR for (int c = 0; c < 5; c++) sm.T1[c][r] = jh[c];
-		oct_sync<DUO>();
-		double Jh[5][N];
-		UNR for (int c = 0; c < 5; c++)
-			UNR for (int j = 0; j < N; j++) Jh[c][j] = sm.T1[c][j];
-		double t1v[5], wr = 0.0, A5[5][5], Lam5[5][5], Lmod5[5][5];
-		UNR for (int l = 0; l < N; l++) wr = fma(mi[l], tauv[l], wr);  // (M^-1 tau_prec)_rr
-		UNR for (int c = 0; c < 5; c++) {
-			double st = 0.0;
-			UNR for (int l = 0; l < N; l++) st = fma(Jh[c][l], mi[l], st);
-			t1v[c] = act ? st : 0.0;
-		}
-		UNR for (int c = 0; c < 5; c++)
-			UNR for (int k5 = 0; k5 <= c; k5++) {
-				const double gs = octl_sum(t1v[c] * jh[k5]);
-				A5[c][k5] = (c == k5 && c >= rank) ? 1.0 : gs;
-			}
-		oct_spd_inverse_n<5>(A5, Lam5);
-		if (jt_dec == DEC_FULL) {
-			UNR for (int c = 0; c < 5; c++)
-				UNR for (int k5 = 0; k5 < 5; k5++) Lmod5[c][k5] = Lam5[c][k5];
-		} else if (jt_dec == DEC_IMPEDANCE) {
-			UNR for (int c = 0; c < 5; c++)
-				UNR for (int k5 = 0; k5 < 5; k5++) Lmod5[c][k5] = (c == k5) ? 1.0 : 0.0;
-		} else if (general_bie) {
-			double tbv[5];
-			UNR for (int c = 0; c < 5; c++) {
-				double st = 0.0;
-				UNR for (int l = 0; l < N; l++) st = fma(Jh[c][l], mb[l], st);
-				tbv[c] = act ? st : 0.0;
-			}
-			UNR for (int c = 0; c < 5; c++)
-				UNR for (int k5 = 0; k5 <= c; k5++) {
-					const double gs = octl_sum(tbv[c] * jh[k5]);
-					A5[c][k5] = (c == k5 && c >= rank) ? 1.0 : gs;
-				}
-			oct_spd_inverse_n<5>(A5, Lmod5);
-		} else {
-			double t[5], lt[5], qq = 0.0;
-			UNR for (int c = 0; c < 5; c++) {
-				double st = 0.0;
-				UNR for (int l = 0; l < N; l++) st = fma(Jh[c][l], mcol[l], st);
-				t[c] = st;
-			}
-			UNR for (int c = 0; c < 5; c++) {
-				double sl = 0.0;
-				UNR for (int k5 = 0; k5 < 5; k5++) sl = fma(Lam5[c][k5], t[k5], sl);
-				lt[c] = sl;
-				qq = fma(t[c], sl, qq);
-			}
-			const double gamma = beta * oct_rcp(fma(-beta, qq, 1.0));
-			UNR for (int c = 0; c < 5; c++)
-				UNR for (int k5 = 0; k5 < 5; k5++) Lmod5[c][k5] = fma(gamma * lt[c], lt[k5], Lam5[c][k5]);
-		}
-		// (the control law of this lane's joint ran behind M(q): fi_pre); its range coordinates by sums over the lanes
-		const double fi = fi_pre;
-		const double ai = jg_ddq - wr;
-		double a1[5], b1[5];
-		UNR for (int c = 0; c < 5; c++) {
-			a1[c] = octl_sum(uown[c] * ai);
-			b1[c] = octl_sum(uown[c] * fi);
-		}
-		double tj = tau_r;
-		UNR for (int c = 0; c < 5; c++) {
-			double gc = 0.0;
-			UNR for (int k5 = 0; k5 < 5; k5++) gc = fma(Lam5[c][k5], a1[k5], fma(Lmod5[c][k5], b1[k5], gc));
-			tj = fma(jh[c], (c < rank) ? gc : 0.0, tj);
-		}
-		tv = tj;
-	}
 	}  // GJ != 0
 	STAMP(14);
 	// ---------------------------------------------------------------- post-processing, RobotController.cpp:86-116
@@ -2134,50 +1662,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		const double lim = md.effort[rr];
 		tv = tv > lim ? lim : (tv < -lim ? -lim : tv);
 	}
-	if (FULL && P.jla) {
-		// joint limit avoidance wrap, RobotController.cpp:96-112: tau = JLA.computeTorques(tau) + N_c^T tau with
-		// N_c^T = I - S^T (S M^-1 S^T)^-1 S M^-1 over the joints inside a limit zone (padded to 7 x 7 with identity rows).  The zone logic is
-		// per joint = per lane; the rest only runs when some instance of the wavefront touches a zone.
-		bool zone;
-		const double tj = jla_joint(q_r, dq_r, md.q_lower[rr], md.q_upper[rr], md.vel_limit[rr], md.effort[rr], tv, &zone);
-		const bool in_zone = zone && act && !singular;
-		if (__any(in_zone)) {
-			sm.vec[1][r] = tv;
-			sm.vec[3][r] = in_zone ? 1.0 : 0.0;
-			oct_sync<DUO>();
-			double tall[N], zall[N];
-			UNR for (int j = 0; j < N; j++) {
-				tall[j] = sm.vec[1][j];
-				zall[j] = sm.vec[3][j];
-			}
-			double sacc = 0.0;
-			UNR for (int j = 0; j < N; j++) sacc = fma(mi[j], tall[j], sacc);  // (M^-1 tau)_rr
-			sm.vec[4][r] = in_zone ? sacc : 0.0;
-			UNR for (int j = 0; j < N; j++) sm.N1[r][j] = (in_zone && zall[j] != 0.0) ? mi[j] : ((j == rr) ? 1.0 : 0.0);  // N1 is dead: masked M^-1
-			oct_sync<DUO>();
-			double L[N][N], dinv[N], y[N], x[N];
-			UNR for (int i = 0; i < N; i++)
-				UNR for (int j = 0; j <= i; j++) L[i][j] = sm.N1[i][j];
-			oct_cholesky<N>(L, dinv);
-			UNR for (int i = 0; i < N; i++) {
-				double sy = sm.vec[4][i];
-				UNR for (int k = 0; k < i; k++) sy = fma(-L[i][k], y[k], sy);
-				y[i] = sy * dinv[i];
-			}
-			UNR for (int i = N - 1; i >= 0; i--) {
-				double sx = y[i];
-				UNR for (int k = i + 1; k < N; k++) sx = fma(-L[k][i], x[k], sx);
-				x[i] = sx * dinv[i];
-			}
-			double yr = 0.0;
-			UNR for (int i = 0; i < N; i++) yr = (i == rr) ? x[i] : yr;
-			if (in_zone) tv = tj + tv - yr;
-			if (P.torque_sat) {
-				const double lim = md.effort[rr];
-				tv = tv > lim ? lim : (tv < -lim ? -lim : tv);
-			}
-		}
-	}
+	if (FULL && P.jla) tv = oct_jla_wrap<DUO, N>(P, sm, lane, q_r, dq_r, mi, singular, tv);  // joint limit avoidance wrap, RobotController.cpp:96-112
 	if (P.gravity_comp) {
 		const double* gv = md.gravity;
 		const double ax_ = Ic[1] - Ic[0] * o[0], ay_ = Ic[2] - Ic[0] * o[1], az_ = Ic[3] - Ic[0] * o[2];  // m (c - o)
@@ -2206,26 +1691,6 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	}
 	STAMP(15);
 	return live && to_tail;
-}
-
-// Slow tail (round 4): the instances of this wavefront that ended flagged -- outside SingularityHandler's non-singular branch with the blended
-// strategies on (SingularityHandler.cpp:100-121, 146-158, 310-367), a reduced task with fewer than two directions left, an ambiguous rank
-// gap -- are recomputed here, one after the other, by the general kernel's body (saip_wg_cycle.h: Jacobi eigen-pairs of the Gram matrix,
-// U_ns / U_s split, blended type-1 / type-2 strategies with their per-instance state) on this wavefront's own LDS block, which the cycle no
-// longer needs.  The instance's inputs are untouched (nothing was written for it, no integrator advanced), so the result is what the list
-// launch behind the kernel used to produce -- without the launch, which cost 4.5 us per cycle whether or not anything was on the list.
-// Everything the tail needs is in HBM or batch-uniform: no register of the ordinary path lives across it.
-__device__ __forceinline__ void oct_slow_tail(const CycleParams& P, const bool flagged, void* lds) {
-	const unsigned long long votes = __ballot(flagged);
-	if (__builtin_expect(votes == 0ull, 1)) return;  // wave-uniform: the usual case
-	static_assert(sizeof(WgSmem<8>) <= 8 * sizeof(OctInst), "the general kernel's block fits the eight instance blocks of a wavefront");
-	WgSmem<8>& wsm = *reinterpret_cast<WgSmem<8>*>(lds);
-	for (int g = 0; g < 8; g++) {
-		const int l0 = ((g >> 1) << 4) | (g & 1);  // the lane of joint 0 of instance g (octl_grp / octl_r)
-		if (((votes >> l0) & 1ull) == 0ull) continue;    // wave-uniform
-		SAIP_WG_SYNC();  // the block's previous user (the cycle, or the instance before) is done with it
-		wg_cycle<8, 64>(P, (int)blockIdx.x * 8 + g, wsm);
-	}
 }
 
 // SIM (rollouts of stacks without internal OTGs and without a slow path behind): the wavefront that finished the cycle of its eight
@@ -2274,19 +1739,7 @@ __global__ void __launch_bounds__(DUO ? 128 : 64) saip_cycle_oct(const CyclePara
 	}
 }
 
-// two wavefronts per instance group for the lean stack while the launch still fits the chip in one round (two workgroups per CU = one
-// wavefront per SIMD: 4096 instances on 256 CUs); beyond that the second wavefront only competes for issue slots (measured, B = 6144:
-// 14.3 us against 10.8 us)
-static bool oct_duo_enabled(const int workgroups) {
-	static int cus = 0;
-	if (cus == 0) {
-		int dev = 0, n = 0;
-		if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-		cus = n;
-	}
-	return workgroups <= 2 * cus;
-}
-
+// (two wavefronts per instance group while the launch still fits the chip in one round: oct_duo_enabled, saip_oct_slow_tail.h)
 hipError_t launch_cycle_oct(const CycleParams& P, hipStream_t stream) {
 	const dim3 grid((P.B + 7) / 8), block(64);
 	const bool duo = oct_duo_enabled((int)grid.x);

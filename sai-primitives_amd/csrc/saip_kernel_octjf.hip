@@ -27,14 +27,7 @@
 #include "saip_fk.h"
 #include "saip_law.h"
 #include "saip_oct_common.h"
-// the general kernel's body as this kernel's slow tail (see saip_kernel_oct.hip: oct_slow_tail): one wavefront plays the 64-thread workgroup
-#define SAIP_WG_SYNC()                                          \
-	do {                                                        \
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  \
-		__builtin_amdgcn_wave_barrier();                        \
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  \
-	} while (0)
-#include "saip_wg_cycle.h"
+#include "saip_oct_slow_tail.h"  // the general kernel's body as this kernel's slow tail
 
 namespace saip {
 
@@ -602,21 +595,6 @@ __device__ __forceinline__ bool jf_body(const CycleParams& P, JfInst* smem, doub
 	return live && to_tail;
 }
 
-// Slow tail (round 4; the same as saip_kernel_oct.hip's): the instances of this wavefront whose motion-force task left the non-singular branch
-// are recomputed here by the general kernel's body on this wavefront's own LDS block -- no list, no second launch behind the kernel.
-__device__ __forceinline__ void jf_slow_tail(const CycleParams& P, const bool flagged, void* lds) {
-	const unsigned long long votes = __ballot(flagged);
-	if (__builtin_expect(votes == 0ull, 1)) return;  // wave-uniform: the usual case
-	static_assert(sizeof(WgSmem<8>) <= 8 * sizeof(JfInst), "the general kernel's block fits the eight instance blocks of a wavefront");
-	WgSmem<8>& wsm = *reinterpret_cast<WgSmem<8>*>(lds);
-	for (int g = 0; g < 8; g++) {
-		const int l0 = ((g >> 1) << 4) | (g & 1);  // the lane of joint 0 of instance g (interleaved layout)
-		if (((votes >> l0) & 1ull) == 0ull) continue;
-		SAIP_WG_SYNC();
-		wg_cycle<8, 64>(P, (int)blockIdx.x * 8 + g, wsm);
-	}
-}
-
 template <bool DUO>
 __global__ void __launch_bounds__(DUO ? 128 : 64) saip_cycle_octjf(const CycleParams P) {
 	__shared__ JfInst smem[8];
@@ -624,22 +602,16 @@ __global__ void __launch_bounds__(DUO ? 128 : 64) saip_cycle_octjf(const CyclePa
 	if (DUO) {
 		const bool wave_b = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 1;
 		if (wave_b) jf_body<2>(P, smem, bx);
-		else jf_slow_tail(P, jf_body<1>(P, smem, bx), smem);
+		else oct_slow_tail(P, jf_body<1>(P, smem, bx), smem);
 	} else {
-		jf_slow_tail(P, jf_body<0>(P, smem, bx), smem);
+		oct_slow_tail(P, jf_body<0>(P, smem, bx), smem);
 	}
 }
 
 // two wavefronts per group of eight instances while the launch fits the chip in one round (<= 2 workgroups per CU), as in saip_kernel_oct.hip
 hipError_t launch_cycle_octjf(const CycleParams& P, hipStream_t stream) {
 	const dim3 grid((P.B + 7) / 8);
-	static int cus = 0;
-	if (cus == 0) {
-		int dev = 0, n = 0;
-		if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-		cus = n;
-	}
-	if ((int)grid.x <= 2 * cus) hipLaunchKernelGGL(saip_cycle_octjf<true>, grid, dim3(128), 0, stream, P);
+	if (oct_duo_enabled((int)grid.x)) hipLaunchKernelGGL(saip_cycle_octjf<true>, grid, dim3(128), 0, stream, P);
 	else hipLaunchKernelGGL(saip_cycle_octjf<false>, grid, dim3(64), 0, stream, P);
 	return hipGetLastError();
 }

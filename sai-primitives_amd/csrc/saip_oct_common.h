@@ -87,6 +87,21 @@ __device__ __forceinline__ double octl_max(double x) {
 }
 // the three exchange steps of a butterfly over the eight lanes of an instance (arg-max with its index, ...)
 constexpr int OCT_BFLY0 = DPP_QUAD_XOR2, OCT_BFLY1 = DPP_ROW_ROR + 4, OCT_BFLY2 = DPP_ROW_ROR + 8;
+// arg-max over the eight lanes of an instance: every lane ends with the largest `best` and the joint index `idx` that came with it (ties: the
+// lowest index).  A macro, not a function: as a function taking references the kernels built under max-ilp scheduling came out different
+// (more instructions, scratch or registers in 14 of 16 instantiations of saip_cycle_oct).
+#define OCT_ARGMAX_STEP(CTRL, best, idx)                                                                        \
+	{                                                                                                           \
+		const double ob = oct_dpp<CTRL>(best);                                                                  \
+		const int oj = __builtin_amdgcn_update_dpp(0, idx, CTRL, 0xF, 0xF, true);                               \
+		const bool take = ob > best || (ob == best && oj < idx);                                                \
+		best = take ? ob : best;                                                                                \
+		idx = take ? oj : idx;                                                                                  \
+	}
+#define OCT_ARGMAX(best, idx)            \
+	OCT_ARGMAX_STEP(OCT_BFLY0, best, idx) \
+	OCT_ARGMAX_STEP(OCT_BFLY1, best, idx) \
+	OCT_ARGMAX_STEP(OCT_BFLY2, best, idx)
 // value of joint r - D (shr) / r + D (shl) of the same instance; lanes without such a joint get `fill` (0 or 1: the identity's diagonal)
 template <int D, bool ONE>
 __device__ __forceinline__ double octl_shr(const double x) {
@@ -174,6 +189,94 @@ __device__ __forceinline__ void oct_spd_inverse_n(const double (&A)[R][R], doubl
 		UNR for (int i = 0; i < R; i++) Ainv[i][col] = x[i];
 	}
 }
+
+// eigen-decomposition of a symmetric R x R matrix (R = 4, 6) held, identically, by all eight lanes of an instance: round-robin Jacobi.
+// The R/2 rotations of a round touch disjoint index pairs, so they are computed at the same time in different lanes (lane m of each
+// quad takes pair m; the reciprocal / rsqrt chains are most of a rotation's cost), broadcast inside the quad by DPP quad_perm and applied
+// by every lane to its copy of A; the eigenvector matrix is distributed (lane i < R keeps row i: 4 instead of 4 R operations per
+// rotation) and gathered at the end.  Wave-uniform convergence test per sweep.  Eigenvalues on the diagonal of A, eigenvectors in the
+// columns of V (all lanes alike).  (The row-cyclic form this replaces computed every rotation in every lane: 92 instructions per pair
+// against ~49 now; config 14: 37 k clocks of the blended block's 100 k.)
+template <int R>
+__device__ __forceinline__ void oct_jacobi_n(double (&A)[R][R], double (&V)[R][R], const int lane) {
+	static_assert(R == 4 || R == 6, "even sizes with at most three pairs per round");
+	constexpr int NP = R / 2, RM = R - 1;
+	// which pair of a round this lane computes.  A quad holds joints 2 q, 2 q + 1 of two instances -- even joints take pair 0, odd joints pair 1
+	// (quad_perm [0,1,0,1] / [2,3,2,3] hands them to the quad's lanes of the same instance), and the third pair of a 6 x 6 round is computed by
+	// every lane itself (fetching all three by ds_bpermute from joints 0, 1, 2 measured the same or slower: config 12 27.4 vs 26.7 us).
+	const int r = octl_r(lane), m = r & 1;
+	// t = tan of the rotation angle: sign(theta) / (|theta| + sqrt(theta^2 + 1)), theta = (aqq - app) / (2 apq), written without the
+	// division by apq; hardware reciprocal / rsqrt estimates + Newton steps (arguments are positive and in range)
+	auto rotation = [](const double apq, const double app, const double aqq, double& cs, double& sn, double& tn) {
+		const double d = aqq - app, b2 = 2.0 * apq;
+		const double x = fma(d, d, b2 * b2);
+		const bool rot = x > 1e-300;
+		const double h = rot ? x * oct_rsqrt(x) : 1.0;
+		const double tm = fabs(b2) * oct_rcp(fabs(d) + h);
+		tn = rot ? (((d >= 0.0) == (b2 >= 0.0)) ? tm : -tm) : 0.0;
+		cs = oct_rsqrt(fma(tn, tn, 1.0));
+		sn = tn * cs;
+	};
+	double vrow[R];
+	UNR for (int j = 0; j < R; j++) vrow[j] = (j == r) ? 1.0 : 0.0;
+	for (int sweep = 0; sweep < 12; sweep++) {
+		double off = 0.0, dg = 0.0;
+		UNR for (int p = 0; p < R; p++) {
+			dg = fma(A[p][p], A[p][p], dg);
+			UNR for (int q = p + 1; q < R; q++) off = fma(A[p][q], A[p][q], off);
+		}
+		if (!__any(off > 1e-32 * dg)) break;  // every instance of the wavefront has converged (quadratic convergence: 3 - 6 sweeps)
+		UNR for (int t = 0; t < RM; t++) {
+			// tournament round t: (t, R-1) and ((t + j) mod (R-1), (t - j) mod (R-1)), j = 1 .. R/2 - 1
+			double apq = 0.0, app = 0.0, aqq = 0.0;
+			UNR for (int j = 0; j < NP; j++) {
+				const int a_ = j == 0 ? t : (t + j) % RM, b_ = j == 0 ? RM : (t + RM - j) % RM;
+				const int p = a_ < b_ ? a_ : b_, q = a_ < b_ ? b_ : a_;
+				const bool mine = m == j;
+				apq = mine ? A[p][q] : apq;
+				app = mine ? A[p][p] : app;
+				aqq = mine ? A[q][q] : aqq;
+			}
+			double cs, sn, tn, cs2 = 1.0, sn2 = 0.0, tn2 = 0.0;
+			rotation(apq, app, aqq, cs, sn, tn);
+			if (NP == 3) {  // the third pair of the round, in every lane
+				const int a_ = (t + 2) % RM, b_ = (t + RM - 2) % RM;
+				const int p = a_ < b_ ? a_ : b_, q = a_ < b_ ? b_ : a_;
+				rotation(A[p][q], A[p][p], A[q][q], cs2, sn2, tn2);
+			}
+			UNR for (int j = 0; j < NP; j++) {
+				const int a_ = j == 0 ? t : (t + j) % RM, b_ = j == 0 ? RM : (t + RM - j) % RM;
+				const int p = a_ < b_ ? a_ : b_, q = a_ < b_ ? b_ : a_;
+				double c, s_, tj;
+				if (j == 0) { c = oct_dpp<0x44>(cs); s_ = oct_dpp<0x44>(sn); tj = oct_dpp<0x44>(tn); }
+				else if (j == 1) { c = oct_dpp<0xEE>(cs); s_ = oct_dpp<0xEE>(sn); tj = oct_dpp<0xEE>(tn); }
+				else { c = cs2; s_ = sn2; tj = tn2; }
+				const double apq_j = A[p][q];
+				UNR for (int k = 0; k < R; k++) {
+					if (k != p && k != q) {
+						const double akp = A[k][p], akq = A[k][q];
+						const double np_ = c * akp - s_ * akq, nq_ = s_ * akp + c * akq;
+						A[k][p] = np_;
+						A[p][k] = np_;
+						A[k][q] = nq_;
+						A[q][k] = nq_;
+					}
+				}
+				A[p][p] = fma(-tj, apq_j, A[p][p]);
+				A[q][q] = fma(tj, apq_j, A[q][q]);
+				A[p][q] = 0.0;
+				A[q][p] = 0.0;
+				const double vp = vrow[p], vq = vrow[q];
+				vrow[p] = c * vp - s_ * vq;
+				vrow[q] = s_ * vp + c * vq;
+			}
+		}
+	}
+	UNR for (int i = 0; i < R; i++)
+		UNR for (int c = 0; c < R; c++) V[i][c] = __shfl(vrow[c], octl_src(lane, i));
+}
+__device__ __forceinline__ void oct_jacobi4(double (&A)[4][4], double (&V)[4][4], const int lane) { oct_jacobi_n<4>(A, V, lane); }
+__device__ __forceinline__ void oct_spd_inverse4(const double (&A)[4][4], double (&Ainv)[4][4]) { oct_spd_inverse_n<4>(A, Ainv); }
 
 // cyclic Jacobi eigen-solve of a symmetric n x n matrix in LDS by ONE lane (rare exact path): eigenvalues on the diagonal of A,
 // eigenvectors in the columns of V (optional)
