@@ -162,6 +162,24 @@ struct CycleParams {
 	// in front of the goals than in front of anything else the wavefront asks for.
 	const double* goal2[2];
 	double* integ2[2];
+	// eight-lane kernels: the batch-uniform words of the model, of the stack's first motion-force task and of its first joint task that the
+	// ordinary path reads behind its fences and LDS stores, once more, as kernel arguments (launch words).  Read from the model / task block there they are vector loads
+	// of a uniform word at the point of use -- the compiler can no longer prove the blocks unclobbered -- each with its memory round trip on
+	// the dependent chain; kernel arguments arrive with the scalar loads that fetch the pointers.  The blocks keep their fields (the general
+	// kernel, the slow tail and the queries read those); make_params derives these from the same host copies at every launch, so a setter
+	// shows in both at the next launch.  Appended at the end: the other kernels take this struct by value and do not notice.
+	struct LaunchWords {
+		int all_axis_z;        // ModelDev::all_axis_z
+		int body;              // TaskDev::body
+		int sing_handling;     // TaskDev::sing_handling
+		int strategies_on;     // sing_handling && sing_strategies && sh != nullptr: the blended strategies run in the kernel
+		int mf_dec, mf_has_ki; // motion-force task: TaskDev::decoupling, ::has_ki
+		int jt_dec, jt_has_ki, jt_vel_sat, pad_;  // joint task: TaskDev::decoupling, ::has_ki, ::vel_sat
+		double dt, s_max, s_abs_tol, cert_kroot;  // motion-force task
+		double jt_dt;
+		double pos[3], rot[9];
+		double gain[18];       // motion-force task: kp_pos, kv_pos, ki_pos, kp_ori, kv_ori, ki_ori (the run of the task block, in its order)
+	} lw;
 };
 
 // forward dynamics + semi-implicit Euler step (saip_dynamics.hip)

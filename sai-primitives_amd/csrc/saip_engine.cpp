@@ -957,6 +957,35 @@ saip_status saip::eng::ensure_lazy_state(saip_batch* b) {
 	}
 	return SAIP_OK;
 }
+// The launch words of the eight-lane kernels (CycleParams::lw): what they read of the model block, of the stack's first motion-force
+// task and of its first joint task, derived from the host copies the blocks were uploaded from.  The one place that does so: a word and
+// its field cannot disagree.
+static CycleParams::LaunchWords launch_words(const ModelDev& md, const TaskDev* mf, const TaskDev* jt) {
+	CycleParams::LaunchWords w = {};
+	w.all_axis_z = md.all_axis_z;
+	if (jt) {
+		w.jt_dec = jt->decoupling;
+		w.jt_has_ki = jt->has_ki;
+		w.jt_vel_sat = jt->vel_sat;
+		w.jt_dt = jt->dt;
+	}
+	if (!mf) return w;
+	w.body = mf->body;
+	w.sing_handling = mf->sing_handling;
+	w.strategies_on = (mf->sing_handling && mf->sing_strategies && mf->sh != nullptr) ? 1 : 0;
+	w.mf_dec = mf->decoupling;
+	w.mf_has_ki = mf->has_ki;
+	w.dt = mf->dt;
+	w.s_max = mf->s_max;
+	w.s_abs_tol = mf->s_abs_tol;
+	w.cert_kroot = mf->cert_kroot;
+	for (int e = 0; e < 3; e++) w.pos[e] = mf->pos[e];
+	for (int e = 0; e < 9; e++) w.rot[e] = mf->rot[e];
+	const double* const gains[6] = {mf->kp_pos, mf->kv_pos, mf->ki_pos, mf->kp_ori, mf->kv_ori, mf->ki_ori};
+	for (int k = 0; k < 6; k++)
+		for (int e = 0; e < 3; e++) w.gain[3 * k + e] = gains[k][e];
+	return w;
+}
 static saip_status make_params(saip_batch* b, CycleParams& P, bool diag) {
 	{
 		saip_status st = ensure_lazy_state(b);
@@ -1032,6 +1061,12 @@ static saip_status make_params(saip_batch* b, CycleParams& P, bool diag) {
 			P.any_bie = 1;
 			P.bie_thr = d.bie_threshold;
 		}
+	}
+	{
+		const TaskDev* jt = nullptr;
+		for (size_t t = 0; t < b->tasks.size() && !jt; t++)
+			if (b->tasks[t].dev.type == saip::TASK_JOINT) jt = &b->tasks[t].dev;
+		P.lw = launch_words(b->model->dev, P.mf_task[0] >= 0 ? &b->tasks[P.mf_task[0]].dev : nullptr, jt);
 	}
 	P.reinit_task = -1;
 	P.reinit_mask = 7;

@@ -177,8 +177,15 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	const TaskDev& mf = P.tasks[0];
 	const TaskDev& jt = P.tasks[1];
 	const int kmf = FULL ? mf.k : 6;  // rank of the motion-force task (partial tasks: rows >= k of its Jacobian are zero, diagonals padded with 1)
+	// Launch words (CycleParams::lw): in the two-wavefront forms the batch-uniform words the ordinary path reads behind its first
+	// fence come from the kernel arguments -- read from the model / task block there they are vector loads of a uniform word, each with a
+	// memory round trip on the dependent chain.  Read by the lean two-wavefront form only (existing template parameters, not a property of the
+	// words): the one-wavefront forms, whose loads of these words are scalar loads hoisted to the top anyway, and the general (FULL)
+	// two-wavefront forms measured slower or no faster with the words and read the blocks as before.
+	constexpr bool LW = DUO && !FULL;
+	// (each read is written at its point of use, `LW ? word : field`: hoisted into a local, the general two-wavefront forms compiled differently)
 	// the decoupling types decide branches in the tail of the cycle; read there (vector loads of a uniform word behind the fences) each cost a
-	// memory round trip on the critical path -- requested here, made scalar behind the local transform
+	// memory round trip on the critical path -- launch words, or requested here and made scalar behind the local transform
 	const int mf_dec_v = mf.decoupling, jt_dec_v = jt.decoupling;
 	// disableSingularityHandling(): near-singular tasks are reduced in the kernel instead of being flagged (batch-uniform)
 	const bool trunc_mode = FULL && GJ == 2 && P.oct_truncate;
@@ -238,7 +245,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	// the very start they make the wavefront wait before it has issued anything else -- the two-wavefront form asks behind the local transform
 	// (7.23 -> 7.00 us), the one-wavefront form, which has the motion-force goal loads in flight there anyway, at the start (9.18 vs 9.01 us).
 #define OCT_REQUEST_STATE(SFX)                                                                                          \
-	const bool track_mf##SFX = (mf.has_ki || P.integ_always), track_jt##SFX = (jt.has_ki || P.integ_always);            \
+	const bool track_mf##SFX = ((LW ? P.lw.mf_has_ki : mf.has_ki) || P.integ_always), track_jt##SFX = ((LW ? P.lw.jt_has_ki : jt.has_ki) || P.integ_always); \
 	double mfi_pre##SFX = 0.0, jti_pre##SFX = 0.0;                                                                      \
 	if (roleB && track_mf##SFX && r < 6) mfi_pre##SFX = saip_ldg(P.integ2[0], (size_t)r * ld + b);                                   \
 	if (roleA && track_jt##SFX) jti_pre##SFX = saip_ldg(P.integ2[1], (size_t)(GJ == 1 ? rj : rr) * ld + b);                          \
@@ -260,7 +267,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		if (jtype_r == 1) {
 			double s, c;
 			sincos_joint(q_r, &s, &c);
-			if (md.all_axis_z) {  // (batch-uniform) rotation about the local z axis: R0 Rz(q) mixes the first two columns of R0 only
+			if (LW ? P.lw.all_axis_z : md.all_axis_z) {  // (batch-uniform) rotation about the local z axis: R0 Rz(q) mixes the first two columns of R0 only
 				UNR for (int i = 0; i < 3; i++) {
 					Tw[3 * i] = R0[3 * i] * c + R0[3 * i + 1] * s;
 					Tw[3 * i + 1] = R0[3 * i + 1] * c - R0[3 * i] * s;
@@ -292,7 +299,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		lawc[lane] = lc0;
 		if (lane < 26) lawc[64 + lane] = lc1;
 	}
-	const int mf_dec = __builtin_amdgcn_readfirstlane(mf_dec_v), jt_dec = __builtin_amdgcn_readfirstlane(jt_dec_v);
+	const int mf_dec = LW ? P.lw.mf_dec : __builtin_amdgcn_readfirstlane(mf_dec_v), jt_dec = LW ? P.lw.jt_dec : __builtin_amdgcn_readfirstlane(jt_dec_v);
 	OCT_REQUEST_STATE(_l)  // (dead code in the one-wavefront form)
 	if (ROLE == 1) {
 		UNR for (int e = 0; e < 3; e++) comv[e] = md.com[rr][e];
@@ -381,13 +388,15 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	// (two-wavefront form: B alone forms it, A takes the Jacobian from B's block behind the barrier below -- B gets there first)
 	double pw[3] = {0, 0, 0}, Rc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, jwc[6] = {0, 0, 0, 0, 0, 0};  // control point, control frame, this joint's column of the world Jacobian [Jv; Jw]
 	if (ROLE != 1) {
-		const int bd = mf.body;
+		// (body, control point and control frame are launch words in the two-wavefront forms: read from the task block here, behind the frames' LDS store, they were
+		// vector loads whose round trip sat in front of the LDS read that depends on `body`)
+		const int bd = LW ? P.lw.body : mf.body;
 		double Rb[12];
 		UNR for (int e = 0; e < 12; e++) Rb[e] = sm.X[bd][e];
-		oct_mat3_vec(Rb, mf.pos, pw);
+		oct_mat3_vec(Rb, (LW ? P.lw.pos : mf.pos), pw);
 		UNR for (int e = 0; e < 3; e++) pw[e] += Rb[9 + e];
 		UNR for (int i = 0; i < 3; i++)
-			UNR for (int j = 0; j < 3; j++) Rc[3 * i + j] = Rb[3 * i] * mf.rot[j] + Rb[3 * i + 1] * mf.rot[3 + j] + Rb[3 * i + 2] * mf.rot[6 + j];
+			UNR for (int j = 0; j < 3; j++) Rc[3 * i + j] = Rb[3 * i] * (LW ? P.lw.rot : mf.rot)[j] + Rb[3 * i + 1] * (LW ? P.lw.rot : mf.rot)[3 + j] + Rb[3 * i + 2] * (LW ? P.lw.rot : mf.rot)[6 + j];
 		const bool on = rr <= bd;
 		const double rx = pw[0] - o[0], ry = pw[1] - o[1], rz = pw[2] - o[2];
 		const double c0 = z[1] * rz - z[2] * ry, c1 = z[2] * rx - z[0] * rz, c2 = z[0] * ry - z[1] * rx;
@@ -411,9 +420,9 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	if (roleA && GJ != 1) {
 		const double e = q_r - jg_q;
 		double ie = track_jt ? jti_pre : 0.0;
-		ie += e * jt.dt;  // :323-324
+		ie += e * (LW ? P.lw.jt_dt : jt.dt);  // :323-324
 		jt_ie_new = ie;
-		if (jt.vel_sat) {  // :327-341
+		if (LW ? P.lw.jt_vel_sat : jt.vel_sat) {  // :327-341
 			double vdes = -jkp_r * jt.kvinv[rr] * e - jki_r * jt.kvinv[rr] * ie;
 			vdes = fmin(fmax(vdes, -jt.sat[rr]), jt.sat[rr]);
 			fi_pre = -jkv_r * (dq_r - vdes);
@@ -505,7 +514,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 	STAMP(6);
 	// ---- SingularityHandler branch predicate on G = J J^T (N_prec = I for the first task), every lane of the instance alike
 	bool singular = false, truncated = false, blended_i = false;
-	const bool strategies_on = GJ == 0 && mf.sing_handling && mf.sing_strategies && mf.sh != nullptr;  // batch-uniform; the blended branch lives in the headline stack's tail
+	const bool strategies_on = GJ == 0 && (LW ? P.lw.strategies_on : (mf.sing_handling && mf.sing_strategies && mf.sh != nullptr));  // batch-uniform; the blended branch lives in the headline stack's tail
 	double G[6][6], U6[6][6];
 	bool keepm[6] = {true, true, true, true, true, true};
 	double LG[6][6], dG[6];  // closed form: the Cholesky factor of G itself (the certificates below factor shifted copies)
@@ -581,8 +590,11 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 		// full 6-dof task without force space: the task projections and sigma_position / sigma_orientation are identities (oct_eligible)
 		double e3[3];
 		UNR for (int i = 0; i < 3; i++) e3[i] = pw[i] - G24[i];
-		UNR for (int i = 0; i < 3; i++) ip[i] = fma(e3[i], mf.dt, ip[i]);
-		UNR for (int i = 0; i < 3; i++) Fum[i] = G24[18 + i] - mf.kp_pos[i] * e3[i] - mf.kv_pos[i] * (vw[i] - G24[12 + i]) - mf.ki_pos[i] * ip[i];
+		const double ldt = LW ? P.lw.dt : mf.dt;
+		UNR for (int i = 0; i < 3; i++) ip[i] = fma(e3[i], ldt, ip[i]);
+		// kp_pos, kv_pos, ki_pos, kp_ori, kv_ori, ki_ori: launch words, or the run of the task block (asserted contiguous above)
+		const double* gn = LW ? P.lw.gain : reinterpret_cast<const double*>(reinterpret_cast<const char*>(&mf) + offsetof(TaskDev, kp_pos));
+		UNR for (int i = 0; i < 3; i++) Fum[i] = G24[18 + i] - gn[i] * e3[i] - gn[3 + i] * (vw[i] - G24[12 + i]) - gn[6 + i] * ip[i];
 		double oe[3] = {0, 0, 0};  // orientationError(desired, current) = -1/2 sum_c Rc[:,c] x Rd[:,c]
 		UNR for (int c = 0; c < 3; c++) {
 			const double a0 = Rc[c], a1 = Rc[3 + c], a2 = Rc[6 + c], b0 = G24[3 + c], b1 = G24[6 + c], b2 = G24[9 + c];
@@ -590,8 +602,8 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			oe[1] -= 0.5 * (a2 * b0 - a0 * b2);
 			oe[2] -= 0.5 * (a0 * b1 - a1 * b0);
 		}
-		UNR for (int i = 0; i < 3; i++) io[i] = fma(oe[i], mf.dt, io[i]);
-		UNR for (int i = 0; i < 3; i++) Fum[3 + i] = G24[21 + i] - mf.kp_ori[i] * oe[i] - mf.kv_ori[i] * (vw[3 + i] - G24[15 + i]) - mf.ki_ori[i] * io[i];
+		UNR for (int i = 0; i < 3; i++) io[i] = fma(oe[i], ldt, io[i]);
+		UNR for (int i = 0; i < 3; i++) Fum[3 + i] = G24[21 + i] - gn[9 + i] * oe[i] - gn[12 + i] * (vw[3 + i] - G24[15 + i]) - gn[15 + i] * io[i];
 		}
 		if (track_mf && r == 0) {  // left in LDS: committed in the epilogue once the final status is known (the joint task may still flag the instance)
 			UNR for (int i = 0; i < 3; i++) {
@@ -658,7 +670,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			if (ROLE == 0) asm volatile("" : "+v"(zzcf));
 		}
 		const double itr = oct_rcp(tr);
-		const double smax2 = mf.s_max * mf.s_max, tol2 = mf.s_abs_tol * mf.s_abs_tol;
+		const double smax2 = LW ? P.lw.s_max * P.lw.s_max : mf.s_max * mf.s_max, tol2 = LW ? P.lw.s_abs_tol * P.lw.s_abs_tol : mf.s_abs_tol * mf.s_abs_tol;
 		auto ldl_positive = [&](const double shift) {
 			double Gs[6][6];
 			UNR for (int a = 0; a < 6; a++)
@@ -702,7 +714,7 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 			UNR for (int a = 0; a < 6; a++)
 				UNR for (int c = 0; c < 6; c++) t8 = fma(G2[a][c], G2[a][c], t8);
 			const double u = sqrt(sqrt(sqrt(t8)));
-			const bool ok_s0 = (u * mf.cert_kroot * tr >= tol2);
+			const bool ok_s0 = (u * (LW ? P.lw.cert_kroot : mf.cert_kroot) * tr >= tol2);
 			const bool pos = ldl_positive(smax2 * u);
 			need_exact = need_exact && !(ok_s0 && pos && tr > 0.0);
 			if (need_exact) {
@@ -1296,12 +1308,12 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 				{
 					double T0[12], Rb[12];
 					oct_fk_frame(md, rr, r, q_r, T0);
-					const int srcb = octl_src(lane, mf.body);
+					const int srcb = octl_src(lane, LW ? P.lw.body : mf.body);
 					UNR for (int e2 = 0; e2 < 12; e2++) Rb[e2] = __shfl(T0[e2], srcb);
-					oct_mat3_vec(Rb, mf.pos, pw0);
+					oct_mat3_vec(Rb, (LW ? P.lw.pos : mf.pos), pw0);
 					UNR for (int i = 0; i < 3; i++) pw0[i] += Rb[9 + i];
 					UNR for (int i = 0; i < 3; i++)
-						UNR for (int j = 0; j < 3; j++) Rc0[3 * i + j] = Rb[3 * i] * mf.rot[j] + Rb[3 * i + 1] * mf.rot[3 + j] + Rb[3 * i + 2] * mf.rot[6 + j];
+						UNR for (int j = 0; j < 3; j++) Rc0[3 * i + j] = Rb[3 * i] * (LW ? P.lw.rot : mf.rot)[j] + Rb[3 * i + 1] * (LW ? P.lw.rot : mf.rot)[3 + j] + Rb[3 * i + 2] * (LW ? P.lw.rot : mf.rot)[6 + j];
 				}
 				STAMP(20);
 				// one pass per singular direction an instance has (its k-th one, whichever eigen-index that is: usually a single pass), not one
@@ -1323,12 +1335,12 @@ __device__ __forceinline__ bool oct_cycle_body(const CycleParams& P, OctInst* sm
 					for (int sg = 0; sg < 2; sg++) {
 						double T1w[12], Rb[12], x1[3], R1[9];
 						oct_fk_frame(md, rr, r, q_r + (sg ? -5.0 : 5.0) * vc, T1w);
-						const int srcb = octl_src(lane, mf.body);
+						const int srcb = octl_src(lane, LW ? P.lw.body : mf.body);
 						UNR for (int e2 = 0; e2 < 12; e2++) Rb[e2] = __shfl(T1w[e2], srcb);
-						oct_mat3_vec(Rb, mf.pos, x1);
+						oct_mat3_vec(Rb, (LW ? P.lw.pos : mf.pos), x1);
 						UNR for (int i = 0; i < 3; i++) x1[i] += Rb[9 + i];
 						UNR for (int i = 0; i < 3; i++)
-							UNR for (int j = 0; j < 3; j++) R1[3 * i + j] = Rb[3 * i] * mf.rot[j] + Rb[3 * i + 1] * mf.rot[3 + j] + Rb[3 * i + 2] * mf.rot[6 + j];
+							UNR for (int j = 0; j < 3; j++) R1[3 * i + j] = Rb[3 * i] * (LW ? P.lw.rot : mf.rot)[j] + Rb[3 * i + 1] * (LW ? P.lw.rot : mf.rot)[3 + j] + Rb[3 * i + 2] * (LW ? P.lw.rot : mf.rot)[6 + j];
 						double w6[6] = {x1[0] - pw0[0], x1[1] - pw0[1], x1[2] - pw0[2], 0.0, 0.0, 0.0};
 						UNR for (int col = 0; col < 3; col++) {  // orientationError(R1, Rc)
 							const double a0 = Rc0[col], a1 = Rc0[3 + col], a2 = Rc0[6 + col], b0 = R1[col], b1 = R1[3 + col], b2 = R1[6 + col];

@@ -84,6 +84,10 @@ __device__ __forceinline__ bool jf_body(const CycleParams& P, JfInst* smem, doub
 	const ModelDev& md = *P.model;
 	const TaskDev& jt = P.tasks[0];
 	const TaskDev& mf = P.tasks[1];
+	// launch words (CycleParams::lw) in the two-wavefront form; the one-wavefront form measured slower with them and reads the blocks
+	constexpr bool LW = ROLE != 0;
+	const double* const cpos = LW ? P.lw.pos : mf.pos;
+	const double* const crot = LW ? P.lw.rot : mf.rot;
 	const int m = jt.m;  // <= 4
 	int idx[4] = {0, 0, 0, 0};  // the joint each task row selects (batch-uniform: scalar loads)
 	for (int a = 0; a < 4; a++)
@@ -134,7 +138,7 @@ __device__ __forceinline__ bool jf_body(const CycleParams& P, JfInst* smem, doub
 		if (jtype_r == 1) {
 			double s, c;
 			sincos_joint(q_r, &s, &c);
-			if (md.all_axis_z) {  // (batch-uniform) rotation about the local z axis: R0 Rz(q) mixes the first two columns of R0 only
+			if (LW ? P.lw.all_axis_z : md.all_axis_z) {  // (batch-uniform) rotation about the local z axis: R0 Rz(q) mixes the first two columns of R0 only
 				UNR for (int i = 0; i < 3; i++) {
 					Tw[3 * i] = R0[3 * i] * c + R0[3 * i + 1] * s;
 					Tw[3 * i + 1] = R0[3 * i + 1] * c - R0[3 * i] * s;
@@ -242,13 +246,13 @@ __device__ __forceinline__ bool jf_body(const CycleParams& P, JfInst* smem, doub
 	// ---------------------------------------------------------------- MotionForceTask: this joint's column of the world Jacobian, control point, control frame
 	double pw[3], Rc[9], jw[6];
 	{
-		const int bd = mf.body;
+		const int bd = LW ? P.lw.body : mf.body;
 		double Rb[12];
 		UNR for (int e = 0; e < 12; e++) Rb[e] = Xf[bd][e];
-		oct_mat3_vec(Rb, mf.pos, pw);
+		oct_mat3_vec(Rb, cpos, pw);
 		UNR for (int e = 0; e < 3; e++) pw[e] += Rb[9 + e];
 		UNR for (int i = 0; i < 3; i++)
-			UNR for (int j = 0; j < 3; j++) Rc[3 * i + j] = Rb[3 * i] * mf.rot[j] + Rb[3 * i + 1] * mf.rot[3 + j] + Rb[3 * i + 2] * mf.rot[6 + j];
+			UNR for (int j = 0; j < 3; j++) Rc[3 * i + j] = Rb[3 * i] * crot[j] + Rb[3 * i + 1] * crot[3 + j] + Rb[3 * i + 2] * crot[6 + j];
 		const bool on = act && rr <= bd;
 		const double rx = pw[0] - o[0], ry = pw[1] - o[1], rz = pw[2] - o[2];
 		const double c0 = z[1] * rz - z[2] * ry, c1 = z[2] * rx - z[0] * rz, c2 = z[0] * ry - z[1] * rx;
@@ -429,7 +433,8 @@ __device__ __forceinline__ bool jf_body(const CycleParams& P, JfInst* smem, doub
 				if (a == c) tr += s;
 			}
 		const double itr = oct_rcp(tr);
-		const double smax2 = mf.s_max * mf.s_max, tol2 = mf.s_abs_tol * mf.s_abs_tol;
+		const double smx = LW ? P.lw.s_max : mf.s_max, stol = LW ? P.lw.s_abs_tol : mf.s_abs_tol;
+		const double smax2 = smx * smx, tol2 = stol * stol;
 		auto ldl_positive = [&](const double shift) {
 			double Gs[6][6];
 			UNR for (int a = 0; a < 6; a++)
@@ -475,7 +480,7 @@ __device__ __forceinline__ bool jf_body(const CycleParams& P, JfInst* smem, doub
 			UNR for (int a = 0; a < 6; a++)
 				UNR for (int c = 0; c < 6; c++) t8 = fma(G2[a][c], G2[a][c], t8);
 			const double u = sqrt(sqrt(sqrt(t8)));
-			const bool ok_s0 = (u * mf.cert_kroot * tr >= tol2);
+			const bool ok_s0 = (u * (LW ? P.lw.cert_kroot : mf.cert_kroot) * tr >= tol2);
 			const bool pos = ldl_positive(smax2 * u);
 			need_exact = need_exact && !(ok_s0 && pos && tr > 0.0);
 			if (need_exact) {
