@@ -599,6 +599,62 @@ saip_status saip_batch_inertia_randomize(saip_batch*, unsigned long long seed, l
                                          const double* payload_lo, const double* payload_hi);
 saip_status saip_batch_inertia_rows_host(saip_batch*, double* out /* [dof][10] or [dof][10][B] */);  /* synchronous */
 double* saip_batch_inertia_rows_device(saip_batch*);     /* NULL when detached */
+/* ---- sensing model: what stands between the simulated robot and what the controller reads of it -- a constant offset, Gaussian noise and
+ * quantisation on every joint position and velocity and on the sensed wrench of up to SAIP_SENSE_MAX_WRENCH_TASKS motion-force tasks.  One
+ * attachment per batch.  Nothing in it is state: it is configuration plus a host-side period counter, not part of a state snapshot.
+ *   measured  m = x + off;  if (sigma > 0) m = m + sigma z;  if (res > 0) m = res rint(m / res)   (round half to even)
+ *             every product and sum rounded once, in the order written (csrc/saip_sense.h; tests/sensing_ref.py restates it in NumPy).  A
+ *             non-finite x goes through the same arithmetic: a NaN state stays NaN and the cycle flags the instance as it does unattached.
+ *   joints    SAIP_SENSE_JOINT_WORDS doubles per joint { q_off, q_res, q_sigma, dq_off, dq_res, dq_sigma }: `joint_table` is [dof][6]
+ *             (batch-uniform) or [dof][6][B] (per_instance_joints); NULL: neutral rows, all zeros
+ *   wrenches  n_wrench_tasks (0..2) motion-force tasks `tasks`, each with SAIP_SENSE_WRENCH_WORDS doubles: 6 axes (F then M, the frame the
+ *             simulated sensor writes in) x { off, res, sigma }; `wrench_tables` is [S][6][3] or [S][6][3][B] (per_instance_wrenches).  They
+ *             act on goal rows 30..35 of the task, directly behind every launch of a simulated sensor that writes them (contact planes,
+ *             contact patches; in a rollout period and in the standalone _sense entries).  The sensor rewrites the rows it perturbs, so a
+ *             repeated _sense does not stack the perturbation; a table for a task whose sensor is never simulated is inert.
+ *   noise     z: the standard normals of Philox4x32-10 (the rollout sampler's generator) at counter (instance, row, table << 16, period)
+ *             under `seed`: table 6, row j gives (z of q_j, z of dq_j); table 7, row 3 slot + a / 2 gives the z of wrench axes a (even) and
+ *             a + 1 of the task in slot `slot`.  period: the counter of _info, advanced by every rollout period and every
+ *             saip_batch_integrate, set by _set_period (pair it with saip_batch_restore_state: it is not part of a snapshot).
+ *   while attached, every non-diagnostic cycle launch (the whole-controller cycle, its slow-path launches, the per-task entries,
+ *             re-initialisation, the pose and task-diagnostics queries) and the internal OTGs read q_meas, dq_meas in place of the resident
+ *             state; diagnostic launches, the recorder, the model queries, contact, clearance, plant and the integrator keep reading the true
+ *             state.  The measurement is taken in front of the first such launch after the state, the tables, the seed or the period
+ *             changed: once per rollout period (there in one launch with the wrench part), and two cycles at one state see one
+ *             measurement.  A rollout uses neither fused form.  The true state is never written.
+ *   saip_batch_sensing_randomize fills the per-instance tables on the device: word w (6 j + k of a joint, 18 s + 3 a + e of a wrench) of
+ *             instance i is lo[w] + u (hi[w] - lo[w]) clamped to the interval, u the first uniform of Philox4x32-10 at counter (i, w,
+ *             table, round) (table 4 joints, 5 wrenches); lo == hi gives lo exactly.
+ *   _measure  enqueues the measurement of q, dq now: for host-driven loops and after writes through the _device pointers, which are
+ *             neither checked nor noticed.  _measured_host: the measured copy, [dof][B] each (either may be NULL), synchronous.
+ * Errors: ORDER before saip_batch_finalize, on a model-only batch, on a second attach and from every other entry without an attachment;
+ * INVALID_ARGUMENT for a NaN or non-finite word, a negative res or sigma (the message names the joint or the task and axis, the word and,
+ * for per-instance tables, the instance), a task that is not a motion-force task or is named twice, a period outside 0 .. 2^32 - 1.
+ * Argument and order errors are reported before the device is needed; nothing is written on a refusal. */
+#define SAIP_SENSE_JOINT_WORDS 6
+#define SAIP_SENSE_AXIS_WORDS 3
+#define SAIP_SENSE_WRENCH_WORDS 18
+#define SAIP_SENSE_MAX_WRENCH_TASKS 2
+#define SAIP_SENSE_TABLE_JOINTS 4
+#define SAIP_SENSE_TABLE_WRENCHES 5
+#define SAIP_SENSE_TABLE_JOINT_NOISE 6
+#define SAIP_SENSE_TABLE_WRENCH_NOISE 7
+saip_status saip_batch_sensing_attach(saip_batch*, const double* joint_table /* NULL = neutral */, int per_instance_joints, int n_wrench_tasks,
+                                      const int* tasks, const double* wrench_tables, int per_instance_wrenches, unsigned long long seed);
+saip_status saip_batch_sensing_detach(saip_batch*);
+saip_status saip_batch_sensing_info(saip_batch*, int* per_instance_joints, int* n_wrench_tasks, int* per_instance_wrenches, long long* period);  /* any NULL */
+saip_status saip_batch_sensing_set_joints_host(saip_batch*, const double* joint_table);
+saip_status saip_batch_sensing_set_wrenches_host(saip_batch*, const double* wrench_tables);
+saip_status saip_batch_sensing_seed(saip_batch*, unsigned long long seed);
+saip_status saip_batch_sensing_set_period(saip_batch*, long long period);  /* 0 <= period < 2^32 */
+saip_status saip_batch_sensing_randomize(saip_batch*, unsigned long long seed, long long round, const double* joint_lo, const double* joint_hi,
+                                         const double* wrench_lo, const double* wrench_hi);  /* per-instance tables only */
+saip_status saip_batch_sensing_measure(saip_batch*);
+saip_status saip_batch_sensing_measured_host(saip_batch*, double* q /* [dof][B] */, double* dq);  /* synchronous */
+double* saip_batch_sensing_joints_device(saip_batch*);       /* NULL when detached */
+double* saip_batch_sensing_wrenches_device(saip_batch*);     /* NULL when detached or without wrench tasks */
+double* saip_batch_sensing_measured_q_device(saip_batch*);   /* [dof][ld]; NULL when detached */
+double* saip_batch_sensing_measured_dq_device(saip_batch*);  /* [dof][ld]; NULL when detached */
 /* ---- rollout recorder: a per-period trajectory log and running summaries of saip_batch_rollout_async, kept on the device (the
  * reference's example loops print or log the same quantities every period: state, torques, position / orientation error).  A recorder
  * is attached to a finalized batch and stays attached across rollout calls until detached.  It observes rollout periods only

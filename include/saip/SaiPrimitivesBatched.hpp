@@ -1345,6 +1345,81 @@ public:
 	double* plantTorquesDevice() { return saip_batch_plant_torques_device(_batch); }    // [dof][ld] actuated torques of the last substep
 	double* plantSummaryDevice() { return saip_batch_plant_summary_device(_batch); }    // [4][ld]
 
+	// ---- sensing model: offset, noise and quantisation between the resident simulator and what the controller reads of it (saip.h).
+	// While attached, every control cycle, per-task entry and internal OTG reads the measured q, dq; the simulator, the recorder and the
+	// model queries keep the true state.  The period counter of the noise advances once per integrate() and once per rollout period.
+	struct SensingWrench {
+		int task;                      // id of a motion-force task
+		std::vector<double> table;     // [6][3] rows { off, res, sigma } per axis, F then M; [6][3][B] with per_instance
+	};
+	struct SensingInfo {
+		int per_instance_joints = 0, n_wrench_tasks = 0, per_instance_wrenches = 0;
+		long long period = 0;          // the period the next measurement belongs to
+	};
+	// joints: [dof][6] rows { q_off, q_res, q_sigma, dq_off, dq_res, dq_sigma }, or [dof][6][B] with per_instance; empty: neutral (zeros).
+	// wrenches: up to SAIP_SENSE_MAX_WRENCH_TASKS
+	void attachSensing(const std::vector<double>& joints = {}, const std::vector<SensingWrench>& wrenches = {}, bool per_instance = false,
+					   unsigned long long seed = 0) {
+		const size_t cols = per_instance ? (size_t)_robot->batchSize() : 1;
+		if (!joints.empty() && joints.size() != (size_t)_robot->dof() * SAIP_SENSE_JOINT_WORDS * cols)
+			throw std::invalid_argument("attachSensing: expected [dof][6] joints, or [dof][6][B] per instance");
+		std::vector<int> tasks;
+		std::vector<double> table(wrenches.size() * SAIP_SENSE_WRENCH_WORDS * cols);
+		for (size_t k = 0; k < wrenches.size(); k++) {
+			const SensingWrench& w = wrenches[k];
+			if (w.table.size() != SAIP_SENSE_WRENCH_WORDS * cols) throw std::invalid_argument("attachSensing: expected [6][3] words per wrench, or [6][3][B] per instance");
+			tasks.push_back(w.task);
+			std::copy(w.table.begin(), w.table.end(), table.begin() + k * SAIP_SENSE_WRENCH_WORDS * cols);
+		}
+		check(saip_batch_sensing_attach(_batch, joints.empty() ? nullptr : joints.data(), per_instance ? 1 : 0, (int)wrenches.size(), tasks.data(), table.data(),
+										per_instance ? 1 : 0, seed));
+	}
+	void detachSensing() { check(saip_batch_sensing_detach(_batch)); }
+	SensingInfo sensingInfo() {
+		SensingInfo i;
+		check(saip_batch_sensing_info(_batch, &i.per_instance_joints, &i.n_wrench_tasks, &i.per_instance_wrenches, &i.period));
+		return i;
+	}
+	void setSensingJoints(const std::vector<double>& joints) {
+		const SensingInfo i = sensingInfo();
+		if (joints.size() != (size_t)_robot->dof() * SAIP_SENSE_JOINT_WORDS * (i.per_instance_joints ? (size_t)_robot->batchSize() : 1))
+			throw std::invalid_argument("setSensingJoints: the shape of the attached joint table expected");
+		check(saip_batch_sensing_set_joints_host(_batch, joints.data()));
+	}
+	void setSensingWrenches(const std::vector<double>& tables) {
+		const SensingInfo i = sensingInfo();
+		if (tables.size() != (size_t)i.n_wrench_tasks * SAIP_SENSE_WRENCH_WORDS * (i.per_instance_wrenches ? (size_t)_robot->batchSize() : 1))
+			throw std::invalid_argument("setSensingWrenches: the shape of the attached wrench tables expected");
+		check(saip_batch_sensing_set_wrenches_host(_batch, tables.data()));
+	}
+	void setSensingSeed(unsigned long long seed) { check(saip_batch_sensing_seed(_batch, seed)); }
+	// 0 <= period < 2^32; pair it with restoreState: the counter is not part of a snapshot
+	void setSensingPeriod(long long period) { check(saip_batch_sensing_set_period(_batch, period)); }
+	// per-instance tables drawn on the device, uniform between two batch-uniform tables ([dof][6], [S][6][3]); an empty pair leaves that table alone
+	void sensingRandomize(unsigned long long seed, long long round, const std::vector<double>& joint_lo, const std::vector<double>& joint_hi,
+						  const std::vector<double>& wrench_lo = {}, const std::vector<double>& wrench_hi = {}) {
+		const SensingInfo i = sensingInfo();
+		const size_t jw = (size_t)_robot->dof() * SAIP_SENSE_JOINT_WORDS, ww = (size_t)i.n_wrench_tasks * SAIP_SENSE_WRENCH_WORDS;
+		if ((!joint_lo.empty() || !joint_hi.empty()) && (joint_lo.size() != jw || joint_hi.size() != jw))
+			throw std::invalid_argument("sensingRandomize: expected [dof][6] joint bounds");
+		if ((!wrench_lo.empty() || !wrench_hi.empty()) && (wrench_lo.size() != ww || wrench_hi.size() != ww))
+			throw std::invalid_argument("sensingRandomize: expected [S][6][3] wrench bounds");
+		check(saip_batch_sensing_randomize(_batch, seed, round, joint_lo.empty() ? nullptr : joint_lo.data(), joint_hi.empty() ? nullptr : joint_hi.data(),
+										   wrench_lo.empty() ? nullptr : wrench_lo.data(), wrench_hi.empty() ? nullptr : wrench_hi.data()));
+	}
+	// enqueue the measurement of the resident q, dq now (a host-driven loop's first step; needed after writes through device pointers)
+	void measureState() { check(saip_batch_sensing_measure(_batch)); }
+	// q_meas and dq_meas, [dof][B] each: what the controller last read; waits for the stream
+	void measuredState(std::vector<double>& q, std::vector<double>& dq) {
+		q.resize((size_t)_robot->dof() * _robot->batchSize());
+		dq.resize(q.size());
+		check(saip_batch_sensing_measured_host(_batch, q.data(), dq.data()));
+	}
+	double* sensingJointsDevice() { return saip_batch_sensing_joints_device(_batch); }      // [dof][6] or [dof][6][ld]
+	double* sensingWrenchesDevice() { return saip_batch_sensing_wrenches_device(_batch); }  // [S][6][3] or [S][6][3][ld]; nullptr without wrench tasks
+	double* measuredQDevice() { return saip_batch_sensing_measured_q_device(_batch); }      // [dof][ld]
+	double* measuredDqDevice() { return saip_batch_sensing_measured_dq_device(_batch); }    // [dof][ld]
+
 	// ---- plant inertia: the masses, centres of mass and inertias the resident integrator reads in place of the model's (saip.h).  While
 	// attached, integrate() and rolloutAsync() integrate with the table; everything the controller computes keeps the model.
 	struct InertiaInfo {

@@ -1857,6 +1857,126 @@ class RobotController:
         """device pointer of the (4, ld) running summaries; None when detached"""
         return capi.lib().saip_batch_plant_summary_device(self._h)
 
+    # -- sensing model: offset, noise and quantisation between the resident state and what the controller reads of it (saip.h)
+    SENSE_JOINT_WORDS = ("q_off", "q_res", "q_sigma", "dq_off", "dq_res", "dq_sigma")
+    SENSE_AXIS_WORDS = ("off", "res", "sigma")
+
+    def _sense_rows(self, table, names, per_instance, rows, who, what):
+        """(rows, words) or (rows, B, words) from an array of that shape or from a dict { word: scalar, (rows,) or (rows, B) }"""
+        B = self.batch_size
+        if isinstance(table, dict):
+            unknown = set(table) - set(names)
+            if unknown:
+                raise ValueError(f"{who}: unknown {what} words {sorted(unknown)} (known: {list(names)})")
+            a = np.zeros((rows, B, len(names)) if per_instance else (rows, len(names)))
+            for k, name in enumerate(names):
+                if name in table:
+                    v = np.asarray(table[name], float)
+                    if v.ndim == 2 and not per_instance:
+                        raise ValueError(f"{who}: {what} word {name}: per-instance values need per_instance=True")
+                    try:
+                        a[..., k] = v[:, None] if v.ndim == 1 and per_instance else v
+                    except ValueError:
+                        raise ValueError(f"{who}: {what} word {name}: a scalar, ({rows},) or ({rows}, {B}) expected, got {v.shape}") from None
+            table = a
+        return self._plant_table(table, per_instance, B, rows, len(names), who, what)
+
+    def _sense_wrenches(self, wrenches, per_instance, who):
+        """(task ids, the stacked tables laid out for the C entry or None)"""
+        wrenches = {} if wrenches is None else dict(wrenches)
+        ids, tabs = [], []
+        for task, t in wrenches.items():
+            ids.append(int(task._id if hasattr(task, "_id") else task))
+            tabs.append(self._sense_rows(t, self.SENSE_AXIS_WORDS, per_instance, 6, who, "wrench table"))  # (6, 3) or (6, 3, B)
+        return np.asarray(ids + [0] * (1 - min(len(ids), 1)), np.int32), len(ids), (np.ascontiguousarray(np.stack(tabs)) if tabs else None)
+
+    def attachSensing(self, joints=None, wrenches=None, per_instance=False, seed=0):
+        """put a sensing model between the resident simulator and the controller.  joints: (dof, 6) rows { q_off, q_res, q_sigma, dq_off,
+        dq_res, dq_sigma } (or (dof, B, 6) with per_instance), or a dict { word: scalar or (dof,) or (dof, B) }; None: neutral (zeros).
+        wrenches: { motion-force task (or its id): (6, 3) rows { off, res, sigma } per axis F then M } (or (6, B, 3), or the same kind of
+        dict), at most two tasks: they perturb the sensed wrench a simulated sensor writes (contact planes, contact patches).  A measured
+        value is x + off, plus sigma z when sigma > 0, rounded to a multiple of res when res > 0; z is a function of (seed, instance,
+        row, period), the period counter of sensingInfo() advanced by integrate() and every rollout period.  While attached, every control
+        cycle, per-task entry and internal OTG reads the measured q, dq; the simulator, the recorder and the model queries keep the true state."""
+        who = "attachSensing"
+        jt = None if joints is None else self._sense_rows(joints, self.SENSE_JOINT_WORDS, per_instance, self._robot.dof(), who, "joints")
+        ids, S, wt = self._sense_wrenches(wrenches, per_instance, who)
+        self._call("saip_batch_sensing_attach", None if jt is None else _dptr(jt), int(bool(per_instance)), S, ids.ctypes.data_as(C.POINTER(C.c_int)),
+                   None if wt is None else _dptr(wt), int(bool(per_instance)), int(seed) & (2**64 - 1))
+
+    def sensingInfo(self):
+        """dict per_instance_joints, n_wrench_tasks, per_instance_wrenches, period (the period the next measurement belongs to)"""
+        v = [C.c_int(0) for _ in range(3)]
+        per = C.c_longlong(0)
+        self._call("saip_batch_sensing_info", C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(per))
+        return dict(per_instance_joints=bool(v[0].value), n_wrench_tasks=v[1].value, per_instance_wrenches=bool(v[2].value), period=per.value)
+
+    def detachSensing(self):
+        self._call("saip_batch_sensing_detach")
+
+    def setSensingJoints(self, joints):
+        """replace the joint table (same layout as attached); the next cycle takes a new measurement"""
+        info = self.sensingInfo()
+        a = self._sense_rows(joints, self.SENSE_JOINT_WORDS, info["per_instance_joints"], self._robot.dof(), "setSensingJoints", "joints")
+        self._call("saip_batch_sensing_set_joints_host", _dptr(a))
+
+    def setSensingWrenches(self, tables):
+        """replace the wrench tables: a list of (6, 3) (or (6, B, 3)) tables in the order the tasks were attached in"""
+        info = self.sensingInfo()
+        tabs = [self._sense_rows(t, self.SENSE_AXIS_WORDS, info["per_instance_wrenches"], 6, "setSensingWrenches", "wrench table") for t in tables]
+        if len(tabs) != info["n_wrench_tasks"]:
+            raise ValueError(f"setSensingWrenches: {info['n_wrench_tasks']} tables expected, got {len(tabs)}")
+        a = np.ascontiguousarray(np.stack(tabs)) if tabs else None
+        self._call("saip_batch_sensing_set_wrenches_host", None if a is None else _dptr(a))
+
+    def setSensingSeed(self, seed):
+        self._call("saip_batch_sensing_seed", int(seed) & (2**64 - 1))
+
+    def setSensingPeriod(self, period):
+        """the noise's period counter, 0 <= period < 2^32; pair it with restoreState, since the counter is not part of a snapshot"""
+        self._call("saip_batch_sensing_set_period", int(period))
+
+    def sensingRandomize(self, seed, round=0, joints=None, wrenches=None):
+        """draw the per-instance tables on the device: joints = (lo, hi), two (dof, 6) tables, wrenches = (lo, hi), two (S, 6, 3) tables;
+        every word of every instance is uniform between its bounds (lo == hi: exactly lo), reproducibly for (seed, round); None leaves
+        that table alone.  Tables attached without per_instance are refused."""
+        info = self.sensingInfo()
+        jl = jh = wl = wh = None
+        if joints is not None:
+            jl, jh = (self._plant_table(x, False, 0, self._robot.dof(), capi.SAIP_SENSE_JOINT_WORDS, "sensingRandomize", "joint bounds") for x in joints)
+        if wrenches is not None:
+            S = info["n_wrench_tasks"]
+            wl, wh = (self._plant_table(np.asarray(x, float).reshape(-1, capi.SAIP_SENSE_WRENCH_WORDS), False, 0, S, capi.SAIP_SENSE_WRENCH_WORDS,
+                                        "sensingRandomize", "wrench bounds") for x in wrenches)
+        self._call("saip_batch_sensing_randomize", int(seed) & (2**64 - 1), int(round), *(None if x is None else _dptr(x) for x in (jl, jh, wl, wh)))
+
+    def measureState(self):
+        """enqueue the measurement of the resident q, dq now (a host-driven loop's first step; needed after writes through device pointers)"""
+        self.sensingInfo()  # without an attachment: that error, before the device is needed
+        self._push_state()
+        self._call("saip_batch_sensing_measure")
+
+    def measuredState(self):
+        """(q_meas, dq_meas), each (B, dof): what the controller last read (waits for the engine stream)"""
+        self.sensingInfo()
+        n, B = self._robot.dof(), self.batch_size
+        q, dq = np.empty((n, B)), np.empty((n, B))
+        self._call("saip_batch_sensing_measured_host", _dptr(q), _dptr(dq))
+        return np.ascontiguousarray(q.T), np.ascontiguousarray(dq.T)
+
+    def sensingJointsDevice(self):
+        """device pointer of the resident joint table, (dof, 6) or (dof, 6, ld); None when detached"""
+        return capi.lib().saip_batch_sensing_joints_device(self._h)
+
+    def sensingWrenchesDevice(self):
+        """device pointer of the resident wrench tables, (S, 6, 3) or (S, 6, 3, ld); None when detached or without wrench tasks"""
+        return capi.lib().saip_batch_sensing_wrenches_device(self._h)
+
+    def measuredStateDevice(self):
+        """device pointers (q_meas, dq_meas), each (dof, ld); (None, None) when detached"""
+        L = capi.lib()
+        return L.saip_batch_sensing_measured_q_device(self._h), L.saip_batch_sensing_measured_dq_device(self._h)
+
     # -- plant inertia: the masses, centres of mass and inertias the resident integrator reads in place of the model's (saip.h)
     INERTIA_ROW_WORDS = ("m", "cx", "cy", "cz", "Ixx", "Iyy", "Izz", "Ixy", "Ixz", "Iyz")
 

@@ -135,6 +135,7 @@ extern "C" void saip_batch_destroy(saip_batch* b) {
 		clearance_free(b);
 		plant_free(b);
 		inertia_free(b);
+		sensing_free(b);
 		if (b->stream) (void)hipStreamDestroy(b->stream);
 	}
 	delete b;
@@ -913,6 +914,7 @@ static saip_status run_otg(saip_batch* b, int t, int mode, int mask = 3) {
 	T.otg.goal_comps = T.dev.goal_comps;
 	T.otg.task = b->tasks_dev + t;
 	T.otg.dt = T.dev.dt;
+	T.otg.q = controller_q(b);  // (the measured copy while a sensing model is attached)
 	if (T.otg_limits_dirty) {
 		HIP_TRY(hipMemcpyAsync(T.otg_limits_dev, T.otg_limits, sizeof(T.otg_limits), hipMemcpyHostToDevice, b->stream));
 		HIP_TRY(hipStreamSynchronize(b->stream));  // limits change rarely; keeps the host array free to change again
@@ -986,10 +988,13 @@ static CycleParams::LaunchWords launch_words(const ModelDev& md, const TaskDev* 
 		for (int e = 0; e < 3; e++) w.gain[3 * k + e] = gains[k][e];
 	return w;
 }
-static saip_status make_params(saip_batch* b, CycleParams& P, bool diag) {
+// reads_state: a launch that reads the controller's state follows (with a sensing model attached, the measurement is made current first)
+static saip_status make_params(saip_batch* b, CycleParams& P, bool diag, bool reads_state = true) {
 	{
 		saip_status st = ensure_lazy_state(b);
 		if (st) return st;
+		// (in front of a diagnostic launch too: it reads the true state itself, but may have to initialise an internal OTG first)
+		if (reads_state && (st = sensing_refresh(b))) return st;
 	}
 	if (b->config_dirty || diag) {
 		std::vector<TaskDev> tmp;
@@ -1022,8 +1027,9 @@ static saip_status make_params(saip_batch* b, CycleParams& P, bool diag) {
 	P.jla = b->jla;
 	P.only_flagged = 0;
 	P.diag = diag;
-	P.q = b->q;
-	P.dq = b->dq;
+	// what the controller reads: the measured copy of a sensing model, except in a diagnostic launch, which reports where the robot is
+	P.q = diag ? b->q : controller_q(b);
+	P.dq = diag ? b->dq : controller_dq(b);
 	P.tau = commanded_tau(b);
 	P.status = b->status;
 	if (diag) {
@@ -1096,7 +1102,7 @@ static saip_status make_params(saip_batch* b, CycleParams& P, bool diag) {
 // the task constants on the device made current (uploaded when the configuration changed), for launches that read them without a cycle
 saip_status saip::eng::ensure_task_constants(saip_batch* b) {
 	CycleParams P;
-	return make_params(b, P, false);
+	return make_params(b, P, false, false);
 }
 // the lane-per-instance register kernel covers 6..8 dof, at most two motion-force tasks and one shared BIE threshold
 static bool lane_eligible(const saip_batch* b) {
@@ -1199,6 +1205,7 @@ bool saip::eng::otg_pair_ready(saip_batch* b) {
 		T.otg.goal_comps = T.dev.goal_comps;
 		T.otg.task = b->tasks_dev + t;
 		T.otg.dt = T.dev.dt;
+		T.otg.q = controller_q(b);
 	}
 	return true;
 }

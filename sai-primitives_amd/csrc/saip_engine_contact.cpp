@@ -152,7 +152,9 @@ extern "C" saip_status saip_batch_contact_sense(saip_batch* b) {
 	if (st) return st;
 	if (!b->contact.sensor) return fail(SAIP_ERR_ORDER, "%s: the contact planes were attached without the simulated sensor", fn);
 	if ((st = need_ready(b, fn))) return st;
-	return contact_launch(b, saip::CONTACT_SENSE, 0.0);
+	if ((st = contact_launch(b, saip::CONTACT_SENSE, 0.0))) return st;
+	// a sensing model perturbs the wrench just written (SENSE rewrites the rows: a second call does not stack the perturbation)
+	return b->sensing.attached ? sensing_launch(b, saip::SENSE_MODE_WRENCH, sensing_sensor_slots(b, true, false)) : SAIP_OK;
 }
 extern "C" saip_status saip_batch_contact_readout_host(saip_batch* b, double* out) {
 	const char* fn = "saip_batch_contact_readout_host";
@@ -324,7 +326,8 @@ extern "C" saip_status saip_batch_contact_patch_sense(saip_batch* b) {
 	if (patch_slot(b, -1, fn, &st) < 0) return st;
 	if (!patch_any_sensor(b)) return fail(SAIP_ERR_ORDER, "%s: no contact patch was attached with the simulated sensor", fn);
 	if ((st = need_ready(b, fn))) return st;
-	return patch_launch(b, saip::CONTACT_SENSE, 0.0);
+	if ((st = patch_launch(b, saip::CONTACT_SENSE, 0.0))) return st;
+	return b->sensing.attached ? sensing_launch(b, saip::SENSE_MODE_WRENCH, sensing_sensor_slots(b, false, true)) : SAIP_OK;
 }
 extern "C" saip_status saip_batch_contact_patch_readout_host(saip_batch* b, int task, double* out) {
 	const char* fn = "saip_batch_contact_patch_readout_host";

@@ -23,6 +23,7 @@
 #include "saip_clearance.h"
 #include "saip_plant.h"
 #include "saip_inertia.h"
+#include "saip_sense.h"
 
 namespace saip {
 hipError_t launch_cycle_wg(const CycleParams& P, bool tree, hipStream_t stream);
@@ -57,6 +58,8 @@ hipError_t launch_clearance_summary_reset(int B, int ld, double* summary, hipStr
 hipError_t launch_plant_apply(const PlantParams& P, bool tree, hipStream_t stream);
 hipError_t launch_plant_randomize(const PlantRandomParams& P, hipStream_t stream);
 hipError_t launch_inertia_compose(const InertiaComposeParams& P, hipStream_t stream);
+hipError_t launch_sense_apply(const SenseParams& P, hipStream_t stream);
+hipError_t launch_sense_randomize(const SenseRandomParams& P, hipStream_t stream);
 }  // namespace saip
 
 using saip::CycleParams;
@@ -240,6 +243,23 @@ struct saip_batch {
 		double* parts = nullptr;             // staging of _set_parts_host: bodies [n][4] or [n][4][ld], then payloads [P][7] or [P][7][ld]
 		double* bounds = nullptr;            // body lo [n][4], body hi, payload lo [P][7], payload hi of _randomize (per-instance tables only)
 	} inertia;
+	// saip_batch_sensing_attach: the sensing model of the resident simulator (saip_sense.hip), at most one per batch: offset, noise and
+	// quantisation on what the controller reads of the state and of the simulated force sensor.  Nothing in it is state: its arrays are
+	// configuration and a measured copy of q, dq, its own (freed by _detach), not part of `allocs` or of a snapshot; `period` is a
+	// host-side counter, `epoch` the state_epoch the measured copy was last taken at (-1: stale whatever the state).
+	struct Sensing {
+		bool attached = false;
+		int per_instance_joints = 0, n_wrench_tasks = 0, per_instance_wrenches = 0;
+		int task[saip::SENSE_MAX_WRENCH_TASKS] = {-1, -1};
+		unsigned long long seed = 0;
+		long long period = 0;                // the period the next measurement belongs to (noise counter)
+		long epoch = -1;
+		double* joints = nullptr;            // [n][6] (batch-uniform) or [n][6][ld]
+		double* wrenches = nullptr;          // [S][6][3] or [S][6][3][ld] (nullptr: no wrench task)
+		double* q_meas = nullptr;            // [n][ld] what every non-diagnostic cycle, per-task and OTG launch reads in place of q
+		double* dq_meas = nullptr;           // [n][ld]
+		double* bounds = nullptr;            // joint lo [n][6], joint hi, wrench lo [S][18], wrench hi of saip_batch_sensing_randomize
+	} sensing;
 };
 
 namespace saip {
@@ -249,6 +269,9 @@ inline constexpr auto& fail = fail_external;
 // ---- saip_engine.cpp
 inline bool has_device(const saip_batch* b) { return b->device >= 0; }
 inline double* commanded_tau(const saip_batch* b) { return b->tau_bound ? b->tau_bound : b->tau; }  // the caller's bound buffer or the batch's own
+// the state the controller reads: the measured copy while a sensing model is attached, else the resident state itself
+inline const double* controller_q(const saip_batch* b) { return b->sensing.attached ? b->sensing.q_meas : b->q; }
+inline const double* controller_dq(const saip_batch* b) { return b->sensing.attached ? b->sensing.dq_meas : b->dq; }
 saip_status check_batch(const saip_batch* b, int task, const char* fn);
 saip_status need_state(saip_batch* b, const char* fn);
 saip_status need_ready(saip_batch* b, const char* fn);
@@ -298,6 +321,11 @@ void plant_free(saip_batch* b);
 saip_status plant_launch(saip_batch* b, double dt);
 // ---- saip_engine_inertia.cpp
 void inertia_free(saip_batch* b);
+// ---- saip_engine_sensing.cpp
+void sensing_free(saip_batch* b);
+int sensing_sensor_slots(const saip_batch* b, bool planes, bool patches);
+saip_status sensing_launch(saip_batch* b, int mode, int slot_mask);
+saip_status sensing_refresh(saip_batch* b);
 // ---- saip_engine_rollout.cpp
 void record_free(saip_batch* b);
 void schedule_release(saip_batch* b, int task);

@@ -38,11 +38,12 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 			if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "integrate launch failed: %s", hipGetErrorString(e));
 		}
 		if (b->plant.attached) b->plant.period++;
+		if (b->sensing.attached) b->sensing.period++;
 		b->models_valid = false;
 		b->state_epoch++;
 		return SAIP_OK;
 	}
-	if (with_next_otg && S.n == 7 && !tree && !b->inertia.attached && otg_pair_ready(b)) {
+	if (with_next_otg && S.n == 7 && !tree && !b->inertia.attached && !b->sensing.attached && otg_pair_ready(b)) {
 		// rollouts: this integration and the NEXT period's trajectory generation in one launch (they are independent)
 		e = saip::launch_integrate_otg_pair(S, b->tasks[0].otg, b->tasks[1].otg, b->B, b->ld, b->stream);
 		b->otg_prelaunched = true;
@@ -50,6 +51,7 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 		e = saip::launch_integrate(S, tree, b->stream);
 	}
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "integrate launch failed: %s", hipGetErrorString(e));
+	if (b->sensing.attached) b->sensing.period++;
 	b->models_valid = false;  // the state moved: like after robot->setQ(), updateControllerTaskModels() is due
 	b->state_epoch++;
 	return SAIP_OK;
@@ -389,13 +391,20 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 	// (contact patches: the same, with their kernel)
 	// a plant model does the same: it sits between the cycle and every integration substep
 	// an inertia table rules out both fused forms as well: they integrate with the model's inertial parameters
-	const bool contact = b->contact.attached || b->n_patch > 0 || b->plant.attached || b->inertia.attached;
+	// a sensing model too: the fused cycle would compute from the measured copy and integrate it, and the next period's OTG step would
+	// run ahead of the measurement it belongs behind
+	const bool contact = b->contact.attached || b->n_patch > 0 || b->plant.attached || b->inertia.attached || b->sensing.attached;
 	const bool patch_sensor = patch_any_sensor(b);
+	const int sense_slots = b->sensing.attached ? sensing_sensor_slots(b, true, true) : 0;
 	auto period = [&](const bool more = false) -> saip_status {  // more: another period follows inside this call
 		if (scheduled && (st = apply_schedules(b))) return st;
 		// contact planes with the simulated sensor: the sensed wrench of this period's state, in front of the OTGs (which pass it on) and the cycle
 		if (b->contact.attached && b->contact.sensor && (st = contact_launch(b, saip::CONTACT_SENSE, 0.0))) return st;
 		if (patch_sensor && (st = patch_launch(b, saip::CONTACT_SENSE, 0.0))) return st;
+		// a sensing model: this period's measurement of q, dq and the perturbation of the wrench just sensed, in one launch
+		if (b->sensing.attached &&
+			(st = sensing_launch(b, (b->sensing.epoch != b->state_epoch ? saip::SENSE_MODE_JOINTS : 0) | saip::SENSE_MODE_WRENCH, sense_slots)))
+			return st;
 		// no internal OTG in the stack: the cycle launch integrates the state itself when it can (eight-lane kernel, no slow path behind)
 		bool integrated = false;
 		saip_status s2 = launch_cycle(b, false, (!any_otg && b->model->n == 7 && !contact) ? &sim : nullptr, &integrated);

@@ -29,7 +29,11 @@
    one-substep integrate calls both ways: the difference is the plant launch alone.
    --inertia [--inertia-payloads P] [--substeps S] times, interleaved in the same run, the closed-loop period without and with a per-instance
    inertia table (link masses within 20 %, centres of mass within 2 cm, P box payloads of up to 3 kg, 0..2, drawn on the device), the
-   event-timed mean of 200 integrate calls both ways and of 50 draws of the whole table."""
+   event-timed mean of 200 integrate calls both ways and of 50 draws of the whole table.
+   --sensing [--sensing-wrench] [--substeps S] times, interleaved in the same run, the closed-loop period without and with a per-instance
+   sensing model (encoder offsets, 14-bit position resolution, position and velocity noise; with --sensing-wrench also contact planes with
+   the simulated sensor, attached throughout, and a biased, quantised, noisy wrench table on their task) and the event-timed mean of 200
+   measurements of q, dq alone."""
 import argparse
 import os
 import sys
@@ -90,6 +94,8 @@ ap.add_argument("--clearance-obstacles", type=int, default=4)
 ap.add_argument("--clearance-pairs", type=int, default=0)
 ap.add_argument("--plant", action="store_true")
 ap.add_argument("--plant-wrenches", type=int, choices=range(5), default=1)
+ap.add_argument("--sensing", action="store_true")
+ap.add_argument("--sensing-wrench", action="store_true")
 ap.add_argument("--inertia", action="store_true")
 ap.add_argument("--inertia-payloads", type=int, choices=range(3), default=1)
 args = ap.parse_args()
@@ -331,6 +337,40 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
                   f"closed-loop period {plain:.1f} us; with a per-instance plant model and {Wn} wrench(es) {with_p:.1f} us; without it again {again:.1f} us; "
                   f"one substep on the stream {plain_s:.2f} us plain, {with_s:.2f} us with the plant: launch alone {with_s - plain_s:.2f} us "
                   f"({clipped} of {B} instances clipped a torque)")
+        continue
+    if args.sensing:
+        rng = np.random.default_rng(0)
+        table = np.zeros((7, B, 6))
+        table[..., 0], table[..., 1], table[..., 2] = rng.uniform(-5e-3, 5e-3, (7, B)), 2 * np.pi / 2 ** 14, 1e-4
+        table[..., 3], table[..., 4], table[..., 5] = rng.uniform(-1e-2, 1e-2, (7, B)), 0.0, 5e-3
+        wrench = None
+        if args.sensing_wrench:   # the sensed wrench needs a simulated sensor: a table 2 mm inside every tool, as --contact has it
+            p = robot.position("end-effector", (0, 0, 0.07))
+            planes = np.zeros((1, B, 8))
+            planes[0] = [0, 0, 1, 0, 2.0e4, 400.0, 0.3, 1e-3]
+            planes[0, :, 3] = p[:, 2] + 2e-3
+            mf.attachContactPlanes(planes, sensor=True, per_instance=True)
+            wrench = {mf: np.tile([0.5, 0.01, 0.2], (6, B, 1))}
+        timed_us, _ = stream_timer(ctrl)
+
+        def period_us():
+            t0 = time.perf_counter()
+            ctrl.rolloutAsync(K, 5e-4, args.substeps, gravity=(0, 0, 0))
+            ctrl.synchronize()
+            return (time.perf_counter() - t0) / K * 1e6
+
+        for _ in range(args.repeats):
+            plain = period_us()
+            ctrl.attachSensing(table, wrenches=wrench, per_instance=True, seed=1)
+            period_us()
+            with_s = period_us()
+            alone = timed_us(ctrl.measureState, 200)
+            noisy = float(np.abs(ctrl.measuredState()[0] - ctrl.pullState()[0]).max())
+            ctrl.detachSensing()
+            again, again2 = period_us(), period_us()
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {args.substeps}: "
+                  f"closed-loop period {plain:.1f} us; with a per-instance sensing model{' and a wrench table' if wrench else ''} {with_s:.1f} us; without it "
+                  f"again {again:.1f} us, and once more {again2:.1f} us; one measurement of q, dq alone {alone:.2f} us (largest |q_meas - q| {noisy:.2e})")
         continue
     if args.inertia:
         Pn = args.inertia_payloads
