@@ -655,6 +655,45 @@ double* saip_batch_sensing_joints_device(saip_batch*);       /* NULL when detach
 double* saip_batch_sensing_wrenches_device(saip_batch*);     /* NULL when detached or without wrench tasks */
 double* saip_batch_sensing_measured_q_device(saip_batch*);   /* [dof][ld]; NULL when detached */
 double* saip_batch_sensing_measured_dq_device(saip_batch*);  /* [dof][ld]; NULL when detached */
+/* ---- sensing chain: the optional second stage of the sensing model, per joint: a delay line of up to SAIP_SENSE_CHAIN_MAX_DEPTH samples, an
+ * optional finite-difference velocity and a first-order low-pass between the measured sample (q_m, dq_m) above and what the controller
+ * reads.  Attached only while a sensing model is attached (an all-zero sensing table is a valid carrier); saip_batch_sensing_detach detaches
+ * the chain first.  It is the one attachment with STATE, and that state is part of a state snapshot.
+ *   table     SAIP_SENSE_CHAIN_WORDS doubles per joint { delay, vel_mode, a_q, a_dq }: [dof][4] (batch-uniform) or [dof][4][B] (per_instance);
+ *             NULL: neutral rows, all zeros (no delay, measured dq, no filter), which return the sensing model's output bit for bit.
+ *             delay is integer-valued in 0..depth, vel_mode 0 (measured dq) or 1 (finite difference), a_q and a_dq in [0, 1] (0: no filter).
+ *             For a cutoff f_c in Hz the facades offer a = 1 - exp(-2 pi f_c sample_time); the kernel never sees a frequency.
+ *   sample    d = (int)delay;  unless primed: every tap = (q_m, dq_m), q_prev = y_q = q_m, y_dq = dq_m, primed = 1
+ *             x = d ? tap_q[d-1] : q_m;  v = d ? tap_dq[d-1] : dq_m;   taps 1..d-1 shift by one, tap 0 takes (q_m, dq_m)
+ *             if (vel_mode == 1) { v = (x - q_prev) / sample_time;  q_prev = x }        (the first sample gives 0)
+ *             y_q = a_q > 0 ? y_q + a_q (x - y_q) : x;   y_dq = a_dq > 0 ? y_dq + a_dq (v - y_dq) : v;   the controller reads (y_q, y_dq)
+ *             every product, sum and quotient rounded once, in the order written (csrc/saip_sense_chain.h; tests/sensing_chain_ref.py).
+ *   every JOINTS launch of the sensing model is one sample: one per state change in front of the first launch that reads the controller's
+ *             state, one per rollout period, and one per saip_batch_sensing_measure (two calls at one state are two samples).  While
+ *             attached, saip_sense_chain_apply is enqueued wherever saip_sense_apply would be; a rollout period keeps one measurement launch.
+ *   state     per (joint, instance): taps [dof][2][depth][ld] (absent at depth 0), filt [dof][3][ld] { q_prev, y_q, y_dq }, primed [dof][ld]
+ *             (int32); zeroed at attach, freed at detach, listed by a snapshot as sense.chain.taps / .filt / .primed while attached.  A
+ *             snapshot of another chain layout (not attached, another depth, another attachment) is refused with ORDER, the segment named.
+ *             A restore does not re-prime: primed travels with the column.  _chain_reset clears primed on the stream.
+ *   _chain_randomize fills the per-instance table: word w = 4 j + k of instance i is lo[w] + u (hi[w] - lo[w]) as in
+ *             saip_batch_sensing_randomize, table id 8; delay and vel_mode are then rounded, floor(x + 0.5), and clamped to their range.
+ *   _chain_state_host: taps [dof][2][depth][B], filt [dof][3][B], primed [dof][B] (any may be NULL), synchronous: for tests and debugging.
+ * Errors: INVALID_ARGUMENT for a depth outside 0..8, a sample time that is not finite and positive, a bad table word (the message names the
+ * joint, the word and, per instance, the instance); ORDER before saip_batch_finalize, on a model-only batch, without a sensing model, on a
+ * second attach and from every other _chain entry without a chain (_chain_info needs the sensing model only).  Argument and order errors
+ * are reported before the device is needed; nothing is written on a refusal. */
+#define SAIP_SENSE_CHAIN_WORDS 4
+#define SAIP_SENSE_CHAIN_MAX_DEPTH 8
+#define SAIP_SENSE_TABLE_CHAIN 8
+saip_status saip_batch_sensing_chain_attach(saip_batch*, const double* table /* NULL = neutral */, int per_instance, int depth, double sample_time);
+saip_status saip_batch_sensing_chain_detach(saip_batch*);
+saip_status saip_batch_sensing_chain_info(saip_batch*, int* attached, int* per_instance, int* depth, double* sample_time, size_t* state_bytes);  /* any NULL */
+saip_status saip_batch_sensing_chain_set_table_host(saip_batch*, const double* table);
+saip_status saip_batch_sensing_chain_randomize(saip_batch*, unsigned long long seed, long long round, const double* lo, const double* hi);  /* per-instance table only */
+saip_status saip_batch_sensing_chain_reset(saip_batch*);
+double* saip_batch_sensing_chain_table_device(saip_batch*);  /* NULL when detached */
+saip_status saip_batch_sensing_chain_state_host(saip_batch*, double* taps, double* filt, int* primed);  /* synchronous */
+saip_status saip_batch_sensing_chain_state_device(saip_batch*, double** taps, double** filt, int** primed);  /* the arrays, [rows][ld]; taps NULL at depth 0 */
 /* ---- rollout recorder: a per-period trajectory log and running summaries of saip_batch_rollout_async, kept on the device (the
  * reference's example loops print or log the same quantities every period: state, torques, position / orientation error).  A recorder
  * is attached to a finalized batch and stays attached across rollout calls until detached.  It observes rollout periods only

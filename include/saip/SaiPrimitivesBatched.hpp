@@ -1420,6 +1420,61 @@ public:
 	double* measuredQDevice() { return saip_batch_sensing_measured_q_device(_batch); }      // [dof][ld]
 	double* measuredDqDevice() { return saip_batch_sensing_measured_dq_device(_batch); }    // [dof][ld]
 
+	// ---- sensing chain: per joint a delay line, an optional finite-difference velocity and a first-order low-pass behind the sensing model
+	// (saip.h).  Needs an attached sensing model (attachSensing() alone is a neutral carrier).  Its state is part of saveState() / restoreState().
+	struct SensingChainInfo {
+		int attached = 0, per_instance = 0, depth = 0;
+		double sample_time = 0;
+		size_t state_bytes = 0;                // device bytes of taps, filt and primed
+	};
+	struct SensingChainState {
+		std::vector<double> taps, filt;        // [dof][2][depth][B], [dof][3][B] { q_prev, y_q, y_dq }
+		std::vector<int> primed;               // [dof][B]
+	};
+	// the low-pass coefficient of a first-order filter with cutoff f_c (Hz) sampled every sample_time seconds: for the a_q / a_dq words
+	static double sensingChainAlpha(double cutoff_hz, double sample_time) { return 1.0 - std::exp(-2.0 * M_PI * cutoff_hz * sample_time); }
+	// table: [dof][4] rows { delay, vel_mode, a_q, a_dq }, or [dof][4][B] with per_instance; empty: neutral.  depth 0..SAIP_SENSE_CHAIN_MAX_DEPTH
+	void attachSensingChain(const std::vector<double>& table, bool per_instance, int depth, double sample_time) {
+		const size_t cols = per_instance ? (size_t)_robot->batchSize() : 1;
+		if (!table.empty() && table.size() != (size_t)_robot->dof() * SAIP_SENSE_CHAIN_WORDS * cols)
+			throw std::invalid_argument("attachSensingChain: expected a [dof][4] table, or [dof][4][B] per instance");
+		check(saip_batch_sensing_chain_attach(_batch, table.empty() ? nullptr : table.data(), per_instance ? 1 : 0, depth, sample_time));
+	}
+	void detachSensingChain() { check(saip_batch_sensing_chain_detach(_batch)); }
+	SensingChainInfo sensingChainInfo() {
+		SensingChainInfo i;
+		check(saip_batch_sensing_chain_info(_batch, &i.attached, &i.per_instance, &i.depth, &i.sample_time, &i.state_bytes));
+		return i;
+	}
+	void setSensingChainTable(const std::vector<double>& table) {
+		const SensingChainInfo i = sensingChainInfo();
+		if (table.size() != (size_t)_robot->dof() * SAIP_SENSE_CHAIN_WORDS * (i.per_instance ? (size_t)_robot->batchSize() : 1))
+			throw std::invalid_argument("setSensingChainTable: the shape of the attached chain table expected");
+		check(saip_batch_sensing_chain_set_table_host(_batch, table.data()));
+	}
+	// the per-instance table drawn on the device between two [dof][4] tables; delay and vel_mode rounded and clamped after the draw
+	void sensingChainRandomize(unsigned long long seed, long long round, const std::vector<double>& lo, const std::vector<double>& hi) {
+		const size_t w = (size_t)_robot->dof() * SAIP_SENSE_CHAIN_WORDS;
+		if (lo.size() != w || hi.size() != w) throw std::invalid_argument("sensingChainRandomize: expected [dof][4] bounds");
+		check(saip_batch_sensing_chain_randomize(_batch, seed, round, lo.data(), hi.data()));
+	}
+	// the next sample primes the chain again (enqueued, no wait)
+	void resetSensingChain() { check(saip_batch_sensing_chain_reset(_batch)); }
+	// for tests and debugging; waits for the stream
+	SensingChainState sensingChainState() {
+		const SensingChainInfo i = sensingChainInfo();
+		const size_t n = _robot->dof(), B = _robot->batchSize();
+		SensingChainState s;
+		s.taps.resize(n * 2 * i.depth * B);
+		s.filt.resize(n * 3 * B);
+		s.primed.resize(n * B);
+		check(saip_batch_sensing_chain_state_host(_batch, s.taps.empty() ? nullptr : s.taps.data(), s.filt.data(), s.primed.data()));
+		return s;
+	}
+	// the state arrays, [rows][ld]: taps [dof][2][depth] rows (nullptr at depth 0), filt [dof][3] rows, primed [dof] rows
+	void sensingChainStateDevice(double** taps, double** filt, int** primed) { check(saip_batch_sensing_chain_state_device(_batch, taps, filt, primed)); }
+	double* sensingChainTableDevice() { return saip_batch_sensing_chain_table_device(_batch); }  // [dof][4] or [dof][4][ld]
+
 	// ---- plant inertia: the masses, centres of mass and inertias the resident integrator reads in place of the model's (saip.h).  While
 	// attached, integrate() and rolloutAsync() integrate with the table; everything the controller computes keeps the model.
 	struct InertiaInfo {

@@ -1977,6 +1977,79 @@ class RobotController:
         L = capi.lib()
         return L.saip_batch_sensing_measured_q_device(self._h), L.saip_batch_sensing_measured_dq_device(self._h)
 
+    # -- sensing chain: delay line, finite-difference velocity and low-pass behind the sensing model's joint rows; its state is snapshot state
+    SENSE_CHAIN_WORDS = ("delay", "vel_mode", "a_q", "a_dq")
+
+    @staticmethod
+    def sensingChainAlpha(cutoff_hz, sample_time):
+        """the low-pass coefficient a = 1 - exp(-2 pi f_c sample_time) of a first-order filter with cutoff f_c (Hz) sampled every
+        sample_time seconds, for the a_q / a_dq words (scalars or arrays)"""
+        return 1.0 - np.exp(-2.0 * np.pi * np.asarray(cutoff_hz, float) * float(sample_time))
+
+    def attachSensingChain(self, table=None, per_instance=False, depth=0, sample_time=1e-3):
+        """put a sensing chain behind the attached sensing model (attachSensing() first; attachSensing() alone is a neutral carrier).
+        table: (dof, 4) rows { delay, vel_mode, a_q, a_dq } (or (dof, B, 4) with per_instance), or a dict { word: scalar or (dof,) or
+        (dof, B) }; None: neutral.  delay: whole samples, 0..depth (depth <= 8); vel_mode 1: dq is the finite difference of the delayed q
+        over sample_time; a_q, a_dq in [0, 1]: y += a (x - y), 0 for no filter (sensingChainAlpha() from a cutoff).  Every measurement the
+        engine takes is one sample: one per state change, one per rollout period, one per measureState().  The chain's state is part of
+        saveState() / restoreState()."""
+        who = "attachSensingChain"
+        t = None if table is None else self._sense_rows(table, self.SENSE_CHAIN_WORDS, per_instance, self._robot.dof(), who, "chain table")
+        self._call("saip_batch_sensing_chain_attach", None if t is None else _dptr(t), int(bool(per_instance)), int(depth), float(sample_time))
+
+    def detachSensingChain(self):
+        self._call("saip_batch_sensing_chain_detach")
+
+    def sensingChainInfo(self):
+        """dict attached, per_instance, depth, sample_time, state_bytes (device bytes of taps, filt and primed); needs a sensing model"""
+        v = [C.c_int(0) for _ in range(3)]
+        T, nb = C.c_double(0), C.c_size_t(0)
+        self._call("saip_batch_sensing_chain_info", C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(T), C.byref(nb))
+        return dict(attached=bool(v[0].value), per_instance=bool(v[1].value), depth=v[2].value, sample_time=T.value, state_bytes=nb.value)
+
+    def _chain_info(self, who):
+        info = self.sensingChainInfo()
+        if not info["attached"]:
+            raise capi.SaipError(f"{who}: no sensing chain is attached (attachSensingChain)")
+        return info
+
+    def setSensingChainTable(self, table):
+        """replace the chain table (same layout as attached); the state stays (resetSensingChain() starts afresh)"""
+        info = self._chain_info("setSensingChainTable")
+        a = self._sense_rows(table, self.SENSE_CHAIN_WORDS, info["per_instance"], self._robot.dof(), "setSensingChainTable", "chain table")
+        self._call("saip_batch_sensing_chain_set_table_host", _dptr(a))
+
+    def sensingChainRandomize(self, seed, round=0, lo=None, hi=None):
+        """draw the per-instance chain table on the device between two (dof, 4) tables; delay and vel_mode are rounded to the nearest
+        integer and clamped to 0..depth and 0..1 after the draw; reproducible for (seed, round)"""
+        self._chain_info("sensingChainRandomize")
+        lo, hi = (self._plant_table(x, False, 0, self._robot.dof(), capi.SAIP_SENSE_CHAIN_WORDS, "sensingChainRandomize", "chain bounds") for x in (lo, hi))
+        self._call("saip_batch_sensing_chain_randomize", int(seed) & (2**64 - 1), int(round), _dptr(lo), _dptr(hi))
+
+    def resetSensingChain(self):
+        """the next sample primes the chain again: every tap, q_prev and both filters start from that sample (enqueued, no wait)"""
+        self._call("saip_batch_sensing_chain_reset")
+
+    def sensingChainState(self):
+        """dict taps (B, dof, 2, depth) { q, dq } x tap, filt (B, dof, 3) { q_prev, y_q, y_dq }, primed (B, dof) int (waits for the engine
+        stream): for tests and debugging"""
+        info = self._chain_info("sensingChainState")
+        n, B, d = self._robot.dof(), self.batch_size, info["depth"]
+        taps, filt, primed = np.zeros((n, 2, d, B)), np.empty((n, 3, B)), np.empty((n, B), np.int32)
+        self._call("saip_batch_sensing_chain_state_host", _dptr(taps) if d else None, _dptr(filt), primed.ctypes.data_as(C.POINTER(C.c_int)))
+        return dict(taps=np.ascontiguousarray(taps.transpose(3, 0, 1, 2)), filt=np.ascontiguousarray(filt.transpose(2, 0, 1)), primed=np.ascontiguousarray(primed.T))
+
+    def sensingChainStateDevice(self):
+        """device pointers (taps, filt, primed) of the state arrays, (2 depth dof, ld), (3 dof, ld) float64 and (dof, ld) int32; taps is
+        None at depth 0"""
+        p = [C.c_void_p() for _ in range(3)]
+        self._call("saip_batch_sensing_chain_state_device", C.byref(p[0]), C.byref(p[1]), C.byref(p[2]))
+        return tuple(x.value for x in p)
+
+    def sensingChainTableDevice(self):
+        """device pointer of the resident chain table, (dof, 4) or (dof, 4, ld); None when detached"""
+        return capi.lib().saip_batch_sensing_chain_table_device(self._h)
+
     # -- plant inertia: the masses, centres of mass and inertias the resident integrator reads in place of the model's (saip.h)
     INERTIA_ROW_WORDS = ("m", "cx", "cy", "cz", "Ixx", "Iyy", "Izz", "Ixy", "Ixz", "Iyz")
 

@@ -24,6 +24,7 @@
 #include "saip_plant.h"
 #include "saip_inertia.h"
 #include "saip_sense.h"
+#include "saip_sense_chain.h"
 
 namespace saip {
 hipError_t launch_cycle_wg(const CycleParams& P, bool tree, hipStream_t stream);
@@ -60,6 +61,8 @@ hipError_t launch_plant_randomize(const PlantRandomParams& P, hipStream_t stream
 hipError_t launch_inertia_compose(const InertiaComposeParams& P, hipStream_t stream);
 hipError_t launch_sense_apply(const SenseParams& P, hipStream_t stream);
 hipError_t launch_sense_randomize(const SenseRandomParams& P, hipStream_t stream);
+hipError_t launch_sense_chain_apply(const SenseChainParams& C, hipStream_t stream);
+hipError_t launch_sense_chain_randomize(const SenseChainRandomParams& P, hipStream_t stream);
 }  // namespace saip
 
 using saip::CycleParams;
@@ -259,6 +262,19 @@ struct saip_batch {
 		double* q_meas = nullptr;            // [n][ld] what every non-diagnostic cycle, per-task and OTG launch reads in place of q
 		double* dq_meas = nullptr;           // [n][ld]
 		double* bounds = nullptr;            // joint lo [n][6], joint hi, wrench lo [S][18], wrench hi of saip_batch_sensing_randomize
+		// saip_batch_sensing_chain_attach: the sensing chain (saip_sense_chain.hip), the optional second stage: delay line, finite-difference
+		// velocity and low-pass per joint.  The first attachment with state: taps, filt and primed are on the snapshot directory
+		// (sense.chain.*) while attached; the table is configuration.  Nothing of the chain lives in a host scalar.
+		struct Chain {
+			bool attached = false;
+			int per_instance = 0, depth = 0;
+			double sample_time = 0;
+			double* table = nullptr;         // [n][4] (batch-uniform) or [n][4][ld]
+			double* taps = nullptr;          // [n][2][depth][ld] (nullptr at depth 0)
+			double* filt = nullptr;          // [n][3][ld] q_prev, y_q, y_dq
+			int* primed = nullptr;           // [n][ld]
+			double* bounds = nullptr;        // lo [n][4], hi of saip_batch_sensing_chain_randomize (per-instance table only)
+		} chain;
 	} sensing;
 };
 
@@ -323,6 +339,7 @@ saip_status plant_launch(saip_batch* b, double dt);
 void inertia_free(saip_batch* b);
 // ---- saip_engine_sensing.cpp
 void sensing_free(saip_batch* b);
+void sensing_chain_free(saip_batch* b);
 int sensing_sensor_slots(const saip_batch* b, bool planes, bool patches);
 saip_status sensing_launch(saip_batch* b, int mode, int slot_mask);
 saip_status sensing_refresh(saip_batch* b);

@@ -97,6 +97,21 @@ struct SenseParams {
 	const double* wrenches;      // [slots][6][3] or [slots][6][3][ld]
 	double* goal[SENSE_MAX_WRENCH_TASKS];  // the goal block of the slot's task, [goal_comps][ld]: rows 30..35 in place
 };
+#if defined(__HIPCC__)
+// Row `row` >= n of a sensing launch for instance b (b < B): one axis pair of the sensed wrench of one slot's task, goal rows 30..35 in
+// place.  Shared by saip_sense_apply and saip_sense_chain_apply (saip_sense_chain.hip), so that a rollout period keeps one measurement launch.
+__device__ inline void se_wrench_rows(const SenseParams& P, int row, int b) {
+	const size_t ld = P.ld;
+	const int r = row - P.n, slot = r / 3, pair = r % 3;
+	if (!(P.mode & SENSE_MODE_WRENCH) || slot >= P.n_slots || !((P.slot_mask >> slot) & 1)) return;
+	const long long ws = P.per_instance_wrenches ? (long long)ld : 1, wc = P.per_instance_wrenches ? (long long)b : 0;
+	double* g = (slot == 0 ? P.goal[0] : P.goal[1]) + (size_t)(SENSE_WRENCH_ROW0 + 2 * pair) * ld + b;
+	double f0 = g[0], f1 = g[ld];
+	se_wrench_pair(P.wrenches + (long long)slot * SENSE_WRENCH_WORDS * ws + wc, ws, P.seed_lo, P.seed_hi, P.period, b, slot, pair, &f0, &f1);
+	g[0] = f0;
+	g[ld] = f1;
+}
+#endif
 // one launch of saip_sense_randomize: either table may be left alone (null)
 struct SenseRandomParams {
 	int B, ld, n, n_slots;

@@ -25,14 +25,7 @@ __global__ void __launch_bounds__(64) saip_sense_apply(const SenseParams P) {
 		P.dq_meas[k] = dqm;
 		return;
 	}
-	const int r = row - P.n, slot = r / 3, pair = r % 3;
-	if (!(P.mode & SENSE_MODE_WRENCH) || slot >= P.n_slots || !((P.slot_mask >> slot) & 1)) return;
-	const long long ws = P.per_instance_wrenches ? (long long)ld : 1, wc = P.per_instance_wrenches ? (long long)b : 0;
-	double* g = (slot == 0 ? P.goal[0] : P.goal[1]) + (size_t)(SENSE_WRENCH_ROW0 + 2 * pair) * ld + b;
-	double f0 = g[0], f1 = g[ld];
-	se_wrench_pair(P.wrenches + (long long)slot * SENSE_WRENCH_WORDS * ws + wc, ws, P.seed_lo, P.seed_hi, P.period, b, slot, pair, &f0, &f1);
-	g[0] = f0;
-	g[ld] = f1;
+	se_wrench_rows(P, row, b);
 }
 
 // One lane per instance, looping over the words: every store of a wavefront is one contiguous run of a row.

@@ -33,7 +33,10 @@
    --sensing [--sensing-wrench] [--substeps S] times, interleaved in the same run, the closed-loop period without and with a per-instance
    sensing model (encoder offsets, 14-bit position resolution, position and velocity noise; with --sensing-wrench also contact planes with
    the simulated sensor, attached throughout, and a biased, quantised, noisy wrench table on their task) and the event-timed mean of 200
-   measurements of q, dq alone."""
+   measurements of q, dq alone.
+   --sensing-chain DEPTH [--substeps S] times, interleaved in the same run, the closed-loop period with that sensing model alone and with a
+   per-instance sensing chain of DEPTH taps behind it (delays 0..DEPTH across the instances, finite-difference velocity and both filters
+   on), and the event-timed mean of 200 measurements alone both ways."""
 import argparse
 import os
 import sys
@@ -96,6 +99,7 @@ ap.add_argument("--plant", action="store_true")
 ap.add_argument("--plant-wrenches", type=int, choices=range(5), default=1)
 ap.add_argument("--sensing", action="store_true")
 ap.add_argument("--sensing-wrench", action="store_true")
+ap.add_argument("--sensing-chain", type=int, choices=range(9), default=None, metavar="DEPTH")
 ap.add_argument("--inertia", action="store_true")
 ap.add_argument("--inertia-payloads", type=int, choices=range(3), default=1)
 args = ap.parse_args()
@@ -337,6 +341,42 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
                   f"closed-loop period {plain:.1f} us; with a per-instance plant model and {Wn} wrench(es) {with_p:.1f} us; without it again {again:.1f} us; "
                   f"one substep on the stream {plain_s:.2f} us plain, {with_s:.2f} us with the plant: launch alone {with_s - plain_s:.2f} us "
                   f"({clipped} of {B} instances clipped a torque)")
+        continue
+    if args.sensing_chain is not None:
+        rng = np.random.default_rng(0)
+        depth, T = args.sensing_chain, 5e-4
+        table = np.zeros((7, B, 6))
+        table[..., 0], table[..., 1], table[..., 2] = rng.uniform(-5e-3, 5e-3, (7, B)), 2 * np.pi / 2 ** 14, 1e-4
+        table[..., 3], table[..., 4], table[..., 5] = rng.uniform(-1e-2, 1e-2, (7, B)), 0.0, 5e-3
+        chain = np.zeros((7, B, 4))
+        chain[..., 0], chain[..., 1] = rng.integers(0, depth + 1, (7, B)), 1.0
+        chain[..., 2], chain[..., 3] = ctrl.sensingChainAlpha(200.0, T), ctrl.sensingChainAlpha(50.0, T)
+        timed_us, _ = stream_timer(ctrl)
+
+        def period_us():
+            t0 = time.perf_counter()
+            ctrl.rolloutAsync(K, T, args.substeps, gravity=(0, 0, 0))
+            ctrl.synchronize()
+            return (time.perf_counter() - t0) / K * 1e6
+
+        ctrl.attachSensing(table, per_instance=True, seed=1)
+        period_us()
+        for _ in range(args.repeats):
+            plain = period_us()
+            alone_s = timed_us(ctrl.measureState, 200)
+            ctrl.attachSensingChain(chain, per_instance=True, depth=depth, sample_time=T)
+            period_us()
+            with_c = period_us()
+            alone_c = timed_us(ctrl.measureState, 200)
+            nbytes = ctrl.sensingChainInfo()["state_bytes"]
+            finite = bool(np.isfinite(ctrl.pullState()[0]).all())
+            ctrl.detachSensingChain()
+            again, again2 = period_us(), period_us()
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {args.substeps}: "
+                  f"closed-loop period with the sensing model alone {plain:.1f} us; with a per-instance sensing chain of depth {depth} behind it {with_c:.1f} us; "
+                  f"alone again {again:.1f} us, and once more {again2:.1f} us; one measurement alone {alone_s:.2f} us without, {alone_c:.2f} us with the chain "
+                  f"({nbytes} bytes of chain state; state finite: {finite})")
+        ctrl.detachSensing()
         continue
     if args.sensing:
         rng = np.random.default_rng(0)
