@@ -550,6 +550,50 @@ double* saip_batch_plant_joints_device(saip_batch*);    /* NULL when detached */
 double* saip_batch_plant_wrenches_device(saip_batch*);  /* NULL when detached or without wrenches */
 double* saip_batch_plant_torques_device(saip_batch*);   /* [dof][ld]; NULL when detached */
 double* saip_batch_plant_summary_device(saip_batch*);   /* [4][ld]; NULL when detached */
+/* ---- actuation chain: the optional second stage of the plant model, the command-side twin of the sensing chain below.  Per joint it
+ * stands between the commanded torque and the plant's joint arithmetic: a delay line of up to SAIP_PLANT_CHAIN_MAX_DEPTH control periods,
+ * then a slew-rate limit, then a first-order lag.  Everything behind it (gain, bias, tau_max, friction, stops, wrenches, the summaries, the
+ * contact launch, the integrator) keeps its arithmetic and sees the chain's output in place of the commanded torque.  Attached only while a
+ * plant model is attached (an all-neutral plant table is a valid carrier); saip_batch_plant_detach detaches the chain first.  Its STATE is
+ * part of a state snapshot.
+ *   table     SAIP_PLANT_CHAIN_WORDS doubles per joint { delay, rate_max, tau_lag }: [dof][3] (batch-uniform) or [dof][3][B] (per_instance);
+ *             NULL: neutral rows { 0, +inf, 0 }, which hand the plant the command bit for bit (a NaN command as 0, as the plant reads it).
+ *             delay is integer-valued in 0..depth (control periods), rate_max > 0 in torque units per second (+inf: no limit), tau_lag
+ *             >= 0 and finite, the time constant in seconds (0: no lag).
+ *   substep   one per (joint, instance) per integration substep of length dt; advance = the first substep of a period:
+ *             x0 = t == t ? t : 0;   d = (int)delay
+ *             if (advance) { unless primed: every tap = x0, x_held = y_rate = y_lag = x0, primed = 1;
+ *                            x_held = d ? tap[d-1] : x0;   taps 1..d-1 shift by one, tap 0 takes x0 }
+ *             step = rate_max dt;   y_rate = rate_max < +inf ? y_rate + min(max(x_held - y_rate, -step), step) : x_held
+ *             y_lag = tau_lag > 0 ? y_lag + (dt / (tau_lag + dt)) (y_rate - y_lag) : y_rate;   the plant's joint gets y_lag
+ *             every product, sum and quotient rounded once, in the order written (csrc/saip_plant_chain.h; tests/plant_chain_ref.py).
+ *             The delay counts control periods (one saip_batch_integrate call or one rollout period is one period); the rate limit and
+ *             the lag run every substep.  No extra launch: while attached, saip_plant_apply<*, true> is enqueued where saip_plant_apply is.
+ *   state     per (joint, instance): taps [dof][depth][ld] (absent at depth 0), filt [dof][3][ld] { x_held, y_rate, y_lag }, primed
+ *             [dof][ld] (int32); zeroed at attach, freed at detach, listed by a snapshot as plant.chain.taps / .filt / .primed while
+ *             attached.  A snapshot of another chain layout is refused with ORDER, the segment named.  A restore does not re-prime: primed
+ *             travels with the column.  _chain_reset clears primed on the stream.  A new table keeps the state.
+ *   _chain_randomize fills the per-instance table: word w = 3 j + k of instance i is lo[w] + u (hi[w] - lo[w]) as in
+ *             saip_batch_plant_randomize, table id 9; lo == hi gives lo exactly (+inf stays +inf); delay is then rounded, floor(x + 0.5),
+ *             and clamped to 0..depth.
+ *   _chain_state_host: taps [dof][depth][B], filt [dof][3][B], primed [dof][B] (any may be NULL), synchronous: for tests and debugging.
+ * The recorder keeps logging commanded torques; saip_batch_plant_torques_device shows the actuated ones.
+ * Errors: INVALID_ARGUMENT for a depth outside 0..8, a bad table word (the message names the joint, the word and, per instance, the
+ * instance); ORDER before saip_batch_finalize, on a model-only batch, without a plant model, on a second attach and from every other _chain
+ * entry without a chain (_chain_info needs the plant model only).  Argument and order errors are reported before the device is needed;
+ * nothing is written on a refusal. */
+#define SAIP_PLANT_CHAIN_WORDS 3
+#define SAIP_PLANT_CHAIN_MAX_DEPTH 8
+#define SAIP_PLANT_TABLE_CHAIN 9
+saip_status saip_batch_plant_chain_attach(saip_batch*, const double* table /* NULL = neutral */, int per_instance, int depth);
+saip_status saip_batch_plant_chain_detach(saip_batch*);
+saip_status saip_batch_plant_chain_info(saip_batch*, int* attached, int* per_instance, int* depth, size_t* state_bytes);  /* any NULL */
+saip_status saip_batch_plant_chain_set_table_host(saip_batch*, const double* table);
+saip_status saip_batch_plant_chain_randomize(saip_batch*, unsigned long long seed, long long round, const double* lo, const double* hi);  /* per-instance table only */
+saip_status saip_batch_plant_chain_reset(saip_batch*);
+double* saip_batch_plant_chain_table_device(saip_batch*);  /* NULL when detached */
+saip_status saip_batch_plant_chain_state_host(saip_batch*, double* taps, double* filt, int* primed);  /* synchronous */
+saip_status saip_batch_plant_chain_state_device(saip_batch*, double** taps, double** filt, int** primed);  /* the arrays, [rows][ld]; taps NULL at depth 0 */
 /* ---- plant inertia: the inertial parameters of the SIMULATED robot, per instance.  While attached, the resident integrator (and nothing
  * else: the cycle kernels, the model queries and everything the controller computes keep the batch-uniform model) reads mass, centre of
  * mass and inertia of every movable body from a resident table.  One attachment per batch; configuration only, not part of a state

@@ -1345,6 +1345,65 @@ public:
 	double* plantTorquesDevice() { return saip_batch_plant_torques_device(_batch); }    // [dof][ld] actuated torques of the last substep
 	double* plantSummaryDevice() { return saip_batch_plant_summary_device(_batch); }    // [4][ld]
 
+	// ---- actuation chain: per joint a delay line, a slew-rate limit and a first-order lag between the commanded torque and the plant's
+	// joint rows (saip.h).  Needs an attached plant model (attachPlant() alone is a neutral carrier).  Its state is part of saveState() /
+	// restoreState().
+	struct ActuationChainInfo {
+		int attached = 0, per_instance = 0, depth = 0;
+		size_t state_bytes = 0;                // device bytes of taps, filt and primed
+	};
+	struct ActuationChainState {
+		std::vector<double> taps, filt;        // [dof][depth][B], [dof][3][B] { x_held, y_rate, y_lag }
+		std::vector<int> primed;               // [dof][B]
+	};
+	// the [dof][3] table that changes nothing: rows { 0, +inf, 0 }
+	std::vector<double> neutralActuationChainTable() {
+		std::vector<double> t((size_t)_robot->dof() * SAIP_PLANT_CHAIN_WORDS, 0.0);
+		for (size_t j = 0; j < (size_t)_robot->dof(); j++) t[j * SAIP_PLANT_CHAIN_WORDS + 1] = INFINITY;
+		return t;
+	}
+	// table: [dof][3] rows { delay, rate_max, tau_lag }, or [dof][3][B] with per_instance; empty: neutral.  depth 0..SAIP_PLANT_CHAIN_MAX_DEPTH
+	void attachActuationChain(const std::vector<double>& table, bool per_instance, int depth) {
+		const size_t cols = per_instance ? (size_t)_robot->batchSize() : 1;
+		if (!table.empty() && table.size() != (size_t)_robot->dof() * SAIP_PLANT_CHAIN_WORDS * cols)
+			throw std::invalid_argument("attachActuationChain: expected a [dof][3] table, or [dof][3][B] per instance");
+		check(saip_batch_plant_chain_attach(_batch, table.empty() ? nullptr : table.data(), per_instance ? 1 : 0, depth));
+	}
+	void detachActuationChain() { check(saip_batch_plant_chain_detach(_batch)); }
+	ActuationChainInfo actuationChainInfo() {
+		ActuationChainInfo i;
+		check(saip_batch_plant_chain_info(_batch, &i.attached, &i.per_instance, &i.depth, &i.state_bytes));
+		return i;
+	}
+	void setActuationChainTable(const std::vector<double>& table) {
+		const ActuationChainInfo i = actuationChainInfo();
+		if (table.size() != (size_t)_robot->dof() * SAIP_PLANT_CHAIN_WORDS * (i.per_instance ? (size_t)_robot->batchSize() : 1))
+			throw std::invalid_argument("setActuationChainTable: the shape of the attached chain table expected");
+		check(saip_batch_plant_chain_set_table_host(_batch, table.data()));
+	}
+	// the per-instance table drawn on the device between two [dof][3] tables; delay rounded and clamped after the draw
+	void actuationChainRandomize(unsigned long long seed, long long round, const std::vector<double>& lo, const std::vector<double>& hi) {
+		const size_t w = (size_t)_robot->dof() * SAIP_PLANT_CHAIN_WORDS;
+		if (lo.size() != w || hi.size() != w) throw std::invalid_argument("actuationChainRandomize: expected [dof][3] bounds");
+		check(saip_batch_plant_chain_randomize(_batch, seed, round, lo.data(), hi.data()));
+	}
+	// the next period primes the chain again (enqueued, no wait)
+	void resetActuationChain() { check(saip_batch_plant_chain_reset(_batch)); }
+	// for tests and debugging; waits for the stream
+	ActuationChainState actuationChainState() {
+		const ActuationChainInfo i = actuationChainInfo();
+		const size_t n = _robot->dof(), B = _robot->batchSize();
+		ActuationChainState s;
+		s.taps.resize(n * i.depth * B);
+		s.filt.resize(n * 3 * B);
+		s.primed.resize(n * B);
+		check(saip_batch_plant_chain_state_host(_batch, s.taps.empty() ? nullptr : s.taps.data(), s.filt.data(), s.primed.data()));
+		return s;
+	}
+	// the state arrays, [rows][ld]: taps [dof][depth] rows (nullptr at depth 0), filt [dof][3] rows, primed [dof] rows
+	void actuationChainStateDevice(double** taps, double** filt, int** primed) { check(saip_batch_plant_chain_state_device(_batch, taps, filt, primed)); }
+	double* actuationChainTableDevice() { return saip_batch_plant_chain_table_device(_batch); }  // [dof][3] or [dof][3][ld]
+
 	// ---- sensing model: offset, noise and quantisation between the resident simulator and what the controller reads of it (saip.h).
 	// While attached, every control cycle, per-task entry and internal OTG reads the measured q, dq; the simulator, the recorder and the
 	// model queries keep the true state.  The period counter of the noise advances once per integrate() and once per rollout period.

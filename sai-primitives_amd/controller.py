@@ -1857,6 +1857,80 @@ class RobotController:
         """device pointer of the (4, ld) running summaries; None when detached"""
         return capi.lib().saip_batch_plant_summary_device(self._h)
 
+    # -- actuation chain: delay line, slew-rate limit and first-order lag between the commanded torque and the plant's joint rows; its state
+    # is snapshot state
+    PLANT_CHAIN_WORDS = ("delay", "rate_max", "tau_lag")
+
+    def _plant_chain_rows(self, table, per_instance, who, what="chain table"):
+        if isinstance(table, dict):
+            table = dict(table)
+            table.setdefault("rate_max", np.inf)  # the neutral word: a dict names only what it changes
+        return self._sense_rows(table, self.PLANT_CHAIN_WORDS, per_instance, self._robot.dof(), who, what)
+
+    def attachActuationChain(self, table=None, per_instance=False, depth=0):
+        """put an actuation chain in front of the attached plant model (attachPlant() first; attachPlant() alone is a neutral carrier).
+        table: (dof, 3) rows { delay, rate_max, tau_lag } (or (dof, B, 3) with per_instance), or a dict { word: scalar or (dof,) or
+        (dof, B) } of the words that differ from the neutral row 0, inf, 0; None: neutral.  delay: whole control periods, 0..depth
+        (depth <= 8); rate_max > 0: the largest change of the torque per second (inf: no limit); tau_lag >= 0: the time constant of a
+        first-order lag in seconds (0: none).  The delay line moves once per period (integrate() call or rollout period), the rate limit
+        and the lag run every substep.  The chain's state is part of saveState() / restoreState()."""
+        who = "attachActuationChain"
+        t = None if table is None else self._plant_chain_rows(table, per_instance, who)
+        self._call("saip_batch_plant_chain_attach", None if t is None else _dptr(t), int(bool(per_instance)), int(depth))
+
+    def detachActuationChain(self):
+        self._call("saip_batch_plant_chain_detach")
+
+    def actuationChainInfo(self):
+        """dict attached, per_instance, depth, state_bytes (device bytes of taps, filt and primed); needs a plant model"""
+        v = [C.c_int(0) for _ in range(3)]
+        nb = C.c_size_t(0)
+        self._call("saip_batch_plant_chain_info", C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(nb))
+        return dict(attached=bool(v[0].value), per_instance=bool(v[1].value), depth=v[2].value, state_bytes=nb.value)
+
+    def _actuation_chain_info(self, who):
+        info = self.actuationChainInfo()
+        if not info["attached"]:
+            raise capi.SaipError(f"{who}: no actuation chain is attached (attachActuationChain)")
+        return info
+
+    def setActuationChainTable(self, table):
+        """replace the chain table (same layout as attached); the state stays (resetActuationChain() starts afresh)"""
+        info = self._actuation_chain_info("setActuationChainTable")
+        a = self._plant_chain_rows(table, info["per_instance"], "setActuationChainTable")
+        self._call("saip_batch_plant_chain_set_table_host", _dptr(a))
+
+    def actuationChainRandomize(self, seed, round=0, lo=None, hi=None):
+        """draw the per-instance chain table on the device between two (dof, 3) tables; lo == hi gives lo exactly (an infinite rate_max
+        stays infinite); delay is rounded to the nearest integer and clamped to 0..depth after the draw; reproducible for (seed, round)"""
+        self._actuation_chain_info("actuationChainRandomize")
+        lo, hi = (self._plant_table(x, False, 0, self._robot.dof(), capi.SAIP_PLANT_CHAIN_WORDS, "actuationChainRandomize", "chain bounds") for x in (lo, hi))
+        self._call("saip_batch_plant_chain_randomize", int(seed) & (2**64 - 1), int(round), _dptr(lo), _dptr(hi))
+
+    def resetActuationChain(self):
+        """the next period primes the chain again: every tap, x_held and both filters start from that period's command (enqueued, no wait)"""
+        self._call("saip_batch_plant_chain_reset")
+
+    def actuationChainState(self):
+        """dict taps (B, dof, depth), filt (B, dof, 3) { x_held, y_rate, y_lag }, primed (B, dof) int (waits for the engine stream): for
+        tests and debugging"""
+        info = self._actuation_chain_info("actuationChainState")
+        n, B, d = self._robot.dof(), self.batch_size, info["depth"]
+        taps, filt, primed = np.zeros((n, d, B)), np.empty((n, 3, B)), np.empty((n, B), np.int32)
+        self._call("saip_batch_plant_chain_state_host", _dptr(taps) if d else None, _dptr(filt), primed.ctypes.data_as(C.POINTER(C.c_int)))
+        return dict(taps=np.ascontiguousarray(taps.transpose(2, 0, 1)), filt=np.ascontiguousarray(filt.transpose(2, 0, 1)), primed=np.ascontiguousarray(primed.T))
+
+    def actuationChainStateDevice(self):
+        """device pointers (taps, filt, primed) of the state arrays, (depth dof, ld), (3 dof, ld) float64 and (dof, ld) int32; taps is
+        None at depth 0"""
+        p = [C.c_void_p() for _ in range(3)]
+        self._call("saip_batch_plant_chain_state_device", C.byref(p[0]), C.byref(p[1]), C.byref(p[2]))
+        return tuple(x.value for x in p)
+
+    def actuationChainTableDevice(self):
+        """device pointer of the resident chain table, (dof, 3) or (dof, 3, ld); None when detached"""
+        return capi.lib().saip_batch_plant_chain_table_device(self._h)
+
     # -- sensing model: offset, noise and quantisation between the resident state and what the controller reads of it (saip.h)
     SENSE_JOINT_WORDS = ("q_off", "q_res", "q_sigma", "dq_off", "dq_res", "dq_sigma")
     SENSE_AXIS_WORDS = ("off", "res", "sigma")

@@ -22,6 +22,7 @@
 #include "saip_contact_patch.h"
 #include "saip_clearance.h"
 #include "saip_plant.h"
+#include "saip_plant_chain.h"
 #include "saip_inertia.h"
 #include "saip_sense.h"
 #include "saip_sense_chain.h"
@@ -58,6 +59,8 @@ hipError_t launch_clearance_add_cost(int B, int ld, const double* summary, doubl
 hipError_t launch_clearance_summary_reset(int B, int ld, double* summary, hipStream_t stream);
 hipError_t launch_plant_apply(const PlantParams& P, bool tree, hipStream_t stream);
 hipError_t launch_plant_randomize(const PlantRandomParams& P, hipStream_t stream);
+hipError_t launch_plant_chain_apply(const PlantChainParams& C, bool tree, hipStream_t stream);
+hipError_t launch_plant_chain_randomize(const PlantChainRandomParams& P, hipStream_t stream);
 hipError_t launch_inertia_compose(const InertiaComposeParams& P, hipStream_t stream);
 hipError_t launch_sense_apply(const SenseParams& P, hipStream_t stream);
 hipError_t launch_sense_randomize(const SenseRandomParams& P, hipStream_t stream);
@@ -222,8 +225,9 @@ struct saip_batch {
 		double* centres = nullptr;           // [3 S][ld], keep_centres only
 	} clearance;
 	// saip_batch_plant_attach: the plant model of the resident simulator (saip_plant.hip), at most one per batch: actuator limits, friction,
-	// joint stops and external wrenches in front of every integration substep.  Nothing in it is state: its arrays are configuration,
-	// scratch and summaries, its own (freed by _detach), not part of `allocs` or of a snapshot; `period` is a host-side counter.
+	// joint stops and external wrenches in front of every integration substep.  Nothing in it but the `chain` sub-block is state: its
+	// arrays are configuration, scratch and summaries, its own (freed by _detach), not part of `allocs` or of a snapshot; `period` is a
+	// host-side counter.
 	struct Plant {
 		bool attached = false;
 		int per_instance_joints = 0, n_wrenches = 0, per_instance_wrenches = 0;
@@ -234,6 +238,19 @@ struct saip_batch {
 		double* tau_act = nullptr;           // [n][ld] what the actuators, friction, stops and wrenches make of the commanded torques
 		double* summary = nullptr;           // [4][ld]
 		double* bounds = nullptr;            // joint lo [n][10], joint hi, wrench lo [W][8], wrench hi of saip_batch_plant_randomize (per-instance tables only)
+		// saip_batch_plant_chain_attach: the actuation chain (saip_plant_chain.h), the optional second stage: per joint a delay line, a
+		// slew-rate limit and a first-order lag between the commanded torque and pl_joint.  Like the sensing chain it has state: taps, filt
+		// and primed are on the snapshot directory (plant.chain.*) while attached; the table is configuration.  Nothing of the chain lives
+		// in a host scalar.
+		struct Chain {
+			bool attached = false;
+			int per_instance = 0, depth = 0;
+			double* table = nullptr;         // [n][3] (batch-uniform) or [n][3][ld]
+			double* taps = nullptr;          // [n][depth][ld] (nullptr at depth 0)
+			double* filt = nullptr;          // [n][3][ld] x_held, y_rate, y_lag
+			int* primed = nullptr;           // [n][ld]
+			double* bounds = nullptr;        // lo [n][3], hi of saip_batch_plant_chain_randomize (per-instance table only)
+		} chain;
 	} plant;
 	// saip_batch_inertia_attach: the inertial parameters of the simulated robot (saip_inertia.hip), at most one per batch: the table the
 	// resident integrator reads in place of the model's masses, centres of mass and inertias.  Configuration only: its arrays are its own
@@ -334,7 +351,8 @@ void clearance_free(saip_batch* b);
 saip_status clearance_launch(saip_batch* b, int mode, double dt);
 // ---- saip_engine_plant.cpp
 void plant_free(saip_batch* b);
-saip_status plant_launch(saip_batch* b, double dt);
+void plant_chain_free(saip_batch* b);
+saip_status plant_launch(saip_batch* b, double dt, int substep);
 // ---- saip_engine_inertia.cpp
 void inertia_free(saip_batch* b);
 // ---- saip_engine_sensing.cpp

@@ -7,8 +7,15 @@ static saip_status need_plant(const saip_batch* b, const char* fn) {
 	if (!b->plant.attached) return fail(SAIP_ERR_ORDER, "%s: no plant model is attached (saip_batch_plant_attach)", fn);
 	return SAIP_OK;
 }
+void saip::eng::plant_chain_free(saip_batch* b) {
+	auto& H = b->plant.chain;
+	for (void* p : {(void*)H.table, (void*)H.taps, (void*)H.filt, (void*)H.primed, (void*)H.bounds})
+		if (p) (void)hipFree(p);
+	H = saip_batch::Plant::Chain();
+}
 void saip::eng::plant_free(saip_batch* b) {
 	auto& C = b->plant;
+	plant_chain_free(b);  // the chain goes with its carrier
 	for (void* p : {(void*)C.joints, (void*)C.wrenches, (void*)C.tau_act, (void*)C.summary, (void*)C.bounds})
 		if (p) (void)hipFree(p);
 	C = saip_batch::Plant();
@@ -257,7 +264,8 @@ extern "C" double* saip_batch_plant_wrenches_device(saip_batch* b) { return b ? 
 extern "C" double* saip_batch_plant_torques_device(saip_batch* b) { return b ? b->plant.tau_act : nullptr; }
 extern "C" double* saip_batch_plant_summary_device(saip_batch* b) { return b ? b->plant.summary : nullptr; }
 // one launch of the plant kernel at the resident state, in front of an integration substep of length dt
-saip_status saip::eng::plant_launch(saip_batch* b, double dt) {
+// (substep: its index inside the period; the actuation chain advances its delay line in substep 0 only)
+saip_status saip::eng::plant_launch(saip_batch* b, double dt, int substep) {
 	const auto& C = b->plant;
 	saip::PlantParams P;
 	memset(&P, 0, sizeof(P));
@@ -278,7 +286,198 @@ saip_status saip::eng::plant_launch(saip_batch* b, double dt) {
 	P.tau_act = C.tau_act;
 	P.summary = C.summary;
 	for (int k = 0; k < C.n_wrenches; k++) P.site[k] = C.site[k];
-	hipError_t e = saip::launch_plant_apply(P, b->model->dev.is_tree != 0, b->stream);
+	hipError_t e;
+	if (C.chain.attached) {
+		// the chain's instantiation in place of the plant's: the same launch, pc_step in front of every pl_joint
+		const auto& H = C.chain;
+		saip::PlantChainParams Q;
+		memset(&Q, 0, sizeof(Q));
+		Q.P = P;
+		Q.per_instance = H.per_instance;
+		Q.depth = H.depth;
+		Q.advance = substep == 0 ? 1 : 0;
+		Q.table = H.table;
+		Q.taps = H.taps;
+		Q.filt = H.filt;
+		Q.primed = H.primed;
+		e = saip::launch_plant_chain_apply(Q, b->model->dev.is_tree != 0, b->stream);
+	} else e = saip::launch_plant_apply(P, b->model->dev.is_tree != 0, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "plant launch failed: %s", hipGetErrorString(e));
+	return SAIP_OK;
+}
+
+// ---- the actuation chain (saip_plant_chain.h): delay line, slew-rate limit and first-order lag in front of the plant's joint rows.  Its
+// state (taps, filt, primed) is on the snapshot directory while attached (saip_engine_snapshot.cpp).
+static saip_status need_plant_chain(const saip_batch* b, const char* fn) {
+	saip_status st = need_plant(b, fn);
+	if (st) return st;
+	if (!b->plant.chain.attached) return fail(SAIP_ERR_ORDER, "%s: no actuation chain is attached (saip_batch_plant_chain_attach)", fn);
+	return SAIP_OK;
+}
+static const char* const PLANT_CHAIN_WORD_NAMES[saip::PLANT_CHAIN_WORDS] = {"delay", "rate_max", "tau_lag"};
+// a chain table [n][3] (cols = 1) or [n][3][cols]: true when fine, else msg names the joint and the word (and the instance).  bounds: the
+// two tables of a draw, whose delay is rounded and clamped afterwards and only has to be finite
+static bool plant_chain_check_table(const double* t, int n, size_t cols, int depth, bool bounds, char* msg, size_t len) {
+	using namespace saip;
+	char buf[96];
+	for (int j = 0; j < n; j++)
+		for (size_t i = 0; i < cols; i++)
+			for (int k = 0; k < PLANT_CHAIN_WORDS; k++) {
+				const double v = t[((size_t)j * PLANT_CHAIN_WORDS + k) * cols + i];
+				const char* name = PLANT_CHAIN_WORD_NAMES[k];
+				buf[0] = 0;
+				if (v != v) snprintf(buf, sizeof(buf), "word %s is NaN", name);
+				else if (k != PLANT_CHAIN_RATE_MAX && !std::isfinite(v)) snprintf(buf, sizeof(buf), "word %s is not finite", name);
+				else if (k == PLANT_CHAIN_DELAY && !bounds && (v != std::floor(v) || v < 0 || v > depth))
+					snprintf(buf, sizeof(buf), "word %s = %g is not an integer in 0..%d", name, v, depth);
+				else if (k == PLANT_CHAIN_RATE_MAX && !(v > 0)) snprintf(buf, sizeof(buf), "word %s = %g is not above 0", name, v);
+				else if (k == PLANT_CHAIN_TAU_LAG && v < 0) snprintf(buf, sizeof(buf), "word %s = %g is below 0", name, v);
+				if (!buf[0]) continue;
+				if (cols > 1) snprintf(msg, len, "joint %d of instance %zu: %s", j, i, buf);
+				else snprintf(msg, len, "joint %d: %s", j, buf);
+				return false;
+			}
+	return true;
+}
+static size_t plant_chain_state_bytes(const saip_batch* b, int depth) {
+	const size_t n = b->model->n, ld = b->ld;
+	return ((size_t)depth * n + saip::PLANT_CHAIN_FILT_ROWS * n) * ld * sizeof(double) + n * ld * sizeof(int);
+}
+extern "C" saip_status saip_batch_plant_chain_attach(saip_batch* b, const double* table, int per_instance, int depth) {
+	const char* fn = "saip_batch_plant_chain_attach";
+	saip_status st = need_controller(b, fn);
+	if (st) return st;
+	const int n = b->model->n;
+	// the arguments first (nothing here needs the plant model or the device), then the call order
+	if (depth < 0 || depth > saip::PLANT_CHAIN_MAX_DEPTH) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a depth of 0..%d required (got %d)", fn, saip::PLANT_CHAIN_MAX_DEPTH, depth);
+	per_instance = per_instance ? 1 : 0;
+	const size_t cols = per_instance ? (size_t)b->B : 1;
+	std::vector<double> neutral;
+	if (!table) {
+		neutral.assign((size_t)n * saip::PLANT_CHAIN_WORDS * cols, 0.0);
+		for (int j = 0; j < n; j++)
+			for (size_t i = 0; i < cols; i++) neutral[((size_t)j * saip::PLANT_CHAIN_WORDS + saip::PLANT_CHAIN_RATE_MAX) * cols + i] = INFINITY;
+		table = neutral.data();
+	}
+	char msg[200];
+	if (!plant_chain_check_table(table, n, cols, depth, false, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, msg);
+	if (!b->plant.attached) return fail(SAIP_ERR_ORDER, "%s: no plant model is attached (saip_batch_plant_attach; an all-neutral table is a valid carrier)", fn);
+	if (b->plant.chain.attached) return fail(SAIP_ERR_ORDER, "%s: an actuation chain is already attached (saip_batch_plant_chain_detach first)", fn);
+	if ((st = need_ready(b, fn))) return st;
+	auto& H = b->plant.chain;
+	H = saip_batch::Plant::Chain();
+	const size_t ld = b->ld, rows = (size_t)n * saip::PLANT_CHAIN_WORDS;
+	double* primed = nullptr;
+	if ((st = alloc_zero(b, &H.table, rows * (per_instance ? ld : 1))) || (depth > 0 && (st = alloc_zero(b, &H.taps, (size_t)depth * n * ld))) ||
+		(st = alloc_zero(b, &H.filt, (size_t)saip::PLANT_CHAIN_FILT_ROWS * n * ld)) || (st = alloc_zero(b, &primed, ((size_t)n * ld + 1) / 2)) ||
+		(per_instance && (st = alloc_zero(b, &H.bounds, 2 * rows))) || (st = upload_table(b, H.table, table, rows, per_instance, "table", fn))) {
+		if (primed) (void)hipFree(primed);
+		plant_chain_free(b);
+		return st;
+	}
+	H.primed = (int*)primed;  // n ld 32-bit flags, zeroed
+	H.attached = true;
+	H.per_instance = per_instance;
+	H.depth = depth;
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_plant_chain_detach(saip_batch* b) {
+	const char* fn = "saip_batch_plant_chain_detach";
+	saip_status st = need_plant_chain(b, fn);
+	if (st || (st = need_ready(b, fn))) return st;
+	HIP_TRY(hipStreamSynchronize(b->stream));  // a plant substep that writes the chain's state may still be in flight
+	plant_chain_free(b);
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_plant_chain_info(saip_batch* b, int* attached, int* per_instance, int* depth, size_t* state_bytes) {
+	saip_status st = need_plant(b, "saip_batch_plant_chain_info");
+	if (st) return st;
+	const auto& H = b->plant.chain;
+	if (attached) *attached = H.attached ? 1 : 0;
+	if (per_instance) *per_instance = H.per_instance;
+	if (depth) *depth = H.depth;
+	if (state_bytes) *state_bytes = H.attached ? plant_chain_state_bytes(b, H.depth) : 0;
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_plant_chain_set_table_host(saip_batch* b, const double* table) {
+	const char* fn = "saip_batch_plant_chain_set_table_host";
+	saip_status st = need_plant_chain(b, fn);
+	if (st) return st;
+	if (!table) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null table", fn);
+	auto& H = b->plant.chain;
+	char msg[200];
+	if (!plant_chain_check_table(table, b->model->n, H.per_instance ? (size_t)b->B : 1, H.depth, false, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, msg);
+	if ((st = need_ready(b, fn))) return st;
+	// the state stays: the next substep runs the new words over the history there is (saip_batch_plant_chain_reset starts afresh)
+	return upload_table(b, H.table, table, (size_t)b->model->n * saip::PLANT_CHAIN_WORDS, H.per_instance, "table", fn);
+}
+// The per-instance table drawn on the device between two batch-uniform tables [n][3] (host pointers).  rate_max and tau_lag of both bounds
+// have to be valid words, an infinite rate_max on both sides or on neither; delay only finite: the draw is rounded to the nearest integer
+// and clamped to its range.
+extern "C" saip_status saip_batch_plant_chain_randomize(saip_batch* b, unsigned long long seed, long long round, const double* lo, const double* hi) {
+	const char* fn = "saip_batch_plant_chain_randomize";
+	saip_status st = need_plant_chain(b, fn);
+	if (st) return st;
+	auto& H = b->plant.chain;
+	const int n = b->model->n;
+	if (!lo || !hi) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null bounds", fn);
+	if (!H.per_instance) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the chain table is batch-uniform (attach it per instance)", fn);
+	char msg[200];
+	for (const double* t : {lo, hi})
+		if (!plant_chain_check_table(t, n, 1, H.depth, true, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s bound: %s", fn, t == lo ? "lower" : "upper", msg);
+	const size_t rows = (size_t)n * saip::PLANT_CHAIN_WORDS;
+	for (size_t k = 0; k < rows; k++)
+		if (lo[k] != hi[k] && !(std::isfinite(lo[k]) && std::isfinite(hi[k])))
+			return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: joint %zu: word %s has an infinite bound on one side only", fn, k / saip::PLANT_CHAIN_WORDS, PLANT_CHAIN_WORD_NAMES[k % saip::PLANT_CHAIN_WORDS]);
+	if ((st = need_ready(b, fn))) return st;
+	if ((st = upload_table(b, H.bounds, lo, rows, 0, "table", fn)) || (st = upload_table(b, H.bounds + rows, hi, rows, 0, "table", fn))) return st;
+	saip::PlantChainRandomParams P;
+	memset(&P, 0, sizeof(P));
+	P.B = b->B;
+	P.ld = b->ld;
+	P.n = n;
+	P.depth = H.depth;
+	P.seed_lo = (uint32_t)seed;
+	P.seed_hi = (uint32_t)(seed >> 32);
+	P.round = (uint32_t)round;
+	P.table = H.table;
+	P.lo = H.bounds;
+	P.hi = H.bounds + rows;
+	hipError_t e = saip::launch_plant_chain_randomize(P, b->stream);
+	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "actuation chain randomize launch failed: %s", hipGetErrorString(e));
+	return SAIP_OK;
+}
+// primed cleared on the stream, without a synchronisation: the next period's first substep primes every (joint, instance) again
+extern "C" saip_status saip_batch_plant_chain_reset(saip_batch* b) {
+	const char* fn = "saip_batch_plant_chain_reset";
+	saip_status st = need_plant_chain(b, fn);
+	if (st || (st = need_ready(b, fn))) return st;
+	HIP_TRY(hipMemsetAsync(b->plant.chain.primed, 0, (size_t)b->model->n * b->ld * sizeof(int), b->stream));
+	return SAIP_OK;
+}
+extern "C" double* saip_batch_plant_chain_table_device(saip_batch* b) { return b ? b->plant.chain.table : nullptr; }
+// the state arrays themselves, [rows][ld] (taps null at depth 0); any output may be null
+extern "C" saip_status saip_batch_plant_chain_state_device(saip_batch* b, double** taps, double** filt, int** primed) {
+	saip_status st = need_plant_chain(b, "saip_batch_plant_chain_state_device");
+	if (st) return st;
+	const auto& H = b->plant.chain;
+	if (taps) *taps = H.taps;
+	if (filt) *filt = H.filt;
+	if (primed) *primed = H.primed;
+	return SAIP_OK;
+}
+// the state for tests and debugging: taps [n][depth][B], filt [n][3][B], primed [n][B]; any may be null
+extern "C" saip_status saip_batch_plant_chain_state_host(saip_batch* b, double* taps, double* filt, int* primed) {
+	const char* fn = "saip_batch_plant_chain_state_host";
+	saip_status st = need_plant_chain(b, fn);
+	if (st || (st = need_ready(b, fn))) return st;
+	const auto& H = b->plant.chain;
+	const int n = b->model->n;
+	if (taps && H.depth > 0 && (st = copy_d2h(b, taps, H.taps, H.depth * n))) return st;
+	if (filt && (st = copy_d2h(b, filt, H.filt, saip::PLANT_CHAIN_FILT_ROWS * n))) return st;
+	if (primed) {
+		HIP_TRY(hipMemcpy2DAsync(primed, (size_t)b->B * sizeof(int), H.primed, (size_t)b->ld * sizeof(int), (size_t)b->B * sizeof(int), n, hipMemcpyDeviceToHost, b->stream));
+		HIP_TRY(hipStreamSynchronize(b->stream));
+	}
 	return SAIP_OK;
 }

@@ -30,7 +30,7 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 		S.substeps = 1;
 		S.tau = patches ? b->patch_tau_sim : contact ? b->contact.tau_sim : b->plant.tau_act;
 		for (int s = 0; s < substeps; s++) {
-			saip_status st = b->plant.attached ? plant_launch(b, dt) : SAIP_OK;
+			saip_status st = b->plant.attached ? plant_launch(b, dt, s) : SAIP_OK;  // s == 0: the actuation chain advances its delay line
 			if (st) return st;
 			if (contact) st = patches ? patch_launch(b, saip::CONTACT_APPLY, dt) : contact_launch(b, saip::CONTACT_APPLY, dt);
 			if (st) return st;

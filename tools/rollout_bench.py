@@ -36,7 +36,10 @@
    measurements of q, dq alone.
    --sensing-chain DEPTH [--substeps S] times, interleaved in the same run, the closed-loop period with that sensing model alone and with a
    per-instance sensing chain of DEPTH taps behind it (delays 0..DEPTH across the instances, finite-difference velocity and both filters
-   on), and the event-timed mean of 200 measurements alone both ways."""
+   on), and the event-timed mean of 200 measurements alone both ways.
+   --plant --plant-chain DEPTH [--plant-wrenches W] [--substeps S] times, interleaved in the same run, the closed-loop period with that plant
+   model alone and with a per-instance actuation chain of DEPTH taps in front of it (delays 0..DEPTH across the instances, rate limit and
+   lag on), and the event-timed mean of 200 one-substep integrate calls both ways."""
 import argparse
 import os
 import sys
@@ -97,12 +100,15 @@ ap.add_argument("--clearance-obstacles", type=int, default=4)
 ap.add_argument("--clearance-pairs", type=int, default=0)
 ap.add_argument("--plant", action="store_true")
 ap.add_argument("--plant-wrenches", type=int, choices=range(5), default=1)
+ap.add_argument("--plant-chain", type=int, choices=range(9), default=None, metavar="DEPTH")
 ap.add_argument("--sensing", action="store_true")
 ap.add_argument("--sensing-wrench", action="store_true")
 ap.add_argument("--sensing-chain", type=int, choices=range(9), default=None, metavar="DEPTH")
 ap.add_argument("--inertia", action="store_true")
 ap.add_argument("--inertia-payloads", type=int, choices=range(3), default=1)
 args = ap.parse_args()
+if args.plant_chain is not None and not args.plant:
+    ap.error("--plant-chain needs --plant: the actuation chain stands in front of the plant model")
 record = args.record_stride is not None or args.record_channels is not None or args.record_summaries
 
 for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
@@ -329,6 +335,27 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
         def substep_us():
             return timed_us(lambda: ctrl.integrate(5e-4, 1, gravity=(0, 0, 0)), 200)
 
+        if args.plant_chain is not None:
+            depth = args.plant_chain
+            chain = np.zeros((7, B, 3))
+            chain[..., 0], chain[..., 1], chain[..., 2] = rng.integers(0, depth + 1, (7, B)), rng.uniform(2e3, 2e4, (7, B)), rng.uniform(5e-4, 5e-3, (7, B))
+            ctrl.attachPlant(table, wr, per_instance=True)
+            period_us()
+            for _ in range(args.repeats):
+                plain, plain_s = period_us(), substep_us()
+                ctrl.attachActuationChain(chain, per_instance=True, depth=depth)
+                period_us()
+                with_c, with_s = period_us(), substep_us()
+                nbytes = ctrl.actuationChainInfo()["state_bytes"]
+                finite = bool(np.isfinite(ctrl.pullState()[0]).all())
+                ctrl.detachActuationChain()
+                again, again2 = period_us(), period_us()
+                print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {args.substeps}: "
+                      f"closed-loop period with the plant model alone {plain:.1f} us; with a per-instance actuation chain of depth {depth} in front of it {with_c:.1f} us; "
+                      f"alone again {again:.1f} us, and once more {again2:.1f} us; one substep on the stream {plain_s:.2f} us without, {with_s:.2f} us with the chain "
+                      f"({nbytes} bytes of chain state; state finite: {finite})")
+            ctrl.detachPlant()
+            continue
         for _ in range(args.repeats):
             plain, plain_s = period_us(), substep_us()
             ctrl.attachPlant(table, wr, per_instance=True)
