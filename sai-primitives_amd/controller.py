@@ -1857,15 +1857,51 @@ class RobotController:
         """device pointer of the (4, ld) running summaries; None when detached"""
         return capi.lib().saip_batch_plant_summary_device(self._h)
 
+    # -- the two chains (below: the actuation chain; behind the sensing model: the sensing chain) share these helpers.  k is what differs:
+    # (C prefix, words, leading shape of taps per unit of depth, noun, the public methods' stem, neutral words that are not 0, whether the
+    # info has a sample time)
+    def _chain_rows(self, k, table, per_instance, who):
+        if isinstance(table, dict):
+            table = {**k[5], **table}  # the neutral words: a dict names only what it changes
+        return self._sense_rows(table, k[1], per_instance, self._robot.dof(), who, "chain table")
+
+    def _chain_attach(self, k, table, per_instance, depth, *more):
+        t = None if table is None else self._chain_rows(k, table, per_instance, "attach" + k[4])
+        self._call(k[0] + "_attach", None if t is None else _dptr(t), int(bool(per_instance)), int(depth), *more)
+
+    def _chain_info(self, k, who=None):
+        """the info dict; with who, that method's refusal of a detached chain"""
+        v, T, nb = [C.c_int(0) for _ in range(3)], [C.c_double(0)] * k[6], C.c_size_t(0)
+        self._call(k[0] + "_info", *(C.byref(x) for x in v + T + [nb]))
+        info = dict(attached=bool(v[0].value), per_instance=bool(v[1].value), depth=v[2].value, **({"sample_time": T[0].value} if T else {}), state_bytes=nb.value)
+        if who and not info["attached"]:
+            raise capi.SaipError(f"{who}: no {k[3]} is attached (attach{k[4]})")
+        return info
+
+    def _chain_set_table(self, k, table):
+        who = f"set{k[4]}Table"
+        self._call(k[0] + "_set_table_host", _dptr(self._chain_rows(k, table, self._chain_info(k, who)["per_instance"], who)))
+
+    def _chain_randomize(self, k, who, seed, round, lo, hi):
+        self._chain_info(k, who)
+        lo, hi = (self._plant_table(x, False, 0, self._robot.dof(), len(k[1]), who, "chain bounds") for x in (lo, hi))
+        self._call(k[0] + "_randomize", int(seed) & (2**64 - 1), int(round), _dptr(lo), _dptr(hi))
+
+    def _chain_state(self, k, who):
+        n, B, d = self._robot.dof(), self.batch_size, self._chain_info(k, who)["depth"]
+        taps, filt, primed = np.zeros((n,) + k[2] + (d, B)), np.empty((n, 3, B)), np.empty((n, B), np.int32)
+        self._call(k[0] + "_state_host", _dptr(taps) if d else None, _dptr(filt), primed.ctypes.data_as(C.POINTER(C.c_int)))
+        return dict(taps=np.ascontiguousarray(np.moveaxis(taps, -1, 0)), filt=np.ascontiguousarray(filt.transpose(2, 0, 1)), primed=np.ascontiguousarray(primed.T))
+
+    def _chain_state_device(self, k):
+        p = [C.c_void_p() for _ in range(3)]
+        self._call(k[0] + "_state_device", C.byref(p[0]), C.byref(p[1]), C.byref(p[2]))
+        return tuple(x.value for x in p)
+
     # -- actuation chain: delay line, slew-rate limit and first-order lag between the commanded torque and the plant's joint rows; its state
     # is snapshot state
     PLANT_CHAIN_WORDS = ("delay", "rate_max", "tau_lag")
-
-    def _plant_chain_rows(self, table, per_instance, who, what="chain table"):
-        if isinstance(table, dict):
-            table = dict(table)
-            table.setdefault("rate_max", np.inf)  # the neutral word: a dict names only what it changes
-        return self._sense_rows(table, self.PLANT_CHAIN_WORDS, per_instance, self._robot.dof(), who, what)
+    _ACTUATION_CHAIN = ("saip_batch_plant_chain", PLANT_CHAIN_WORDS, (), "actuation chain", "ActuationChain", {"rate_max": np.inf}, 0)
 
     def attachActuationChain(self, table=None, per_instance=False, depth=0):
         """put an actuation chain in front of the attached plant model (attachPlant() first; attachPlant() alone is a neutral carrier).
@@ -1874,38 +1910,23 @@ class RobotController:
         (depth <= 8); rate_max > 0: the largest change of the torque per second (inf: no limit); tau_lag >= 0: the time constant of a
         first-order lag in seconds (0: none).  The delay line moves once per period (integrate() call or rollout period), the rate limit
         and the lag run every substep.  The chain's state is part of saveState() / restoreState()."""
-        who = "attachActuationChain"
-        t = None if table is None else self._plant_chain_rows(table, per_instance, who)
-        self._call("saip_batch_plant_chain_attach", None if t is None else _dptr(t), int(bool(per_instance)), int(depth))
+        self._chain_attach(self._ACTUATION_CHAIN, table, per_instance, depth)
 
     def detachActuationChain(self):
         self._call("saip_batch_plant_chain_detach")
 
     def actuationChainInfo(self):
         """dict attached, per_instance, depth, state_bytes (device bytes of taps, filt and primed); needs a plant model"""
-        v = [C.c_int(0) for _ in range(3)]
-        nb = C.c_size_t(0)
-        self._call("saip_batch_plant_chain_info", C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(nb))
-        return dict(attached=bool(v[0].value), per_instance=bool(v[1].value), depth=v[2].value, state_bytes=nb.value)
-
-    def _actuation_chain_info(self, who):
-        info = self.actuationChainInfo()
-        if not info["attached"]:
-            raise capi.SaipError(f"{who}: no actuation chain is attached (attachActuationChain)")
-        return info
+        return self._chain_info(self._ACTUATION_CHAIN)
 
     def setActuationChainTable(self, table):
         """replace the chain table (same layout as attached); the state stays (resetActuationChain() starts afresh)"""
-        info = self._actuation_chain_info("setActuationChainTable")
-        a = self._plant_chain_rows(table, info["per_instance"], "setActuationChainTable")
-        self._call("saip_batch_plant_chain_set_table_host", _dptr(a))
+        self._chain_set_table(self._ACTUATION_CHAIN, table)
 
     def actuationChainRandomize(self, seed, round=0, lo=None, hi=None):
         """draw the per-instance chain table on the device between two (dof, 3) tables; lo == hi gives lo exactly (an infinite rate_max
         stays infinite); delay is rounded to the nearest integer and clamped to 0..depth after the draw; reproducible for (seed, round)"""
-        self._actuation_chain_info("actuationChainRandomize")
-        lo, hi = (self._plant_table(x, False, 0, self._robot.dof(), capi.SAIP_PLANT_CHAIN_WORDS, "actuationChainRandomize", "chain bounds") for x in (lo, hi))
-        self._call("saip_batch_plant_chain_randomize", int(seed) & (2**64 - 1), int(round), _dptr(lo), _dptr(hi))
+        self._chain_randomize(self._ACTUATION_CHAIN, "actuationChainRandomize", seed, round, lo, hi)
 
     def resetActuationChain(self):
         """the next period primes the chain again: every tap, x_held and both filters start from that period's command (enqueued, no wait)"""
@@ -1914,18 +1935,12 @@ class RobotController:
     def actuationChainState(self):
         """dict taps (B, dof, depth), filt (B, dof, 3) { x_held, y_rate, y_lag }, primed (B, dof) int (waits for the engine stream): for
         tests and debugging"""
-        info = self._actuation_chain_info("actuationChainState")
-        n, B, d = self._robot.dof(), self.batch_size, info["depth"]
-        taps, filt, primed = np.zeros((n, d, B)), np.empty((n, 3, B)), np.empty((n, B), np.int32)
-        self._call("saip_batch_plant_chain_state_host", _dptr(taps) if d else None, _dptr(filt), primed.ctypes.data_as(C.POINTER(C.c_int)))
-        return dict(taps=np.ascontiguousarray(taps.transpose(2, 0, 1)), filt=np.ascontiguousarray(filt.transpose(2, 0, 1)), primed=np.ascontiguousarray(primed.T))
+        return self._chain_state(self._ACTUATION_CHAIN, "actuationChainState")
 
     def actuationChainStateDevice(self):
         """device pointers (taps, filt, primed) of the state arrays, (depth dof, ld), (3 dof, ld) float64 and (dof, ld) int32; taps is
         None at depth 0"""
-        p = [C.c_void_p() for _ in range(3)]
-        self._call("saip_batch_plant_chain_state_device", C.byref(p[0]), C.byref(p[1]), C.byref(p[2]))
-        return tuple(x.value for x in p)
+        return self._chain_state_device(self._ACTUATION_CHAIN)
 
     def actuationChainTableDevice(self):
         """device pointer of the resident chain table, (dof, 3) or (dof, 3, ld); None when detached"""
@@ -2053,6 +2068,7 @@ class RobotController:
 
     # -- sensing chain: delay line, finite-difference velocity and low-pass behind the sensing model's joint rows; its state is snapshot state
     SENSE_CHAIN_WORDS = ("delay", "vel_mode", "a_q", "a_dq")
+    _SENSING_CHAIN = ("saip_batch_sensing_chain", SENSE_CHAIN_WORDS, (2,), "sensing chain", "SensingChain", {}, 1)
 
     @staticmethod
     def sensingChainAlpha(cutoff_hz, sample_time):
@@ -2067,38 +2083,23 @@ class RobotController:
         over sample_time; a_q, a_dq in [0, 1]: y += a (x - y), 0 for no filter (sensingChainAlpha() from a cutoff).  Every measurement the
         engine takes is one sample: one per state change, one per rollout period, one per measureState().  The chain's state is part of
         saveState() / restoreState()."""
-        who = "attachSensingChain"
-        t = None if table is None else self._sense_rows(table, self.SENSE_CHAIN_WORDS, per_instance, self._robot.dof(), who, "chain table")
-        self._call("saip_batch_sensing_chain_attach", None if t is None else _dptr(t), int(bool(per_instance)), int(depth), float(sample_time))
+        self._chain_attach(self._SENSING_CHAIN, table, per_instance, depth, float(sample_time))
 
     def detachSensingChain(self):
         self._call("saip_batch_sensing_chain_detach")
 
     def sensingChainInfo(self):
         """dict attached, per_instance, depth, sample_time, state_bytes (device bytes of taps, filt and primed); needs a sensing model"""
-        v = [C.c_int(0) for _ in range(3)]
-        T, nb = C.c_double(0), C.c_size_t(0)
-        self._call("saip_batch_sensing_chain_info", C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(T), C.byref(nb))
-        return dict(attached=bool(v[0].value), per_instance=bool(v[1].value), depth=v[2].value, sample_time=T.value, state_bytes=nb.value)
-
-    def _chain_info(self, who):
-        info = self.sensingChainInfo()
-        if not info["attached"]:
-            raise capi.SaipError(f"{who}: no sensing chain is attached (attachSensingChain)")
-        return info
+        return self._chain_info(self._SENSING_CHAIN)
 
     def setSensingChainTable(self, table):
         """replace the chain table (same layout as attached); the state stays (resetSensingChain() starts afresh)"""
-        info = self._chain_info("setSensingChainTable")
-        a = self._sense_rows(table, self.SENSE_CHAIN_WORDS, info["per_instance"], self._robot.dof(), "setSensingChainTable", "chain table")
-        self._call("saip_batch_sensing_chain_set_table_host", _dptr(a))
+        self._chain_set_table(self._SENSING_CHAIN, table)
 
     def sensingChainRandomize(self, seed, round=0, lo=None, hi=None):
         """draw the per-instance chain table on the device between two (dof, 4) tables; delay and vel_mode are rounded to the nearest
         integer and clamped to 0..depth and 0..1 after the draw; reproducible for (seed, round)"""
-        self._chain_info("sensingChainRandomize")
-        lo, hi = (self._plant_table(x, False, 0, self._robot.dof(), capi.SAIP_SENSE_CHAIN_WORDS, "sensingChainRandomize", "chain bounds") for x in (lo, hi))
-        self._call("saip_batch_sensing_chain_randomize", int(seed) & (2**64 - 1), int(round), _dptr(lo), _dptr(hi))
+        self._chain_randomize(self._SENSING_CHAIN, "sensingChainRandomize", seed, round, lo, hi)
 
     def resetSensingChain(self):
         """the next sample primes the chain again: every tap, q_prev and both filters start from that sample (enqueued, no wait)"""
@@ -2107,18 +2108,12 @@ class RobotController:
     def sensingChainState(self):
         """dict taps (B, dof, 2, depth) { q, dq } x tap, filt (B, dof, 3) { q_prev, y_q, y_dq }, primed (B, dof) int (waits for the engine
         stream): for tests and debugging"""
-        info = self._chain_info("sensingChainState")
-        n, B, d = self._robot.dof(), self.batch_size, info["depth"]
-        taps, filt, primed = np.zeros((n, 2, d, B)), np.empty((n, 3, B)), np.empty((n, B), np.int32)
-        self._call("saip_batch_sensing_chain_state_host", _dptr(taps) if d else None, _dptr(filt), primed.ctypes.data_as(C.POINTER(C.c_int)))
-        return dict(taps=np.ascontiguousarray(taps.transpose(3, 0, 1, 2)), filt=np.ascontiguousarray(filt.transpose(2, 0, 1)), primed=np.ascontiguousarray(primed.T))
+        return self._chain_state(self._SENSING_CHAIN, "sensingChainState")
 
     def sensingChainStateDevice(self):
         """device pointers (taps, filt, primed) of the state arrays, (2 depth dof, ld), (3 dof, ld) float64 and (dof, ld) int32; taps is
         None at depth 0"""
-        p = [C.c_void_p() for _ in range(3)]
-        self._call("saip_batch_sensing_chain_state_device", C.byref(p[0]), C.byref(p[1]), C.byref(p[2]))
-        return tuple(x.value for x in p)
+        return self._chain_state_device(self._SENSING_CHAIN)
 
     def sensingChainTableDevice(self):
         """device pointer of the resident chain table, (dof, 4) or (dof, 4, ld); None when detached"""

@@ -50,17 +50,7 @@ saip_status saip::eng::need_controller(const saip_batch* b, const char* fn) {
 	return SAIP_OK;
 }
 // ---- what every resident attachment does with arrays of its own
-// a zeroed device array of `count` doubles; *p stays null when either call fails
-saip_status saip::eng::alloc_zero(saip_batch* b, double** p, size_t count) {
-	HIP_TRY(hipMalloc((void**)p, count * sizeof(double)));
-	const hipError_t e = hipMemsetAsync(*p, 0, count * sizeof(double), b->stream);
-	if (e != hipSuccess) {
-		(void)hipFree(*p);
-		*p = nullptr;
-		return fail(SAIP_ERR_DEVICE, "hipMemsetAsync failed: %s", hipGetErrorString(e));
-	}
-	return SAIP_OK;
-}
+// (alloc_zero, a template, is in the header; *p stays null when either of its calls fails)
 // host [rows] or [rows][B] -> device [rows] or [rows][ld]; `what` names the table in the message ("plane", "obstacle", "table")
 saip_status saip::eng::upload_table(saip_batch* b, double* dev, const double* host, size_t rows, int per_instance, const char* what, const char* fn) {
 	hipError_t e;
@@ -71,6 +61,16 @@ saip_status saip::eng::upload_table(saip_batch* b, double* dev, const double* ho
 	if (e == hipSuccess) e = hipStreamSynchronize(b->stream);  // the host buffer may be reused by the caller right away
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "%s: %s upload failed: %s", fn, what, hipGetErrorString(e));
 	return SAIP_OK;
+}
+saip_status saip::eng::check_bound_infinities(const char* fn, const char* what, size_t unit, const double* lo, const double* hi, int words, const char* const* names) {
+	for (int k = 0; k < words; k++)
+		if (lo[k] != hi[k] && !(std::isfinite(lo[k]) && std::isfinite(hi[k])))
+			return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s %zu: word %s has an infinite bound on one side only", fn, what, unit, names[k]);
+	return SAIP_OK;
+}
+saip_status saip::eng::upload_bound_pair(saip_batch* b, double* dst, const double* lo, const double* hi, size_t rows, const char* fn) {
+	saip_status st = upload_table(b, dst, lo, rows, 0, "table", fn);
+	return st ? st : upload_table(b, dst + rows, hi, rows, 0, "table", fn);
 }
 // the body of the _readout_host and _summary_host entries behind their own need-check, whose result is `st`: device [rows][ld] -> host [rows][B]
 saip_status saip::eng::rows_to_host(saip_batch* b, saip_status st, double* out, const double* dev, int rows, const char* fn) {

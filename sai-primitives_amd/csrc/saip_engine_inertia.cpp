@@ -239,9 +239,7 @@ extern "C" saip_status saip_batch_inertia_randomize(saip_batch* b, unsigned long
 	if (st) return st;
 	const auto& C = b->inertia;
 	const int n = b->model->n, P = C.n_payloads;
-	if ((body_lo == nullptr) != (body_hi == nullptr) || (payload_lo == nullptr) != (payload_hi == nullptr))
-		return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a lower table without its upper table (or the reverse)", fn);
-	if (!body_lo && !payload_lo) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: nothing to draw: both pairs are null", fn);
+	if ((st = check_bound_pairs(fn, body_lo, body_hi, payload_lo, payload_hi))) return st;
 	if (payload_lo && P == 0) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the table was attached without payloads", fn);
 	if (!C.per_instance) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the table is batch-uniform (attach it per instance)", fn);
 	const size_t nb = (size_t)n * INERTIA_BODY_WORDS, np = (size_t)P * INERTIA_PAYLOAD_WORDS;
@@ -255,19 +253,15 @@ extern "C" saip_status saip_batch_inertia_randomize(saip_batch* b, unsigned long
 		neutral_p.assign(np + 1, 0.0);
 		payload_lo = payload_hi = neutral_p.data();
 	}
-	char msg[200];
-	for (const double* t : {body_lo, body_hi})
-		if (!inertia_check_bodies(b->model, t, 1, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s bound: %s", fn, t == body_lo ? "lower" : "upper", msg);
-	for (const double* t : {payload_lo, payload_hi})
-		if (!inertia_check_payloads(t, P, 1, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s bound: %s", fn, t == payload_lo ? "lower" : "upper", msg);
-	if ((st = need_ready(b, fn))) return st;
+	// every word of both tables has to be finite: nothing to scan for a bound infinite on one side only
+	if ((st = check_bound_pair(fn, body_lo, body_hi, [&](const double* t, char* msg, size_t len) { return inertia_check_bodies(b->model, t, 1, msg, len); })) ||
+		(st = check_bound_pair(fn, payload_lo, payload_hi, [&](const double* t, char* msg, size_t len) { return inertia_check_payloads(t, P, 1, msg, len); })) || (st = need_ready(b, fn)))
+		return st;
 	double* bl = C.bounds;
 	double* bh = bl + nb;
 	double* pl = bh + nb;
 	double* ph = pl + np;
-	if ((st = upload_table(b, bl, body_lo, nb, 0, "table", fn)) || (st = upload_table(b, bh, body_hi, nb, 0, "table", fn)) ||
-		(P > 0 && ((st = upload_table(b, pl, payload_lo, np, 0, "table", fn)) || (st = upload_table(b, ph, payload_hi, np, 0, "table", fn)))))
-		return st;
+	if ((st = upload_bound_pair(b, bl, body_lo, body_hi, nb, fn)) || (P > 0 && (st = upload_bound_pair(b, pl, payload_lo, payload_hi, np, fn)))) return st;
 	InertiaComposeParams K;
 	memset(&K, 0, sizeof(K));
 	K.draw = 1;

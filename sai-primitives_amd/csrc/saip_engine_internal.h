@@ -224,6 +224,18 @@ struct saip_batch {
 		double* summary = nullptr;           // [4][ld]
 		double* centres = nullptr;           // [3 S][ld], keep_centres only
 	} clearance;
+	// The optional second stage of the sensing model and of the plant model: per joint a delay line and filters, W words per joint (a
+	// ChainKind below says which).  The only attachments with state: taps, filt and primed are on the snapshot directory while attached;
+	// the table is configuration.  Nothing of a chain lives in a host scalar but the sensing chain's sample time, which its carrier keeps.
+	struct Chain {
+		bool attached = false;
+		int per_instance = 0, depth = 0;
+		double* table = nullptr;             // [n][W] (batch-uniform) or [n][W][ld]
+		double* taps = nullptr;              // [n][tap_rows][depth][ld] (nullptr at depth 0)
+		double* filt = nullptr;              // [n][filt_rows][ld]: q_prev, y_q, y_dq (sensing); x_held, y_rate, y_lag (actuation)
+		int* primed = nullptr;               // [n][ld]
+		double* bounds = nullptr;            // lo [n][W], hi of the chain's _randomize (per-instance table only)
+	};
 	// saip_batch_plant_attach: the plant model of the resident simulator (saip_plant.hip), at most one per batch: actuator limits, friction,
 	// joint stops and external wrenches in front of every integration substep.  Nothing in it but the `chain` sub-block is state: its
 	// arrays are configuration, scratch and summaries, its own (freed by _detach), not part of `allocs` or of a snapshot; `period` is a
@@ -238,19 +250,7 @@ struct saip_batch {
 		double* tau_act = nullptr;           // [n][ld] what the actuators, friction, stops and wrenches make of the commanded torques
 		double* summary = nullptr;           // [4][ld]
 		double* bounds = nullptr;            // joint lo [n][10], joint hi, wrench lo [W][8], wrench hi of saip_batch_plant_randomize (per-instance tables only)
-		// saip_batch_plant_chain_attach: the actuation chain (saip_plant_chain.h), the optional second stage: per joint a delay line, a
-		// slew-rate limit and a first-order lag between the commanded torque and pl_joint.  Like the sensing chain it has state: taps, filt
-		// and primed are on the snapshot directory (plant.chain.*) while attached; the table is configuration.  Nothing of the chain lives
-		// in a host scalar.
-		struct Chain {
-			bool attached = false;
-			int per_instance = 0, depth = 0;
-			double* table = nullptr;         // [n][3] (batch-uniform) or [n][3][ld]
-			double* taps = nullptr;          // [n][depth][ld] (nullptr at depth 0)
-			double* filt = nullptr;          // [n][3][ld] x_held, y_rate, y_lag
-			int* primed = nullptr;           // [n][ld]
-			double* bounds = nullptr;        // lo [n][3], hi of saip_batch_plant_chain_randomize (per-instance table only)
-		} chain;
+		Chain chain;                         // saip_batch_plant_chain_attach: the actuation chain (saip_plant_chain.h), snapshot segments plant.chain.*
 	} plant;
 	// saip_batch_inertia_attach: the inertial parameters of the simulated robot (saip_inertia.hip), at most one per batch: the table the
 	// resident integrator reads in place of the model's masses, centres of mass and inertias.  Configuration only: its arrays are its own
@@ -279,19 +279,8 @@ struct saip_batch {
 		double* q_meas = nullptr;            // [n][ld] what every non-diagnostic cycle, per-task and OTG launch reads in place of q
 		double* dq_meas = nullptr;           // [n][ld]
 		double* bounds = nullptr;            // joint lo [n][6], joint hi, wrench lo [S][18], wrench hi of saip_batch_sensing_randomize
-		// saip_batch_sensing_chain_attach: the sensing chain (saip_sense_chain.hip), the optional second stage: delay line, finite-difference
-		// velocity and low-pass per joint.  The first attachment with state: taps, filt and primed are on the snapshot directory
-		// (sense.chain.*) while attached; the table is configuration.  Nothing of the chain lives in a host scalar.
-		struct Chain {
-			bool attached = false;
-			int per_instance = 0, depth = 0;
-			double sample_time = 0;
-			double* table = nullptr;         // [n][4] (batch-uniform) or [n][4][ld]
-			double* taps = nullptr;          // [n][2][depth][ld] (nullptr at depth 0)
-			double* filt = nullptr;          // [n][3][ld] q_prev, y_q, y_dq
-			int* primed = nullptr;           // [n][ld]
-			double* bounds = nullptr;        // lo [n][4], hi of saip_batch_sensing_chain_randomize (per-instance table only)
-		} chain;
+		Chain chain;                         // saip_batch_sensing_chain_attach: the sensing chain (saip_sense_chain.hip), snapshot segments sense.chain.*
+		double chain_sample_time = 0;        // what its finite-difference velocity divides by; 0 while no chain is attached
 	} sensing;
 };
 
@@ -324,9 +313,40 @@ saip_status dev_alloc(saip_batch* b, Tp** p, size_t count) {
 	*p = (Tp*)v;
 	return SAIP_OK;
 }
-// the plumbing every attachment uses on arrays of its own (not part of `allocs`)
-saip_status alloc_zero(saip_batch* b, double** p, size_t count);
 saip_status upload_table(saip_batch* b, double* dev, const double* host, size_t rows, int per_instance, const char* what, const char* fn);
+// the plumbing every attachment uses on arrays of its own (not part of `allocs`): count elements, zeroed on the batch's stream
+template <typename Tp>
+saip_status alloc_zero(saip_batch* b, Tp** p, size_t count) {
+	HIP_TRY(hipMalloc((void**)p, count * sizeof(Tp)));
+	const hipError_t e = hipMemsetAsync(*p, 0, count * sizeof(Tp), b->stream);
+	if (e != hipSuccess) {
+		(void)hipFree(*p);
+		*p = nullptr;
+		return fail(SAIP_ERR_DEVICE, "hipMemsetAsync failed: %s", hipGetErrorString(e));
+	}
+	return SAIP_OK;
+}
+// The two bound tables of a _randomize entry that draws per-instance tables between them.  The entries share the order: pairing, the
+// attachment's own conditions, every pair checked, need_ready, every pair uploaded.
+// ... either pair may be absent, but whole and not both
+inline saip_status check_bound_pairs(const char* fn, const double* lo_a, const double* hi_a, const double* lo_b, const double* hi_b) {
+	if ((lo_a == nullptr) != (hi_a == nullptr) || (lo_b == nullptr) != (hi_b == nullptr))
+		return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a lower table without its upper table (or the reverse)", fn);
+	if (!lo_a && !lo_b) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: nothing to draw: both pairs are null", fn);
+	return SAIP_OK;
+}
+// ... both bounds pass the table's checker `bool check(const double* table, char* msg, size_t len)`
+template <typename Check>
+saip_status check_bound_pair(const char* fn, const double* lo, const double* hi, Check check) {
+	char msg[200];
+	for (const double* t : {lo, hi})
+		if (!check(t, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s bound: %s", fn, t == lo ? "lower" : "upper", msg);
+	return SAIP_OK;
+}
+// ... where a word may be infinite: the `words` words of one unit ("joint 3", "wrench 0") differ between the bounds only where both are finite
+saip_status check_bound_infinities(const char* fn, const char* what, size_t unit, const double* lo, const double* hi, int words, const char* const* names);
+// ... lo then hi, [rows] each, to dst
+saip_status upload_bound_pair(saip_batch* b, double* dst, const double* lo, const double* hi, size_t rows, const char* fn);
 saip_status rows_to_host(saip_batch* b, saip_status st, double* out, const double* dev, int rows, const char* fn);
 saip_status zero_rows(saip_batch* b, double* dev, int rows);
 saip_status ensure_lazy_state(saip_batch* b);
@@ -349,15 +369,41 @@ bool patch_any_sensor(const saip_batch* b);
 // ---- saip_engine_clearance.cpp
 void clearance_free(saip_batch* b);
 saip_status clearance_launch(saip_batch* b, int mode, double dt);
+// ---- saip_engine_chain.cpp: the host side of a chain (saip_batch::Chain), written once.  What differs between the two is a ChainKind;
+// the extern "C" entries stay with the carriers (saip_engine_sensing.cpp, saip_engine_plant.cpp), which pick the struct and the kind
+struct ChainKind {
+	int words, filt_rows, tap_rows, max_depth;  // words per joint; taps is [n][tap_rows][depth][ld]
+	const char* const* names;                   // of the words
+	const double* neutral;                      // the row a null table stands for
+	const char *article, *noun, *entry;         // "a", "sensing chain", "saip_batch_sensing_chain": the messages' vocabulary
+	const char *carrier, *carrier_hint;         // "sensing model", and what the attach entry says when it is missing
+	const char* snapshot;                       // prefix of the snapshot segments
+	bool scan_infinities;                       // _randomize refuses a word that is infinite in one bound only
+	// one word that is not NaN: nullptr when fine, else what is wrong with it, rendered into buf.  bounds: the two tables of a draw, whose
+	// integer words are rounded and clamped afterwards and only have to be finite
+	const char* (*rule)(int k, double v, const char* name, int depth, bool bounds, char* buf, size_t len);
+};
+const ChainKind& sense_chain_kind();  // functions: a constant object with host function pointers would be emitted for the device as well
+const ChainKind& plant_chain_kind();
+using Chain = saip_batch::Chain;
+void chain_free(Chain& H);
+saip_status chain_need(const ChainKind& K, const Chain& H, const char* fn);  // behind the carrier's own need-check
+saip_status chain_attach_depth(const ChainKind& K, const saip_batch* b, int depth, const char* fn);  // attach, first half: need_controller and the depth
+saip_status chain_attach(const ChainKind& K, saip_batch* b, Chain& H, bool carrier_attached, const double* table, int per_instance, int depth, const char* fn);
+saip_status chain_detach(saip_batch* b, Chain& H, const char* fn);
+void chain_info(const ChainKind& K, const saip_batch* b, const Chain& H, int* attached, int* per_instance, int* depth, size_t* state_bytes);
+saip_status chain_set_table(const ChainKind& K, saip_batch* b, Chain& H, const double* table, const char* fn);
+saip_status chain_randomize_bounds(const ChainKind& K, saip_batch* b, Chain& H, const double* lo, const double* hi, const char* fn);  // all of _randomize but the launch
+saip_status chain_reset(saip_batch* b, Chain& H, const char* fn);
+saip_status chain_state_device(const Chain& H, double** taps, double** filt, int** primed);
+saip_status chain_state_host(const ChainKind& K, saip_batch* b, const Chain& H, double* taps, double* filt, int* primed, const char* fn);
 // ---- saip_engine_plant.cpp
 void plant_free(saip_batch* b);
-void plant_chain_free(saip_batch* b);
 saip_status plant_launch(saip_batch* b, double dt, int substep);
 // ---- saip_engine_inertia.cpp
 void inertia_free(saip_batch* b);
 // ---- saip_engine_sensing.cpp
 void sensing_free(saip_batch* b);
-void sensing_chain_free(saip_batch* b);
 int sensing_sensor_slots(const saip_batch* b, bool planes, bool patches);
 saip_status sensing_launch(saip_batch* b, int mode, int slot_mask);
 saip_status sensing_refresh(saip_batch* b);

@@ -7,15 +7,9 @@ static saip_status need_plant(const saip_batch* b, const char* fn) {
 	if (!b->plant.attached) return fail(SAIP_ERR_ORDER, "%s: no plant model is attached (saip_batch_plant_attach)", fn);
 	return SAIP_OK;
 }
-void saip::eng::plant_chain_free(saip_batch* b) {
-	auto& H = b->plant.chain;
-	for (void* p : {(void*)H.table, (void*)H.taps, (void*)H.filt, (void*)H.primed, (void*)H.bounds})
-		if (p) (void)hipFree(p);
-	H = saip_batch::Plant::Chain();
-}
 void saip::eng::plant_free(saip_batch* b) {
 	auto& C = b->plant;
-	plant_chain_free(b);  // the chain goes with its carrier
+	chain_free(C.chain);  // the chain goes with its carrier
 	for (void* p : {(void*)C.joints, (void*)C.wrenches, (void*)C.tau_act, (void*)C.summary, (void*)C.bounds})
 		if (p) (void)hipFree(p);
 	C = saip_batch::Plant();
@@ -186,21 +180,15 @@ extern "C" saip_status saip_batch_plant_randomize(saip_batch* b, unsigned long l
 	if (st) return st;
 	const auto& C = b->plant;
 	const int n = b->model->n, W = C.n_wrenches;
-	if ((joint_lo == nullptr) != (joint_hi == nullptr) || (wrench_lo == nullptr) != (wrench_hi == nullptr))
-		return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a lower table without its upper table (or the reverse)", fn);
-	if (!joint_lo && !wrench_lo) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: nothing to draw: both pairs are null", fn);
+	if ((st = check_bound_pairs(fn, joint_lo, joint_hi, wrench_lo, wrench_hi))) return st;
 	if (joint_lo && !C.per_instance_joints) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the joint table is batch-uniform (attach it per instance)", fn);
 	if (wrench_lo && (W == 0 || !C.per_instance_wrenches)) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the wrench table is batch-uniform or empty (attach it per instance)", fn);
-	char msg[200];
 	const size_t jrows = (size_t)n * PLANT_JOINT_WORDS, wrows = (size_t)W * PLANT_WRENCH_WORDS;
 	if (joint_lo) {
-		for (const double* t : {joint_lo, joint_hi})
-			if (!plant_check_joints(t, n, 1, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s bound: %s", fn, t == joint_lo ? "lower" : "upper", msg);
+		if ((st = check_bound_pair(fn, joint_lo, joint_hi, [&](const double* t, char* msg, size_t len) { return plant_check_joints(t, n, 1, msg, len); }))) return st;
 		for (int j = 0; j < n; j++) {
 			const double *l = joint_lo + (size_t)j * PLANT_JOINT_WORDS, *h = joint_hi + (size_t)j * PLANT_JOINT_WORDS;
-			for (int k = 0; k < PLANT_JOINT_WORDS; k++)
-				if (l[k] != h[k] && !(std::isfinite(l[k]) && std::isfinite(h[k])))
-					return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: joint %d: word %s has an infinite bound on one side only", fn, j, PLANT_JOINT_WORD_NAMES[k]);
+			if ((st = check_bound_infinities(fn, "joint", j, l, h, PLANT_JOINT_WORDS, PLANT_JOINT_WORD_NAMES))) return st;
 			if (std::max(l[PLANT_Q_LO], h[PLANT_Q_LO]) > std::min(l[PLANT_Q_HI], h[PLANT_Q_HI]))
 				return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: joint %d: the ranges of words q_lo and q_hi overlap", fn, j);
 			if (std::max(l[PLANT_FC], h[PLANT_FC]) > 0 && !(std::min(l[PLANT_VS], h[PLANT_VS]) > 0))
@@ -208,11 +196,10 @@ extern "C" saip_status saip_batch_plant_randomize(saip_batch* b, unsigned long l
 		}
 	}
 	if (wrench_lo) {
-		for (const double* t : {wrench_lo, wrench_hi})
-			if (!plant_check_wrenches(t, W, 1, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s bound: %s", fn, t == wrench_lo ? "lower" : "upper", msg);
-		for (size_t k = 0; k < wrows; k++)
-			if (wrench_lo[k] != wrench_hi[k] && !(std::isfinite(wrench_lo[k]) && std::isfinite(wrench_hi[k])))
-				return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: wrench %zu: word %s has an infinite bound on one side only", fn, k / PLANT_WRENCH_WORDS, PLANT_WRENCH_WORD_NAMES[k % PLANT_WRENCH_WORDS]);
+		if ((st = check_bound_pair(fn, wrench_lo, wrench_hi, [&](const double* t, char* msg, size_t len) { return plant_check_wrenches(t, W, 1, msg, len); }))) return st;
+		for (int k = 0; k < W; k++)
+			if ((st = check_bound_infinities(fn, "wrench", k, wrench_lo + (size_t)k * PLANT_WRENCH_WORDS, wrench_hi + (size_t)k * PLANT_WRENCH_WORDS, PLANT_WRENCH_WORDS, PLANT_WRENCH_WORD_NAMES)))
+				return st;
 	}
 	if ((st = need_ready(b, fn))) return st;
 	PlantRandomParams P;
@@ -227,13 +214,13 @@ extern "C" saip_status saip_batch_plant_randomize(saip_batch* b, unsigned long l
 	double* jb = C.bounds;
 	double* wb = C.bounds + 2 * jrows;
 	if (joint_lo) {
-		if ((st = upload_table(b, jb, joint_lo, jrows, 0, "table", fn)) || (st = upload_table(b, jb + jrows, joint_hi, jrows, 0, "table", fn))) return st;
+		if ((st = upload_bound_pair(b, jb, joint_lo, joint_hi, jrows, fn))) return st;
 		P.joints = C.joints;
 		P.joint_lo = jb;
 		P.joint_hi = jb + jrows;
 	}
 	if (wrench_lo) {
-		if ((st = upload_table(b, wb, wrench_lo, wrows, 0, "table", fn)) || (st = upload_table(b, wb + wrows, wrench_hi, wrows, 0, "table", fn))) return st;
+		if ((st = upload_bound_pair(b, wb, wrench_lo, wrench_hi, wrows, fn))) return st;
 		P.wrenches = C.wrenches;
 		P.wrench_lo = wb;
 		P.wrench_hi = wb + wrows;
@@ -306,178 +293,69 @@ saip_status saip::eng::plant_launch(saip_batch* b, double dt, int substep) {
 	return SAIP_OK;
 }
 
-// ---- the actuation chain (saip_plant_chain.h): delay line, slew-rate limit and first-order lag in front of the plant's joint rows.  Its
-// state (taps, filt, primed) is on the snapshot directory while attached (saip_engine_snapshot.cpp).
+// ---- the actuation chain (saip_plant_chain.h): delay line, slew-rate limit and first-order lag in front of the plant's joint rows.  The
+// host side is saip_engine_chain.cpp's; nothing but the draw's parameters is its own here.
 static saip_status need_plant_chain(const saip_batch* b, const char* fn) {
 	saip_status st = need_plant(b, fn);
-	if (st) return st;
-	if (!b->plant.chain.attached) return fail(SAIP_ERR_ORDER, "%s: no actuation chain is attached (saip_batch_plant_chain_attach)", fn);
-	return SAIP_OK;
-}
-static const char* const PLANT_CHAIN_WORD_NAMES[saip::PLANT_CHAIN_WORDS] = {"delay", "rate_max", "tau_lag"};
-// a chain table [n][3] (cols = 1) or [n][3][cols]: true when fine, else msg names the joint and the word (and the instance).  bounds: the
-// two tables of a draw, whose delay is rounded and clamped afterwards and only has to be finite
-static bool plant_chain_check_table(const double* t, int n, size_t cols, int depth, bool bounds, char* msg, size_t len) {
-	using namespace saip;
-	char buf[96];
-	for (int j = 0; j < n; j++)
-		for (size_t i = 0; i < cols; i++)
-			for (int k = 0; k < PLANT_CHAIN_WORDS; k++) {
-				const double v = t[((size_t)j * PLANT_CHAIN_WORDS + k) * cols + i];
-				const char* name = PLANT_CHAIN_WORD_NAMES[k];
-				buf[0] = 0;
-				if (v != v) snprintf(buf, sizeof(buf), "word %s is NaN", name);
-				else if (k != PLANT_CHAIN_RATE_MAX && !std::isfinite(v)) snprintf(buf, sizeof(buf), "word %s is not finite", name);
-				else if (k == PLANT_CHAIN_DELAY && !bounds && (v != std::floor(v) || v < 0 || v > depth))
-					snprintf(buf, sizeof(buf), "word %s = %g is not an integer in 0..%d", name, v, depth);
-				else if (k == PLANT_CHAIN_RATE_MAX && !(v > 0)) snprintf(buf, sizeof(buf), "word %s = %g is not above 0", name, v);
-				else if (k == PLANT_CHAIN_TAU_LAG && v < 0) snprintf(buf, sizeof(buf), "word %s = %g is below 0", name, v);
-				if (!buf[0]) continue;
-				if (cols > 1) snprintf(msg, len, "joint %d of instance %zu: %s", j, i, buf);
-				else snprintf(msg, len, "joint %d: %s", j, buf);
-				return false;
-			}
-	return true;
-}
-static size_t plant_chain_state_bytes(const saip_batch* b, int depth) {
-	const size_t n = b->model->n, ld = b->ld;
-	return ((size_t)depth * n + saip::PLANT_CHAIN_FILT_ROWS * n) * ld * sizeof(double) + n * ld * sizeof(int);
+	return st ? st : chain_need(plant_chain_kind(), b->plant.chain, fn);
 }
 extern "C" saip_status saip_batch_plant_chain_attach(saip_batch* b, const double* table, int per_instance, int depth) {
 	const char* fn = "saip_batch_plant_chain_attach";
-	saip_status st = need_controller(b, fn);
-	if (st) return st;
-	const int n = b->model->n;
-	// the arguments first (nothing here needs the plant model or the device), then the call order
-	if (depth < 0 || depth > saip::PLANT_CHAIN_MAX_DEPTH) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a depth of 0..%d required (got %d)", fn, saip::PLANT_CHAIN_MAX_DEPTH, depth);
-	per_instance = per_instance ? 1 : 0;
-	const size_t cols = per_instance ? (size_t)b->B : 1;
-	std::vector<double> neutral;
-	if (!table) {
-		neutral.assign((size_t)n * saip::PLANT_CHAIN_WORDS * cols, 0.0);
-		for (int j = 0; j < n; j++)
-			for (size_t i = 0; i < cols; i++) neutral[((size_t)j * saip::PLANT_CHAIN_WORDS + saip::PLANT_CHAIN_RATE_MAX) * cols + i] = INFINITY;
-		table = neutral.data();
-	}
-	char msg[200];
-	if (!plant_chain_check_table(table, n, cols, depth, false, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, msg);
-	if (!b->plant.attached) return fail(SAIP_ERR_ORDER, "%s: no plant model is attached (saip_batch_plant_attach; an all-neutral table is a valid carrier)", fn);
-	if (b->plant.chain.attached) return fail(SAIP_ERR_ORDER, "%s: an actuation chain is already attached (saip_batch_plant_chain_detach first)", fn);
-	if ((st = need_ready(b, fn))) return st;
-	auto& H = b->plant.chain;
-	H = saip_batch::Plant::Chain();
-	const size_t ld = b->ld, rows = (size_t)n * saip::PLANT_CHAIN_WORDS;
-	double* primed = nullptr;
-	if ((st = alloc_zero(b, &H.table, rows * (per_instance ? ld : 1))) || (depth > 0 && (st = alloc_zero(b, &H.taps, (size_t)depth * n * ld))) ||
-		(st = alloc_zero(b, &H.filt, (size_t)saip::PLANT_CHAIN_FILT_ROWS * n * ld)) || (st = alloc_zero(b, &primed, ((size_t)n * ld + 1) / 2)) ||
-		(per_instance && (st = alloc_zero(b, &H.bounds, 2 * rows))) || (st = upload_table(b, H.table, table, rows, per_instance, "table", fn))) {
-		if (primed) (void)hipFree(primed);
-		plant_chain_free(b);
-		return st;
-	}
-	H.primed = (int*)primed;  // n ld 32-bit flags, zeroed
-	H.attached = true;
-	H.per_instance = per_instance;
-	H.depth = depth;
-	return SAIP_OK;
+	saip_status st = chain_attach_depth(plant_chain_kind(), b, depth, fn);
+	return st ? st : chain_attach(plant_chain_kind(), b, b->plant.chain, b->plant.attached, table, per_instance, depth, fn);
 }
 extern "C" saip_status saip_batch_plant_chain_detach(saip_batch* b) {
 	const char* fn = "saip_batch_plant_chain_detach";
 	saip_status st = need_plant_chain(b, fn);
-	if (st || (st = need_ready(b, fn))) return st;
-	HIP_TRY(hipStreamSynchronize(b->stream));  // a plant substep that writes the chain's state may still be in flight
-	plant_chain_free(b);
-	return SAIP_OK;
+	return st ? st : chain_detach(b, b->plant.chain, fn);
 }
 extern "C" saip_status saip_batch_plant_chain_info(saip_batch* b, int* attached, int* per_instance, int* depth, size_t* state_bytes) {
 	saip_status st = need_plant(b, "saip_batch_plant_chain_info");
 	if (st) return st;
-	const auto& H = b->plant.chain;
-	if (attached) *attached = H.attached ? 1 : 0;
-	if (per_instance) *per_instance = H.per_instance;
-	if (depth) *depth = H.depth;
-	if (state_bytes) *state_bytes = H.attached ? plant_chain_state_bytes(b, H.depth) : 0;
+	chain_info(plant_chain_kind(), b, b->plant.chain, attached, per_instance, depth, state_bytes);
 	return SAIP_OK;
 }
 extern "C" saip_status saip_batch_plant_chain_set_table_host(saip_batch* b, const double* table) {
 	const char* fn = "saip_batch_plant_chain_set_table_host";
 	saip_status st = need_plant_chain(b, fn);
-	if (st) return st;
-	if (!table) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null table", fn);
-	auto& H = b->plant.chain;
-	char msg[200];
-	if (!plant_chain_check_table(table, b->model->n, H.per_instance ? (size_t)b->B : 1, H.depth, false, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, msg);
-	if ((st = need_ready(b, fn))) return st;
-	// the state stays: the next substep runs the new words over the history there is (saip_batch_plant_chain_reset starts afresh)
-	return upload_table(b, H.table, table, (size_t)b->model->n * saip::PLANT_CHAIN_WORDS, H.per_instance, "table", fn);
+	return st ? st : chain_set_table(plant_chain_kind(), b, b->plant.chain, table, fn);
 }
-// The per-instance table drawn on the device between two batch-uniform tables [n][3] (host pointers).  rate_max and tau_lag of both bounds
-// have to be valid words, an infinite rate_max on both sides or on neither; delay only finite: the draw is rounded to the nearest integer
-// and clamped to its range.
+// rate_max and tau_lag of both bounds have to be valid words, an infinite rate_max on both sides or on neither; delay only finite: the
+// draw is rounded to the nearest integer and clamped to its range
 extern "C" saip_status saip_batch_plant_chain_randomize(saip_batch* b, unsigned long long seed, long long round, const double* lo, const double* hi) {
 	const char* fn = "saip_batch_plant_chain_randomize";
 	saip_status st = need_plant_chain(b, fn);
-	if (st) return st;
-	auto& H = b->plant.chain;
-	const int n = b->model->n;
-	if (!lo || !hi) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null bounds", fn);
-	if (!H.per_instance) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the chain table is batch-uniform (attach it per instance)", fn);
-	char msg[200];
-	for (const double* t : {lo, hi})
-		if (!plant_chain_check_table(t, n, 1, H.depth, true, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s bound: %s", fn, t == lo ? "lower" : "upper", msg);
-	const size_t rows = (size_t)n * saip::PLANT_CHAIN_WORDS;
-	for (size_t k = 0; k < rows; k++)
-		if (lo[k] != hi[k] && !(std::isfinite(lo[k]) && std::isfinite(hi[k])))
-			return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: joint %zu: word %s has an infinite bound on one side only", fn, k / saip::PLANT_CHAIN_WORDS, PLANT_CHAIN_WORD_NAMES[k % saip::PLANT_CHAIN_WORDS]);
-	if ((st = need_ready(b, fn))) return st;
-	if ((st = upload_table(b, H.bounds, lo, rows, 0, "table", fn)) || (st = upload_table(b, H.bounds + rows, hi, rows, 0, "table", fn))) return st;
+	if (st || (st = chain_randomize_bounds(plant_chain_kind(), b, b->plant.chain, lo, hi, fn))) return st;
+	const auto& H = b->plant.chain;
 	saip::PlantChainRandomParams P;
 	memset(&P, 0, sizeof(P));
 	P.B = b->B;
 	P.ld = b->ld;
-	P.n = n;
+	P.n = b->model->n;
 	P.depth = H.depth;
 	P.seed_lo = (uint32_t)seed;
 	P.seed_hi = (uint32_t)(seed >> 32);
 	P.round = (uint32_t)round;
 	P.table = H.table;
 	P.lo = H.bounds;
-	P.hi = H.bounds + rows;
+	P.hi = H.bounds + (size_t)P.n * saip::PLANT_CHAIN_WORDS;
 	hipError_t e = saip::launch_plant_chain_randomize(P, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "actuation chain randomize launch failed: %s", hipGetErrorString(e));
 	return SAIP_OK;
 }
-// primed cleared on the stream, without a synchronisation: the next period's first substep primes every (joint, instance) again
 extern "C" saip_status saip_batch_plant_chain_reset(saip_batch* b) {
 	const char* fn = "saip_batch_plant_chain_reset";
 	saip_status st = need_plant_chain(b, fn);
-	if (st || (st = need_ready(b, fn))) return st;
-	HIP_TRY(hipMemsetAsync(b->plant.chain.primed, 0, (size_t)b->model->n * b->ld * sizeof(int), b->stream));
-	return SAIP_OK;
+	return st ? st : chain_reset(b, b->plant.chain, fn);
 }
 extern "C" double* saip_batch_plant_chain_table_device(saip_batch* b) { return b ? b->plant.chain.table : nullptr; }
-// the state arrays themselves, [rows][ld] (taps null at depth 0); any output may be null
 extern "C" saip_status saip_batch_plant_chain_state_device(saip_batch* b, double** taps, double** filt, int** primed) {
 	saip_status st = need_plant_chain(b, "saip_batch_plant_chain_state_device");
-	if (st) return st;
-	const auto& H = b->plant.chain;
-	if (taps) *taps = H.taps;
-	if (filt) *filt = H.filt;
-	if (primed) *primed = H.primed;
-	return SAIP_OK;
+	return st ? st : chain_state_device(b->plant.chain, taps, filt, primed);
 }
-// the state for tests and debugging: taps [n][depth][B], filt [n][3][B], primed [n][B]; any may be null
 extern "C" saip_status saip_batch_plant_chain_state_host(saip_batch* b, double* taps, double* filt, int* primed) {
 	const char* fn = "saip_batch_plant_chain_state_host";
 	saip_status st = need_plant_chain(b, fn);
-	if (st || (st = need_ready(b, fn))) return st;
-	const auto& H = b->plant.chain;
-	const int n = b->model->n;
-	if (taps && H.depth > 0 && (st = copy_d2h(b, taps, H.taps, H.depth * n))) return st;
-	if (filt && (st = copy_d2h(b, filt, H.filt, saip::PLANT_CHAIN_FILT_ROWS * n))) return st;
-	if (primed) {
-		HIP_TRY(hipMemcpy2DAsync(primed, (size_t)b->B * sizeof(int), H.primed, (size_t)b->ld * sizeof(int), (size_t)b->B * sizeof(int), n, hipMemcpyDeviceToHost, b->stream));
-		HIP_TRY(hipStreamSynchronize(b->stream));
-	}
-	return SAIP_OK;
+	return st ? st : chain_state_host(plant_chain_kind(), b, b->plant.chain, taps, filt, primed, fn);
 }
+

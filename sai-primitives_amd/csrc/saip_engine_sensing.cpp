@@ -7,15 +7,9 @@ static saip_status need_sensing(const saip_batch* b, const char* fn) {
 	if (!b->sensing.attached) return fail(SAIP_ERR_ORDER, "%s: no sensing model is attached (saip_batch_sensing_attach)", fn);
 	return SAIP_OK;
 }
-void saip::eng::sensing_chain_free(saip_batch* b) {
-	auto& H = b->sensing.chain;
-	for (void* p : {(void*)H.table, (void*)H.taps, (void*)H.filt, (void*)H.primed, (void*)H.bounds})
-		if (p) (void)hipFree(p);
-	H = saip_batch::Sensing::Chain();
-}
 void saip::eng::sensing_free(saip_batch* b) {
 	auto& C = b->sensing;
-	sensing_chain_free(b);  // the chain goes with its carrier
+	chain_free(C.chain);  // the chain goes with its carrier
 	for (void* p : {(void*)C.joints, (void*)C.wrenches, (void*)C.q_meas, (void*)C.dq_meas, (void*)C.bounds})
 		if (p) (void)hipFree(p);
 	C = saip_batch::Sensing();
@@ -182,19 +176,14 @@ extern "C" saip_status saip_batch_sensing_randomize(saip_batch* b, unsigned long
 	if (st) return st;
 	auto& C = b->sensing;
 	const int n = b->model->n, S = C.n_wrench_tasks;
-	if ((joint_lo == nullptr) != (joint_hi == nullptr) || (wrench_lo == nullptr) != (wrench_hi == nullptr))
-		return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a lower table without its upper table (or the reverse)", fn);
-	if (!joint_lo && !wrench_lo) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: nothing to draw: both pairs are null", fn);
+	if ((st = check_bound_pairs(fn, joint_lo, joint_hi, wrench_lo, wrench_hi))) return st;
 	if (joint_lo && !C.per_instance_joints) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the joint table is batch-uniform (attach it per instance)", fn);
 	if (wrench_lo && (S == 0 || !C.per_instance_wrenches)) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the wrench tables are batch-uniform or empty (attach them per instance)", fn);
-	char msg[200];
 	const size_t jrows = (size_t)n * SENSE_JOINT_WORDS, wrows = (size_t)S * SENSE_WRENCH_WORDS;
-	if (joint_lo)
-		for (const double* t : {joint_lo, joint_hi})
-			if (!sense_check_joints(t, n, 1, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s bound: %s", fn, t == joint_lo ? "lower" : "upper", msg);
-	if (wrench_lo)
-		for (const double* t : {wrench_lo, wrench_hi})
-			if (!sense_check_wrenches(t, S, C.task, 1, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s bound: %s", fn, t == wrench_lo ? "lower" : "upper", msg);
+	// no word of either table may be infinite: nothing to scan for a bound infinite on one side only
+	if (joint_lo && (st = check_bound_pair(fn, joint_lo, joint_hi, [&](const double* t, char* msg, size_t len) { return sense_check_joints(t, n, 1, msg, len); }))) return st;
+	if (wrench_lo && (st = check_bound_pair(fn, wrench_lo, wrench_hi, [&](const double* t, char* msg, size_t len) { return sense_check_wrenches(t, S, C.task, 1, msg, len); })))
+		return st;
 	if ((st = need_ready(b, fn))) return st;
 	SenseRandomParams P;
 	memset(&P, 0, sizeof(P));
@@ -208,13 +197,13 @@ extern "C" saip_status saip_batch_sensing_randomize(saip_batch* b, unsigned long
 	double* jb = C.bounds;
 	double* wb = C.bounds + 2 * jrows;
 	if (joint_lo) {
-		if ((st = upload_table(b, jb, joint_lo, jrows, 0, "table", fn)) || (st = upload_table(b, jb + jrows, joint_hi, jrows, 0, "table", fn))) return st;
+		if ((st = upload_bound_pair(b, jb, joint_lo, joint_hi, jrows, fn))) return st;
 		P.joints = C.joints;
 		P.joint_lo = jb;
 		P.joint_hi = jb + jrows;
 	}
 	if (wrench_lo) {
-		if ((st = upload_table(b, wb, wrench_lo, wrows, 0, "table", fn)) || (st = upload_table(b, wb + wrows, wrench_hi, wrows, 0, "table", fn))) return st;
+		if ((st = upload_bound_pair(b, wb, wrench_lo, wrench_hi, wrows, fn))) return st;
 		P.wrenches = C.wrenches;
 		P.wrench_lo = wb;
 		P.wrench_hi = wb + wrows;
@@ -288,7 +277,7 @@ saip_status saip::eng::sensing_launch(saip_batch* b, int mode, int slot_mask) {
 		Q.S = P;
 		Q.per_instance = H.per_instance;
 		Q.depth = H.depth;
-		Q.sample_time = H.sample_time;
+		Q.sample_time = C.chain_sample_time;
 		Q.table = H.table;
 		Q.taps = H.taps;
 		Q.filt = H.filt;
@@ -306,177 +295,80 @@ saip_status saip::eng::sensing_refresh(saip_batch* b) {
 }
 
 // ---- the sensing chain (saip_sense_chain.hip): delay line, finite-difference velocity and low-pass behind the sensing model's joint rows.
-// Its state (taps, filt, primed) is on the snapshot directory while attached (saip_engine_snapshot.cpp).
+// The host side is saip_engine_chain.cpp's; its own here: the sample time, and the measured copy gone stale (epoch = -1) whenever the
+// chain that wrote it comes, goes or starts afresh.
 static saip_status need_chain(const saip_batch* b, const char* fn) {
 	saip_status st = need_sensing(b, fn);
-	if (st) return st;
-	if (!b->sensing.chain.attached) return fail(SAIP_ERR_ORDER, "%s: no sensing chain is attached (saip_batch_sensing_chain_attach)", fn);
-	return SAIP_OK;
-}
-static const char* const SENSE_CHAIN_WORD_NAMES[saip::SENSE_CHAIN_WORDS] = {"delay", "vel_mode", "a_q", "a_dq"};
-// a chain table [n][4] (cols = 1) or [n][4][cols]: true when fine, else msg names the joint and the word (and the instance).  bounds: the
-// two tables of a draw, whose delay and vel_mode are rounded and clamped afterwards and only have to be finite
-static bool chain_check_table(const double* t, int n, size_t cols, int depth, bool bounds, char* msg, size_t len) {
-	using namespace saip;
-	char buf[96];
-	for (int j = 0; j < n; j++)
-		for (size_t i = 0; i < cols; i++)
-			for (int k = 0; k < SENSE_CHAIN_WORDS; k++) {
-				const double v = t[((size_t)j * SENSE_CHAIN_WORDS + k) * cols + i];
-				const char* name = SENSE_CHAIN_WORD_NAMES[k];
-				buf[0] = 0;
-				if (v != v) snprintf(buf, sizeof(buf), "word %s is NaN", name);
-				else if (!std::isfinite(v)) snprintf(buf, sizeof(buf), "word %s is not finite", name);
-				else if (k == SENSE_CHAIN_DELAY && !bounds && (v != std::floor(v) || v < 0 || v > depth))
-					snprintf(buf, sizeof(buf), "word %s = %g is not an integer in 0..%d", name, v, depth);
-				else if (k == SENSE_CHAIN_VEL_MODE && !bounds && v != 0.0 && v != 1.0) snprintf(buf, sizeof(buf), "word %s = %g is neither 0 nor 1", name, v);
-				else if (k >= SENSE_CHAIN_A_Q && (v < 0 || v > 1)) snprintf(buf, sizeof(buf), "word %s = %g is outside [0, 1]", name, v);
-				if (!buf[0]) continue;
-				if (cols > 1) snprintf(msg, len, "joint %d of instance %zu: %s", j, i, buf);
-				else snprintf(msg, len, "joint %d: %s", j, buf);
-				return false;
-			}
-	return true;
-}
-static size_t chain_state_bytes(const saip_batch* b, int depth) {
-	const size_t n = b->model->n, ld = b->ld;
-	return ((size_t)2 * depth * n + saip::SENSE_CHAIN_FILT_ROWS * n) * ld * sizeof(double) + n * ld * sizeof(int);
+	return st ? st : chain_need(sense_chain_kind(), b->sensing.chain, fn);
 }
 extern "C" saip_status saip_batch_sensing_chain_attach(saip_batch* b, const double* table, int per_instance, int depth, double sample_time) {
 	const char* fn = "saip_batch_sensing_chain_attach";
-	saip_status st = need_controller(b, fn);
+	saip_status st = chain_attach_depth(sense_chain_kind(), b, depth, fn);
 	if (st) return st;
-	const int n = b->model->n;
-	// the arguments first (nothing here needs the sensing model or the device), then the call order
-	if (depth < 0 || depth > saip::SENSE_CHAIN_MAX_DEPTH) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a depth of 0..%d required (got %d)", fn, saip::SENSE_CHAIN_MAX_DEPTH, depth);
 	if (!(sample_time > 0) || !std::isfinite(sample_time)) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a finite sample time > 0 required (got %g)", fn, sample_time);
-	per_instance = per_instance ? 1 : 0;
-	const size_t cols = per_instance ? (size_t)b->B : 1;
-	std::vector<double> neutral;
-	if (!table) {
-		neutral.assign((size_t)n * saip::SENSE_CHAIN_WORDS * cols, 0.0);
-		table = neutral.data();
-	}
-	char msg[200];
-	if (!chain_check_table(table, n, cols, depth, false, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, msg);
-	if (!b->sensing.attached) return fail(SAIP_ERR_ORDER, "%s: no sensing model is attached (saip_batch_sensing_attach; an all-zero table is a valid carrier)", fn);
-	if (b->sensing.chain.attached) return fail(SAIP_ERR_ORDER, "%s: a sensing chain is already attached (saip_batch_sensing_chain_detach first)", fn);
-	if ((st = need_ready(b, fn))) return st;
-	auto& H = b->sensing.chain;
-	H = saip_batch::Sensing::Chain();
-	const size_t ld = b->ld, rows = (size_t)n * saip::SENSE_CHAIN_WORDS;
-	double* primed = nullptr;
-	if ((st = alloc_zero(b, &H.table, rows * (per_instance ? ld : 1))) || (depth > 0 && (st = alloc_zero(b, &H.taps, (size_t)2 * depth * n * ld))) ||
-		(st = alloc_zero(b, &H.filt, (size_t)saip::SENSE_CHAIN_FILT_ROWS * n * ld)) || (st = alloc_zero(b, &primed, ((size_t)n * ld + 1) / 2)) ||
-		(per_instance && (st = alloc_zero(b, &H.bounds, 2 * rows))) || (st = upload_table(b, H.table, table, rows, per_instance, "table", fn))) {
-		if (primed) (void)hipFree(primed);
-		sensing_chain_free(b);
-		return st;
-	}
-	H.primed = (int*)primed;  // n ld 32-bit flags, zeroed
-	H.attached = true;
-	H.per_instance = per_instance;
-	H.depth = depth;
-	H.sample_time = sample_time;
+	if ((st = chain_attach(sense_chain_kind(), b, b->sensing.chain, b->sensing.attached, table, per_instance, depth, fn))) return st;
+	b->sensing.chain_sample_time = sample_time;
 	b->sensing.epoch = -1;  // the next read of the state takes the chain's first sample, which primes it
 	return SAIP_OK;
 }
 extern "C" saip_status saip_batch_sensing_chain_detach(saip_batch* b) {
 	const char* fn = "saip_batch_sensing_chain_detach";
 	saip_status st = need_chain(b, fn);
-	if (st || (st = need_ready(b, fn))) return st;
-	HIP_TRY(hipStreamSynchronize(b->stream));  // a measurement that writes the chain's state may still be in flight
-	sensing_chain_free(b);
+	if (st || (st = chain_detach(b, b->sensing.chain, fn))) return st;
+	b->sensing.chain_sample_time = 0;
 	b->sensing.epoch = -1;  // the measured copy holds the chain's output: the sensing model alone measures again
 	return SAIP_OK;
 }
 extern "C" saip_status saip_batch_sensing_chain_info(saip_batch* b, int* attached, int* per_instance, int* depth, double* sample_time, size_t* state_bytes) {
 	saip_status st = need_sensing(b, "saip_batch_sensing_chain_info");
 	if (st) return st;
-	const auto& H = b->sensing.chain;
-	if (attached) *attached = H.attached ? 1 : 0;
-	if (per_instance) *per_instance = H.per_instance;
-	if (depth) *depth = H.depth;
-	if (sample_time) *sample_time = H.sample_time;
-	if (state_bytes) *state_bytes = H.attached ? chain_state_bytes(b, H.depth) : 0;
+	chain_info(sense_chain_kind(), b, b->sensing.chain, attached, per_instance, depth, state_bytes);
+	if (sample_time) *sample_time = b->sensing.chain_sample_time;
 	return SAIP_OK;
 }
 extern "C" saip_status saip_batch_sensing_chain_set_table_host(saip_batch* b, const double* table) {
 	const char* fn = "saip_batch_sensing_chain_set_table_host";
 	saip_status st = need_chain(b, fn);
-	if (st) return st;
-	if (!table) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null table", fn);
-	auto& H = b->sensing.chain;
-	char msg[200];
-	if (!chain_check_table(table, b->model->n, H.per_instance ? (size_t)b->B : 1, H.depth, false, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, msg);
-	if ((st = need_ready(b, fn))) return st;
-	// the state stays: the next sample runs the new words over the history there is (saip_batch_sensing_chain_reset starts afresh)
-	return upload_table(b, H.table, table, (size_t)b->model->n * saip::SENSE_CHAIN_WORDS, H.per_instance, "table", fn);
+	return st ? st : chain_set_table(sense_chain_kind(), b, b->sensing.chain, table, fn);
 }
-// The per-instance table drawn on the device between two batch-uniform tables [n][4] (host pointers).  a_q and a_dq of both bounds have to
-// be valid words; delay and vel_mode only finite: the draw is rounded to the nearest integer and clamped to its range.
+// a_q and a_dq of both bounds have to be valid words; delay and vel_mode only finite: the draw is rounded to the nearest integer and
+// clamped to its range
 extern "C" saip_status saip_batch_sensing_chain_randomize(saip_batch* b, unsigned long long seed, long long round, const double* lo, const double* hi) {
 	const char* fn = "saip_batch_sensing_chain_randomize";
 	saip_status st = need_chain(b, fn);
-	if (st) return st;
-	auto& H = b->sensing.chain;
-	const int n = b->model->n;
-	if (!lo || !hi) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null bounds", fn);
-	if (!H.per_instance) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the chain table is batch-uniform (attach it per instance)", fn);
-	char msg[200];
-	for (const double* t : {lo, hi})
-		if (!chain_check_table(t, n, 1, H.depth, true, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s bound: %s", fn, t == lo ? "lower" : "upper", msg);
-	if ((st = need_ready(b, fn))) return st;
-	const size_t rows = (size_t)n * saip::SENSE_CHAIN_WORDS;
-	if ((st = upload_table(b, H.bounds, lo, rows, 0, "table", fn)) || (st = upload_table(b, H.bounds + rows, hi, rows, 0, "table", fn))) return st;
+	if (st || (st = chain_randomize_bounds(sense_chain_kind(), b, b->sensing.chain, lo, hi, fn))) return st;
+	const auto& H = b->sensing.chain;
 	saip::SenseChainRandomParams P;
 	memset(&P, 0, sizeof(P));
 	P.B = b->B;
 	P.ld = b->ld;
-	P.n = n;
+	P.n = b->model->n;
 	P.depth = H.depth;
 	P.seed_lo = (uint32_t)seed;
 	P.seed_hi = (uint32_t)(seed >> 32);
 	P.round = (uint32_t)round;
 	P.table = H.table;
 	P.lo = H.bounds;
-	P.hi = H.bounds + rows;
+	P.hi = H.bounds + (size_t)P.n * saip::SENSE_CHAIN_WORDS;
 	hipError_t e = saip::launch_sense_chain_randomize(P, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "sensing chain randomize launch failed: %s", hipGetErrorString(e));
 	return SAIP_OK;
 }
-// primed cleared on the stream, without a synchronisation: the next sample of every (joint, instance) primes again
 extern "C" saip_status saip_batch_sensing_chain_reset(saip_batch* b) {
 	const char* fn = "saip_batch_sensing_chain_reset";
 	saip_status st = need_chain(b, fn);
-	if (st || (st = need_ready(b, fn))) return st;
-	HIP_TRY(hipMemsetAsync(b->sensing.chain.primed, 0, (size_t)b->model->n * b->ld * sizeof(int), b->stream));
+	if (st || (st = chain_reset(b, b->sensing.chain, fn))) return st;
 	b->sensing.epoch = -1;  // the measured copy is the old chain's output: the next read takes the priming sample
 	return SAIP_OK;
 }
 extern "C" double* saip_batch_sensing_chain_table_device(saip_batch* b) { return b ? b->sensing.chain.table : nullptr; }
-// the state arrays themselves, [rows][ld] (taps null at depth 0); any output may be null
 extern "C" saip_status saip_batch_sensing_chain_state_device(saip_batch* b, double** taps, double** filt, int** primed) {
 	saip_status st = need_chain(b, "saip_batch_sensing_chain_state_device");
-	if (st) return st;
-	const auto& H = b->sensing.chain;
-	if (taps) *taps = H.taps;
-	if (filt) *filt = H.filt;
-	if (primed) *primed = H.primed;
-	return SAIP_OK;
+	return st ? st : chain_state_device(b->sensing.chain, taps, filt, primed);
 }
-// the state for tests and debugging: taps [n][2][depth][B], filt [n][3][B], primed [n][B]; any may be null
 extern "C" saip_status saip_batch_sensing_chain_state_host(saip_batch* b, double* taps, double* filt, int* primed) {
 	const char* fn = "saip_batch_sensing_chain_state_host";
 	saip_status st = need_chain(b, fn);
-	if (st || (st = need_ready(b, fn))) return st;
-	const auto& H = b->sensing.chain;
-	const int n = b->model->n;
-	if (taps && H.depth > 0 && (st = copy_d2h(b, taps, H.taps, 2 * H.depth * n))) return st;
-	if (filt && (st = copy_d2h(b, filt, H.filt, saip::SENSE_CHAIN_FILT_ROWS * n))) return st;
-	if (primed) {
-		HIP_TRY(hipMemcpy2DAsync(primed, (size_t)b->B * sizeof(int), H.primed, (size_t)b->ld * sizeof(int), (size_t)b->B * sizeof(int), n, hipMemcpyDeviceToHost, b->stream));
-		HIP_TRY(hipStreamSynchronize(b->stream));
-	}
-	return SAIP_OK;
+	return st ? st : chain_state_host(sense_chain_kind(), b, b->sensing.chain, taps, filt, primed, fn);
 }
+

@@ -62,20 +62,14 @@ static void snapshot_directory(const saip_batch* b, std::vector<SnapSegHost>& D)
 		}
 		if (T.dev.popc) soa(p + "popc", T.dev.popc, 7 + T.dev.popc_cap, 8);
 	}
-	// the sensing chain: an attachment with state (delay taps, filter state, primed flags); absent while detached, so a snapshot of
-	// another chain layout differs in a segment the comparison names
-	if (b->sensing.chain.attached) {
-		const auto& H = b->sensing.chain;
-		if (H.depth > 0) soa("sense.chain.taps", H.taps, 2 * H.depth * n, 8);
-		soa("sense.chain.filt", H.filt, saip::SENSE_CHAIN_FILT_ROWS * n, 8);
-		soa("sense.chain.primed", H.primed, n, 4);
-	}
-	// the actuation chain, its command-side twin, under the same rule
-	if (b->plant.chain.attached) {
-		const auto& H = b->plant.chain;
-		if (H.depth > 0) soa("plant.chain.taps", H.taps, H.depth * n, 8);
-		soa("plant.chain.filt", H.filt, saip::PLANT_CHAIN_FILT_ROWS * n, 8);
-		soa("plant.chain.primed", H.primed, n, 4);
+	// the chains, sensing then actuation: attachments with state (delay taps, filter state, primed flags); absent while detached, so a
+	// snapshot of another chain layout differs in a segment the comparison names
+	for (const auto& [K, H] : {std::pair<const ChainKind&, const Chain&>{sense_chain_kind(), b->sensing.chain}, {plant_chain_kind(), b->plant.chain}}) {
+		if (!H.attached) continue;
+		const std::string p = std::string(K.snapshot) + ".";
+		if (H.depth > 0) soa(p + "taps", H.taps, K.tap_rows * H.depth * n, 8);
+		soa(p + "filt", H.filt, K.filt_rows * n, 8);
+		soa(p + "primed", H.primed, n, 4);
 	}
 }
 static_assert(sizeof(saip::ShState) % 4 == 0, "ShState is moved as 4- or 8-byte words");

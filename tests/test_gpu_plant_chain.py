@@ -561,6 +561,96 @@ def test_lifecycle(sp):
     assert levels[-1] == levels[0] and levels[-2] == levels[1], levels   # 20 more pairs after the first (each way out): nothing is left behind
 
 
+# ------------------------------------------------------------------ 7b. both chains at once: neither entry reaches into the other's state
+def test_both_chains_together(sp):
+    """Config 2 on the Panda, B = 70 at its own ld = 96, a sensing chain of depth 2 (2 * 2 * 7 tap rows) and an actuation chain of depth 3
+    (3 * 7), non-neutral per-instance tables.  Every assertion is an equality between runs of one build: the snapshot directory against the
+    two info calls; a reset or a detach of one chain against the other's state arrays; a restored continuation against the first."""
+    from sai_primitives_amd import capi
+    ld, ds, da, K, sub = 96, 2, 3, 3, 2
+    rng = np.random.default_rng(41)
+    robot, ctrl, objs, mf, _ = _panda(B, True)
+    assert capi.lib().saip_batch_ld(ctrl._h) == ld
+    robot.setDq(0.1 * rng.uniform(-1, 1, (B, N)))
+    robot.updateModel()
+    ctrl.updateControllerTaskModels()
+    plant = np.repeat(PL.neutral(N)[:, None, :], B, axis=1)
+    plant[..., PL.GAIN], plant[..., PL.FV] = rng.uniform(0.9, 1.1, (N, B)), rng.uniform(0.0, 0.3, (N, B))
+    schain = np.zeros((N, B, 4))
+    schain[..., 0], schain[..., 1] = rng.integers(0, ds + 1, (N, B)), rng.integers(0, 2, (N, B))
+    schain[..., 2], schain[..., 3] = rng.choice([0.0, SC.alpha(50.0, DT)], (N, B)), SC.alpha(80.0, DT)
+    achain = _chain_table(rng, da)
+    ctrl.attachPlant(plant, per_instance=True)
+    ctrl.attachSensing(_random_joint_table(rng, N, (), 2e-3), seed=5)
+    ctrl.attachSensingChain(schain, per_instance=True, depth=ds, sample_time=DT)
+    ctrl.attachActuationChain(achain, per_instance=True, depth=da)
+
+    def sense():
+        st = ctrl.sensingChainState()
+        return [st["taps"], st["filt"], st["primed"]]
+
+    def roll():
+        ctrl.rolloutAsync(K, DT, sub, gravity=ZERO_G)
+        return _finals(ctrl)[:3] + sense() + _state(ctrl)
+
+    def names():
+        return [s["name"] for s in ctrl.saveState().segments()]
+
+    def refuses(stem, noun):
+        """with only the other chain attached, every entry of this one answers with its own message (and writes nothing)"""
+        from test_plant_chain_cpu import chain_calls
+        for fn, status, msg in chain_calls(capi.lib(), ctrl._h, stem, B):
+            assert status == capi.SAIP_ERR_ORDER and msg == f"{fn}: no {noun} is attached (saip_batch_{stem}_chain_attach)", (fn, msg)
+
+    # 1. the directory lists both chains' state, each at the size its own info call reports
+    segs = {s["name"]: s for s in ctrl.saveState().segments()}
+    for prefix, rows, info in (("sense.chain.", 2 * ds * N, ctrl.sensingChainInfo()), ("plant.chain.", da * N, ctrl.actuationChainInfo())):
+        mine = [segs[prefix + k] for k in ("taps", "filt", "primed")]
+        assert [s["rows"] for s in mine] == [rows, 3 * N, N] and [s["elem_bytes"] for s in mine] == [8, 8, 4], prefix
+        assert sum(s["rows"] * ld * s["elem_bytes"] for s in mine) == info["state_bytes"], prefix
+        assert info["attached"] and info["per_instance"] and info["depth"] == (ds if prefix[0] == "s" else da)
+    assert len([n for n in segs if ".chain." in n]) == 6
+    # 2. a reset zeroes the chain's own primed and nothing else of either chain
+    roll()
+    s0, a0 = sense(), _state(ctrl)
+    assert (s0[2] == 1).all() and (a0[2] == 1).all() and not (s0[0] == 0).all() and not (a0[0] == 0).all()
+    ctrl.resetSensingChain()
+    s1 = sense()
+    assert (s1[2] == 0).all() and _equal(s1[:2], s0[:2]) and _equal(_state(ctrl), a0)
+    roll()                                                                # both primed again
+    s0, a0 = sense(), _state(ctrl)
+    assert (s0[2] == 1).all() and (a0[2] == 1).all()
+    ctrl.resetActuationChain()
+    a1 = _state(ctrl)
+    assert (a1[2] == 0).all() and _equal(a1[:2], a0[:2]) and _equal(sense(), s0)
+    roll()
+    # 3. a restored continuation repeats the first (the two period counters are not part of a snapshot)
+    snap, periods = ctrl.saveState(), (ctrl.sensingInfo()["period"], ctrl.plantInfo()["period"])
+    first = roll()
+    ctrl.restoreState(snap)
+    ctrl.setSensingPeriod(periods[0])
+    ctrl.setPlantPeriod(periods[1])
+    assert _equal(first, roll()) and np.isfinite(first[0]).all()
+    # 4. a detach takes the chain's own three segments and leaves the other chain's info and state alone
+    every = names()
+    info, a0 = ctrl.actuationChainInfo(), _state(ctrl)
+    ctrl.detachSensingChain()
+    assert ctrl.actuationChainInfo() == info and _equal(_state(ctrl), a0)
+    assert names() == [n for n in every if not n.startswith("sense.chain.")] and len(names()) == len(every) - 3
+    refuses("sensing", "sensing chain")
+    ctrl.attachSensingChain(schain, per_instance=True, depth=ds, sample_time=DT)
+    roll()
+    assert names() == every
+    info, s0 = ctrl.sensingChainInfo(), sense()
+    ctrl.detachActuationChain()
+    assert ctrl.sensingChainInfo() == info and _equal(sense(), s0)
+    assert names() == [n for n in every if not n.startswith("plant.chain.")] and len(names()) == len(every) - 3
+    refuses("plant", "actuation chain")
+    assert ctrl.sensingChainInfo() == info and _equal(sense(), s0)
+    ctrl.detachSensing()
+    ctrl.detachPlant()
+
+
 # ------------------------------------------------------------------ 8. one closed-loop figure (printed and recorded in DESIGN.md 4.19, not asserted)
 def test_closed_loop_under_command_delay_stays_finite_and_the_neutral_row_is_the_plant(sp):
     """A joint task alone at config 1's gains (kp 100, kv 20), gravity-free, a 0.2 rad step on every joint, 300 periods of 1 ms.  Instance i

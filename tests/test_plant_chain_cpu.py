@@ -132,10 +132,48 @@ def test_c_abi_error_contract(sp):
         edge[:, 0], edge[:, 1], edge[:, 2] = 4.0, np.inf, 0.0
         for kw in (dict(), dict(table=None), dict(table=None, per=1), dict(table=per, per=1), dict(table=PC.neutral(7), depth=0), dict(table=edge), dict(depth=8)):
             assert call(b, **kw) == ORDER and b"no plant model is attached" in L.saip_last_error(), kw
+        assert L.saip_last_error() == b"saip_batch_plant_chain_attach: no plant model is attached (saip_batch_plant_attach; an all-neutral table is a valid carrier)"
+        # several at once: the depth is checked first, then the table, then the call order
+        bad = TABLE.copy()
+        bad[0, 2] = -1.0
+        refused(b, b"a depth of 0..8 required (got 9)", table=bad, depth=9)
+        refused(b, b"joint 0: word tau_lag = -1 is below 0", table=bad)
         _others_refuse(L, b, ORDER)
         assert b"no plant model is attached" in L.saip_last_error()
     finally:
         L.saip_batch_destroy(b)
+
+
+def chain_calls(L, b, stem, B=4):
+    """every status entry of the chain `stem` ("plant", "sensing") behind its need-check, called with well-formed arguments:
+    [(entry, status, message)]"""
+    z, flags, p = np.zeros(7 * 4 * B), np.zeros(7 * B, np.int32), C.c_void_p()
+    args = dict(detach=(), set_table_host=(_dp(z),), randomize=(1, 0, _dp(z), _dp(z)), reset=(),
+                state_host=(_dp(z), _dp(z), flags.ctypes.data_as(C.POINTER(C.c_int))), state_device=(C.byref(p),) * 3)
+    out = []
+    for entry, a in args.items():
+        fn = f"saip_batch_{stem}_chain_{entry}"
+        out.append((fn, getattr(L, fn)(b, *a), L.saip_last_error().decode()))
+    return out
+
+
+def each_chain_answers_for_itself(sp, L, stems):
+    """the two chains share their host code: on one batch every entry of either still names itself and its own carrier.  Without a device
+    no carrier can be attached, so this is as far as the order checks go here; tests/test_gpu_plant_chain.py::test_both_chains_together
+    has the "no ... chain is attached" half, with one chain attached and the other not."""
+    from sai_primitives_amd import capi
+    robot, b = _controller_batch(sp, L, 4)
+    try:
+        assert L.saip_batch_finalize(b) == 0
+        for stem in stems + stems[::-1]:
+            for fn, status, msg in chain_calls(L, b, stem):
+                assert status == capi.SAIP_ERR_ORDER and msg == f"{fn}: no {stem} model is attached (saip_batch_{stem}_attach)", (fn, msg)
+    finally:
+        L.saip_batch_destroy(b)
+
+
+def test_each_chain_answers_for_itself(sp):
+    each_chain_answers_for_itself(sp, sp.lib(), ["plant", "sensing"])
 
 
 def test_model_only_batch_refuses_the_chain(sp):

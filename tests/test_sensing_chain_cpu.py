@@ -130,10 +130,22 @@ def test_c_abi_error_contract(sp):
         for kw in (dict(), dict(table=None), dict(table=None, per=1), dict(table=per, per=1), dict(table=np.zeros((7, 4)), depth=0), dict(table=edge), dict(depth=8),
                    dict(T=1e-300)):
             assert call(b, **kw) == ORDER and b"no sensing model is attached" in L.saip_last_error(), kw
+        assert L.saip_last_error() == b"saip_batch_sensing_chain_attach: no sensing model is attached (saip_batch_sensing_attach; an all-zero table is a valid carrier)"
+        # several at once: the depth is checked first, then the sample time, then the table, then the call order
+        bad = TABLE.copy()
+        bad[0, 2] = 2.0
+        refused(b, b"a depth of 0..8 required (got 9)", table=bad, depth=9, T=0.0)
+        refused(b, b"a finite sample time > 0 required (got 0)", table=bad, T=0.0)
+        refused(b, b"joint 0: word a_q = 2 is outside [0, 1]", table=bad)
         _others_refuse(L, b, ORDER)
         assert b"no sensing model is attached" in L.saip_last_error()
     finally:
         L.saip_batch_destroy(b)
+
+
+def test_each_chain_answers_for_itself(sp):
+    from test_plant_chain_cpu import each_chain_answers_for_itself
+    each_chain_answers_for_itself(sp, sp.lib(), ["sensing", "plant"])
 
 
 def test_model_only_batch_refuses_the_chain(sp):
