@@ -331,7 +331,44 @@ saip_status saip_snapshot_import_host(saip_batch*, saip_snapshot*, const void* i
  * outside 0 .. B, a negative or non-finite sigma, a batch-uniform schedule, a range over part of rows 3..11 or of more than 36 rows, a
  * nominal plan that fails the check above.  SAIP_ERR_ORDER: a task without a schedule, a second _attach on a
  * task, any other entry without a sampler, _cost with a non-zero summary weight but no recorder summaries, _cost with a target but no
- * POSE channel or no sample yet.  Argument and order errors are reported before the device is needed; a failed call writes nothing. */
+ * POSE channel or no sample yet.  Argument and order errors are reported before the device is needed; a failed call writes nothing.
+ *
+ * Scenario groups: planning under randomisation.  saip_batch_sampler_set_scenarios(n_scenarios = M, risk, tail) makes the batch of
+ * B = C M instances C candidate plans, each rolled out in M scenarios: instance i = s C + c is candidate c = i % C in scenario s = i / C,
+ * so the batch is M scenario blocks of C columns and block 0 is what an ungrouped sampler on a batch of C would be, bit for bit.  M = 1,
+ * the default, is the sampler described above: the same launches, the same bits.  With M > 1:
+ *   _perturb  the noise counter's instance word and the exempt test use the candidate c: the keyframes of candidate c are the same bits
+ *        in every scenario block, those of an ungrouped batch of C under the same seed, round and task.
+ *   _update  three launches.  First the group cost [C], one lane per candidate over v_s = cost[s C + c]: +inf if any v_s is not finite
+ *        (one bad scenario makes the candidate invalid), else by the risk measure
+ *          SAIP_SAMPLER_RISK_MEAN  (((0.0 + v_0) + v_1) + ... + v_{M-1}) / M
+ *          SAIP_SAMPLER_RISK_MAX   the largest v_s (as 0.0 + v: a largest value of -0.0 is reported as +0.0)
+ *          SAIP_SAMPLER_RISK_CVAR  the `tail` largest v_s added in descending order from 0.0, divided by tail; tail = 1 is MAX bit for bit
+ *        then weights and update as above over the C group costs and columns 0 .. C - 1 of the keyframes: best is the best candidate
+ *        (also the index of its scenario-0 instance), n_valid, min_cost, sum_w and ess are over candidates, and the best map is
+ *        map[i] = (i / C) C + best, every scenario block taking its own copy of the best candidate (-1 everywhere without a finite
+ *        group cost).  The weights [ld] hold C entries.
+ *   _cost, _set_cost_host, _get_cost_host and saip_batch_clearance_add_cost keep working on the B per-instance costs; _shift and the
+ *        nominal accessors are unchanged.
+ *   _get_group_cost_host / _group_cost_device  the group cost [C] the last _update formed.  With M = 1 no group cost is formed: both give
+ *        the cost array itself ([B] = [C]), not a copy.
+ *   _share_scenario_tables  makes scenario s the same simulated robot for every candidate: in every resident per-instance table that a
+ *        _randomize entry can fill, column i takes the bits of column (i / C) C.  One launch per array, enqueued on the engine stream;
+ *        *n_arrays is the number of arrays touched, at most 8: the plant's joint table, its wrench table, the actuation chain's table, the
+ *        inertia's part staging (bodies and payloads, one array), the composed inertia rows the integrator reads (composition is a
+ *        per-column function of the parts), the sensing model's joint table, its wrench tables, the sensing chain's table -- each only
+ *        while attached per instance; batch-uniform tables are skipped and not counted.  Source columns and columns B .. ld - 1 are not
+ *        written.  State is not shared: chain taps, filters and primed flags stay per instance, and the sensing model's noise stays keyed
+ *        by the instance.
+ * SAIP_ERR_INVALID_ARGUMENT of _set_scenarios, before anything else is looked at: n_scenarios outside 1 .. SAIP_SAMPLER_MAX_SCENARIOS, an
+ * unknown risk, a tail outside 1 .. n_scenarios with CVAR or other than 0 without, B no multiple of n_scenarios.  Then SAIP_ERR_ORDER
+ * without a sampler, then SAIP_ERR_INVALID_ARGUMENT if an attached sampler's exempt exceeds C; a later _attach refuses exempt > C likewise.
+ * Detaching the last sampler resets the setting to M = 1.  _share_scenario_tables: SAIP_ERR_ORDER without a sampler or with M = 1.  A
+ * failed call changes nothing. */
+#define SAIP_SAMPLER_MAX_SCENARIOS 64
+#define SAIP_SAMPLER_RISK_MEAN 0
+#define SAIP_SAMPLER_RISK_MAX 1
+#define SAIP_SAMPLER_RISK_CVAR 2
 saip_status saip_batch_sampler_attach(saip_batch*, int task, const double* sigma /* [d] */, const double* nominal /* [K][count], NULL = column 0 of the resident keyframes */, int exempt);
 saip_status saip_batch_sampler_detach(saip_batch*, int task /* -1: all */);
 saip_status saip_batch_sampler_seed(saip_batch*, unsigned long long seed);  /* also sets round = 0 */
@@ -347,6 +384,12 @@ const int* saip_batch_sampler_best_map_device(saip_batch*);                 /* [
 saip_status saip_batch_sampler_get_nominal_host(saip_batch*, int task, double* out /* [K][count] */);
 saip_status saip_batch_sampler_set_nominal_host(saip_batch*, int task, const double* in);
 saip_status saip_batch_sampler_info(saip_batch*, int task, int* d, int* exempt, unsigned long long* seed, long long* round);
+saip_status saip_batch_sampler_set_scenarios(saip_batch*, int n_scenarios, int risk, int tail /* CVAR: 1 .. n_scenarios; else 0 */);
+saip_status saip_batch_sampler_scenarios_info(saip_batch*, int* n_scenarios, int* n_candidates, int* risk, int* tail);  /* any NULL */
+saip_status saip_batch_sampler_get_group_cost_host(saip_batch*, double* out /* [C] */);  /* synchronous */
+double* saip_batch_sampler_group_cost_device(saip_batch*);                  /* [ld]; NULL without a sampler */
+saip_status saip_batch_sampler_share_scenario_tables(saip_batch*, int* n_arrays /* may be NULL */);
+const double* saip_batch_sampler_weights_device(saip_batch*);               /* [ld] the softmin weights of the last _update, one per candidate; NULL without a sampler */
 /* ---- contact planes and a simulated force sensor: something for the resident simulator to touch, so that a force task (closed-loop
  * force / moment control, the passivity observer, the sensed-wrench diagnostics) can be rolled out with no host in the loop.  One
  * attachment per batch: ONE contact point p = x_c + R_c r_c carried by the body of a motion-force task (x_c, R_c: its control point and

@@ -1139,6 +1139,42 @@ public:
 		if (!map) throw std::runtime_error("restoreStateBest: no sampler is attached");
 		restoreStateDevice(snapshot, map);
 	}
+	// ---- scenario groups (saip.h): B = C * M instances as C candidate plans rolled out in M scenarios each, instance i = s * C + c.
+	//   risk "mean", "max" or "cvar"; alpha in (0, 1] with "cvar" only (the mean of the worst ceil(alpha * M) scenarios), else 0
+	struct SamplerScenarios {
+		int n_scenarios = 1, n_candidates = 0, tail = 0;
+		std::string risk = "mean";
+	};
+	void setSamplerScenarios(int n_scenarios, const std::string& risk = "mean", double alpha = 0) {
+		const int r = risk == "mean" ? SAIP_SAMPLER_RISK_MEAN : risk == "max" ? SAIP_SAMPLER_RISK_MAX : risk == "cvar" ? SAIP_SAMPLER_RISK_CVAR : -1;
+		if (r < 0) throw std::invalid_argument("setSamplerScenarios: unknown risk \"" + risk + "\" (mean, max or cvar)");
+		int tail = 0;
+		if (r == SAIP_SAMPLER_RISK_CVAR) {
+			if (!(alpha > 0.0 && alpha <= 1.0)) throw std::invalid_argument("setSamplerScenarios: risk \"cvar\" needs alpha in (0, 1], got " + std::to_string(alpha));
+			tail = std::min(n_scenarios, std::max(1, (int)std::ceil(alpha * n_scenarios)));
+		} else if (alpha != 0.0)
+			throw std::invalid_argument("setSamplerScenarios: alpha = " + std::to_string(alpha) + " applies to risk \"cvar\" only, not to \"" + risk + "\"");
+		check(saip_batch_sampler_set_scenarios(_batch, n_scenarios, r, tail));
+	}
+	SamplerScenarios samplerScenarios() {
+		SamplerScenarios s;
+		int risk = 0;
+		check(saip_batch_sampler_scenarios_info(_batch, &s.n_scenarios, &s.n_candidates, &risk, &s.tail));
+		s.risk = risk == SAIP_SAMPLER_RISK_MAX ? "max" : risk == SAIP_SAMPLER_RISK_CVAR ? "cvar" : "mean";
+		return s;
+	}
+	// [C] the group cost per candidate of the last updateSampler(); without scenario groups the per-instance costs themselves
+	std::vector<double> samplerGroupCost() {
+		std::vector<double> out((size_t)samplerScenarios().n_candidates);
+		check(saip_batch_sampler_get_group_cost_host(_batch, out.data()));
+		return out;
+	}
+	// column i of every resident per-instance randomisable table takes column (i / C) * C; returns the number of arrays touched
+	int shareScenarioTables() {
+		int n = 0;
+		check(saip_batch_sampler_share_scenario_tables(_batch, &n));
+		return n;
+	}
 
 	// ---- rollout recorder: per-period trajectory log and running summaries of rolloutAsync, kept on the device (saip.h)
 	struct RolloutLog {

@@ -16,6 +16,8 @@ SAIP_QUERY_JACOBIAN, SAIP_QUERY_WORLD = 1, 2
 SAIP_RECORD_Q, SAIP_RECORD_DQ, SAIP_RECORD_TAU, SAIP_RECORD_POSE, SAIP_RECORD_ERROR = 1, 2, 4, 8, 16
 SAIP_RECORD_SUMMARY_ROWS = 8
 SAIP_SCHEDULE_HOLD, SAIP_SCHEDULE_LINEAR = 0, 1
+SAIP_SAMPLER_MAX_SCENARIOS = 64
+SAIP_SAMPLER_RISK_MEAN, SAIP_SAMPLER_RISK_MAX, SAIP_SAMPLER_RISK_CVAR = 0, 1, 2
 SAIP_SNAPSHOT_SOA, SAIP_SNAPSHOT_GROUPED, SAIP_SNAPSHOT_AOS = 0, 1, 2
 SAIP_CONTACT_MAX_PLANES, SAIP_CONTACT_PLANE_WORDS, SAIP_CONTACT_READOUT_ROWS, SAIP_CONTACT_SUMMARY_ROWS = 4, 8, 8, 4
 SAIP_CONTACT_PATCH_MAX_POINTS, SAIP_CONTACT_PATCH_MAX, SAIP_CONTACT_PATCH_READOUT_ROWS, SAIP_CONTACT_PATCH_SUMMARY_ROWS = 8, 2, 20, 6
@@ -208,6 +210,12 @@ def lib():
         "saip_batch_sampler_get_nominal_host": (C.c_int, [vp, C.c_int, dp]),
         "saip_batch_sampler_set_nominal_host": (C.c_int, [vp, C.c_int, dp]),
         "saip_batch_sampler_info": (C.c_int, [vp, C.c_int, ip, ip, C.POINTER(C.c_ulonglong), C.POINTER(C.c_longlong)]),
+        "saip_batch_sampler_set_scenarios": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+        "saip_batch_sampler_scenarios_info": (C.c_int, [vp, ip, ip, ip, ip]),
+        "saip_batch_sampler_get_group_cost_host": (C.c_int, [vp, dp]),
+        "saip_batch_sampler_group_cost_device": (vp, [vp]),
+        "saip_batch_sampler_share_scenario_tables": (C.c_int, [vp, ip]),
+        "saip_batch_sampler_weights_device": (vp, [vp]),
         "saip_batch_contact_attach": (C.c_int, [vp, C.c_int, dp, C.c_int, dp, C.c_int, C.c_int]),
         "saip_batch_contact_detach": (C.c_int, [vp]),
         "saip_batch_contact_info": (C.c_int, [vp, ip, ip, ip, ip, dp]),

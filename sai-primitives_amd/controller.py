@@ -17,6 +17,7 @@ import ctypes as C
 import weakref
 import enum
 import json
+import math
 import os
 from dataclasses import dataclass
 
@@ -2260,6 +2261,47 @@ class RobotController:
         mc, sw, ess = C.c_double(0), C.c_double(0), C.c_double(0)
         self._call("saip_batch_sampler_result_host", C.byref(best), C.byref(nv), C.byref(mc), C.byref(sw), C.byref(ess))
         return dict(best=best.value, n_valid=nv.value, min_cost=mc.value, sum_w=sw.value, ess=ess.value)
+
+    # -- scenario groups: B = C * M instances as C candidate plans rolled out in M scenarios each (saip.h)
+    _SAMPLER_RISKS = {"mean": capi.SAIP_SAMPLER_RISK_MEAN, "max": capi.SAIP_SAMPLER_RISK_MAX, "cvar": capi.SAIP_SAMPLER_RISK_CVAR}
+
+    def setSamplerScenarios(self, n_scenarios, risk="mean", alpha=None):
+        """make the batch n_scenarios blocks of C = B / n_scenarios candidate plans (instance i = s * C + c): perturbGoalSchedules()
+        gives candidate c the same keyframes in every block, updateSampler() folds the scenario costs of a candidate into one group
+        cost under `risk` -- "mean", "max" (the worst scenario) or "cvar" (the mean of the worst ceil(alpha * M) scenarios, alpha in
+        (0, 1]) -- and updates the plan over candidates.  n_scenarios = 1 is the ungrouped sampler."""
+        if risk not in self._SAMPLER_RISKS:
+            raise ValueError(f"setSamplerScenarios: unknown risk {risk!r} (one of {sorted(self._SAMPLER_RISKS)})")
+        M, tail = int(n_scenarios), 0
+        if risk == "cvar":
+            if alpha is None or not (0.0 < float(alpha) <= 1.0):
+                raise ValueError(f"setSamplerScenarios: risk \"cvar\" needs alpha in (0, 1], got {alpha!r}")
+            tail = min(M, max(1, math.ceil(float(alpha) * M)))
+        elif alpha is not None:
+            raise ValueError(f"setSamplerScenarios: alpha = {alpha!r} applies to risk \"cvar\" only, not to {risk!r}")
+        self._call("saip_batch_sampler_set_scenarios", M, self._SAMPLER_RISKS[risk], tail)
+
+    def samplerScenarios(self):
+        """dict n_scenarios, n_candidates, risk ("mean" / "max" / "cvar"), tail (the scenarios CVAR averages, else 0)"""
+        m, c, r, t = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._call("saip_batch_sampler_scenarios_info", C.byref(m), C.byref(c), C.byref(r), C.byref(t))
+        names = {v: k for k, v in self._SAMPLER_RISKS.items()}
+        return dict(n_scenarios=m.value, n_candidates=c.value, risk=names[r.value], tail=t.value)
+
+    def samplerGroupCost(self):
+        """(C,) the group cost per candidate of the last updateSampler() (waits for the engine stream); without scenario groups
+        the per-instance costs themselves"""
+        out = np.empty(self.samplerScenarios()["n_candidates"])
+        self._call("saip_batch_sampler_get_group_cost_host", _dptr(out))
+        return out
+
+    def shareScenarioTables(self):
+        """every resident per-instance table a randomize*() call can fill (plant, actuation chain, inertia, sensing, sensing chain):
+        column i takes column (i // C) * C, so that scenario s is the same simulated robot for every candidate.  Returns the number
+        of arrays touched.  Asynchronous."""
+        n = C.c_int(0)
+        self._call("saip_batch_sampler_share_scenario_tables", C.byref(n))
+        return n.value
 
     # -- state snapshots: the complete per-instance state, saved on the device and written back through a source index (saip.h)
     def saveState(self, snapshot=None):

@@ -51,6 +51,9 @@ hipError_t launch_state_gather(const SnapSeg* table, const int* unit_seg, int un
 hipError_t launch_sampler_perturb(const SamplerParams& P, hipStream_t stream);
 hipError_t launch_sampler_cost(const SamplerCostParams& P, hipStream_t stream);
 hipError_t launch_sampler_update(const SamplerParams& P, const double* cost, double temperature, double* w, SamplerResult* res, int* best_map, hipStream_t stream);
+hipError_t launch_sampler_update_grouped(const SamplerParams& P, const double* cost, int risk, int tail, double* group, double temperature, double* w, SamplerResult* res,
+										 int* best_map, hipStream_t stream);
+hipError_t launch_sampler_share_columns(double* a, int rows, int B, int ld, int C, hipStream_t stream);
 hipError_t launch_sampler_shift(const SamplerParams& P, int n, hipStream_t stream);
 hipError_t launch_contact_apply(const ContactParams& P, bool tree, hipStream_t stream);
 hipError_t launch_contact_patch_apply(const ContactPatchParams& P, bool tree, hipStream_t stream);
@@ -187,6 +190,10 @@ struct saip_batch {
 	double* samp_w = nullptr;                // [ld] softmin weights of the last update
 	int* samp_best_map = nullptr;            // [ld]
 	saip::SamplerResult* samp_result = nullptr;
+	// saip_batch_sampler_set_scenarios: B = C M instances are M scenario blocks of C candidates (instance i = s C + c); M = 1 is the
+	// ungrouped sampler.  Back to M = 1 when the last sampler is detached.
+	int samp_scenarios = 1, samp_risk = 0, samp_tail = 0;
+	double* samp_group = nullptr;            // [ld] group cost of the last grouped update, columns 0 .. C - 1
 	// saip_batch_contact_attach: contact planes and the simulated force sensor of the resident simulator (saip_contact.hip), at most one
 	// per batch.  Its arrays are configuration, scratch and readout: its own (freed by _detach), not part of `allocs` or of a snapshot.
 	struct Contact {

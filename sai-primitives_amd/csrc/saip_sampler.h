@@ -15,7 +15,9 @@
 
 namespace saip {
 
-enum { SAMP_LANES = 256, SAMP_WAVE = 64, SAMP_MAX_ROWS = 36, SAMP_MAXT = 8, SAMP_SUMMARY_ROWS = 8 };
+enum { SAMP_LANES = 256, SAMP_WAVE = 64, SAMP_MAX_ROWS = 36, SAMP_MAXT = 8, SAMP_SUMMARY_ROWS = 8, SAMP_MAX_SCENARIOS = 64 };
+// the risk measure that folds the M scenario costs of one candidate into its group cost (SAIP_SAMPLER_RISK_* of saip.h)
+enum { SAMP_RISK_MEAN = 0, SAMP_RISK_MAX = 1, SAMP_RISK_CVAR = 2 };
 
 // the result of one update, resident on the device (saip_batch_sampler_result_host)
 struct SamplerResult {
@@ -39,8 +41,10 @@ struct SamplerEntry {
 	int exempt;           // instances 0 .. exempt - 1 keep the nominal rows
 	int pad_;
 };
+// Scenario groups: a batch of B = C M instances is M scenario blocks of C candidate plans, instance i = s C + c.  C == B (M = 1) is
+// the ungrouped sampler: every instance its own candidate.
 struct SamplerParams {
-	int B, ld, n, pad_;   // n: entries in use
+	int B, ld, n, C;      // n: entries in use; C: candidates (B without scenario groups)
 	uint32_t seed_lo, seed_hi, round, pad2_;
 	SamplerEntry e[SAMP_MAXT];
 };
@@ -148,21 +152,22 @@ SAIP_SAMP_HD inline void samp_log(const double* R0, const double* R1, double* w)
 // sampler coordinate of row r of the range (not one of the nine rotation rows)
 SAIP_SAMP_HD inline int samp_coord(const SamplerEntry& E, int r) { return (E.rot && r >= E.r_rot + 9) ? r - 6 : r; }
 
-// ---- perturb: every keyframe of instance i.  Instances below `exempt` get the nominal rows bit for bit, the others
-// nominal + sigma * z per linear row and R_nom Exp(sigma o z) for the rotation.  Only column i is written.
-SAIP_SAMP_HD inline void samp_perturb_instance(const SamplerEntry& E, int ld, int i, uint32_t seed_lo, uint32_t seed_hi, uint32_t round) {
+// ---- perturb: every keyframe of instance i, which rolls out candidate c (c == i without scenario groups).  Candidates below `exempt`
+// get the nominal rows bit for bit, the others nominal + sigma * z per linear row and R_nom Exp(sigma o z) for the rotation, the noise
+// counter's instance word being c: a candidate has the same keyframes in every scenario block.  Only column i is written.
+SAIP_SAMP_HD inline void samp_perturb_candidate(const SamplerEntry& E, int ld, int i, int c, uint32_t seed_lo, uint32_t seed_hi, uint32_t round) {
 #pragma clang fp contract(off)
 	for (int k = 0; k < E.K; k++) {
 		const double* nom = E.nominal + (size_t)k * E.count;
 		double* key = E.key + (size_t)k * E.count * ld + i;
-		if (i < E.exempt) {
+		if (c < E.exempt) {
 			for (int r = 0; r < E.count; r++) key[(size_t)r * ld] = nom[r];
 			continue;
 		}
 		double z[SAMP_MAX_ROWS];
 		for (int p = 0; 2 * p < E.d; p++) {
 			double zz[2];
-			samp_normals(seed_lo, seed_hi, round, E.task, i, k, p, zz);
+			samp_normals(seed_lo, seed_hi, round, E.task, c, k, p, zz);
 			z[2 * p] = zz[0];
 			if (2 * p + 1 < E.d) z[2 * p + 1] = zz[1];
 		}
@@ -178,6 +183,10 @@ SAIP_SAMP_HD inline void samp_perturb_instance(const SamplerEntry& E, int ld, in
 			for (int e = 0; e < 9; e++) key[(size_t)(E.r_rot + e) * ld] = R[e];
 		}
 	}
+}
+
+SAIP_SAMP_HD inline void samp_perturb_instance(const SamplerEntry& E, int ld, int i, uint32_t seed_lo, uint32_t seed_hi, uint32_t round) {
+	samp_perturb_candidate(E, ld, i, i, seed_lo, seed_hi, round);
 }
 
 // ---- cost of instance i: sum over the summary rows with a non-zero weight, then w_path * sum over the samples (oldest first) of
@@ -203,10 +212,47 @@ SAIP_SAMP_HD inline double samp_cost_instance(const SamplerCostParams& P, int i)
 	return c;
 }
 
+// ---- group cost of candidate c over its M scenarios v_s = cost[s C + c].  One v_s that is not finite makes it +inf (the candidate is
+// invalid whatever the others say).  MEAN: (((0.0 + v_0) + v_1) + ... + v_{M-1}) / M.  MAX: the largest v_s.  CVAR: the `tail` largest
+// v_s added in descending order from 0.0, divided by tail; tail = 1 is MAX bit for bit ((0.0 + v) / 1.0 == v; a largest value of -0.0
+// comes out as +0.0 under both, see below).  CVAR selects by rank and re-reads the costs instead of sorting a per-lane array: the t-th
+// largest is the value with fewer than t + 1 values ahead of it in the order (larger value, then lower scenario), found by counting --
+// O(tail M^2) loads of M L2-resident values, no run-time-indexed registers.
+SAIP_SAMP_HD inline bool samp_finite(double c) { return fabs(c) <= 1.7976931348623157e308; }  // false for NaN and the infinities
+SAIP_SAMP_HD inline double samp_group_cost(const double* cost, int C, int M, int c, int risk, int tail) {
+#pragma clang fp contract(off)
+	const double* v = cost + c;
+	double sum = 0.0, mx = 0.0;
+	for (int s = 0; s < M; s++) {
+		const double x = v[(size_t)s * C];
+		if (!samp_finite(x)) return INFINITY;
+		sum = sum + x;
+		mx = (s == 0 || x > mx) ? x : mx;
+	}
+	if (risk == SAMP_RISK_MEAN) return sum / (double)M;
+	if (risk == SAMP_RISK_MAX) return 0.0 + mx;  // -0.0 becomes +0.0, as CVAR's first addition makes it
+	double top = 0.0;
+	for (int t = 0; t < tail; t++)
+		for (int s = 0; s < M; s++) {  // the scenario of rank t: exactly t others are ahead of it
+			const double x = v[(size_t)s * C];
+			int ahead = 0;
+			for (int o = 0; o < M; o++) {
+				const double y = v[(size_t)o * C];
+				ahead += (y > x || (y == x && o < s)) ? 1 : 0;
+			}
+			if (ahead == t) {
+				top = top + x;
+				break;
+			}
+		}
+	return top / (double)tail;
+}
+// the best map of a grouped update: every scenario block takes its own copy of the best candidate
+SAIP_SAMP_HD inline int samp_group_map(int i, int C, int best) { return best < 0 ? -1 : (i / C) * C + best; }
+
 // ---- update.  Reduction shape, the same for every sum and for the minimum: lane l of SAMP_LANES takes instances l, l + 256, ... in
 // that order; inside each group of 64 lanes the lane values are folded as v[l] += v[l + off] for off = 32, 16, 8, 4, 2, 1; the four
 // group results are combined as (g0 + g1) + (g2 + g3).
-SAIP_SAMP_HD inline bool samp_finite(double c) { return fabs(c) <= 1.7976931348623157e308; }  // false for NaN and the infinities
 // the smaller of two (cost, index) candidates, the lower index on a tie; index -1: no candidate
 SAIP_SAMP_HD inline void samp_min_combine(double& m, int& im, double o, int io) {
 	if (io >= 0 && (im < 0 || o < m || (o == m && io < im))) {
@@ -291,6 +337,16 @@ SAIP_SAMP_HD inline void samp_shift_column(double* nominal, int K, int count, in
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
+// ---- scenario groups on the host: the grouped perturb and the group-cost kernel, instance by instance and candidate by candidate
+inline void samp_host_perturb_grouped(const SamplerEntry& E, int ld, int B, int C, uint32_t seed_lo, uint32_t seed_hi, uint32_t round) {
+	for (int i = 0; i < B; i++) samp_perturb_candidate(E, ld, i, i % C, seed_lo, seed_hi, round);
+}
+inline void samp_host_group_cost(const double* cost, int C, int M, int risk, int tail, double* group) {
+	for (int c = 0; c < C; c++) group[c] = samp_group_cost(cost, C, M, c, risk, tail);
+}
+inline void samp_host_group_map(int B, int C, int best, int* best_map) {
+	for (int i = 0; i < B; i++) best_map[i] = samp_group_map(i, C, best);
+}
 // ---- the reduction shape on the host: `v` holds the SAMP_LANES lane values (overwritten)
 inline double samp_tree_sum(double* v) {
 	for (int g = 0; g < SAMP_LANES; g += SAMP_WAVE)

@@ -8,6 +8,10 @@
 //                         in the tangent space of the old nominal) becomes the new nominal.  A workgroup reads and writes the nominal
 //                         rows of its own keyframe only.
 //   saip_sampler_shift    the receding-horizon warm start of the nominal plan
+// Scenario groups (B = C M instances: M scenario blocks of C candidates, instance i = s C + c):
+//   saip_sampler_group_cost       one lane per candidate: the M scenario costs of a candidate folded into its group cost
+//   saip_sampler_weights_grouped  saip_sampler_weights over the C group costs, and the best map over all B instances
+// perturb keys the noise by the candidate; update runs unchanged on columns 0 .. C - 1.  With M = 1 neither of the two is launched.
 // No atomics, no device-side counter: weights -> update is ordered by the stream, and every sum has the fixed shape stated in
 // saip_sampler.h (lane l takes instances l, l + 256, ...; a fixed tree over the lanes), so two runs give the same bits.  Every array row
 // is a [ld] run: a wavefront's loads and stores are contiguous; columns B .. ld - 1 are never written.
@@ -20,7 +24,15 @@ namespace saip {
 __global__ void __launch_bounds__(64) saip_sampler_perturb(const SamplerParams P) {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= P.B) return;
-	for (int t = 0; t < P.n; t++) samp_perturb_instance(P.e[t], P.ld, i, P.seed_lo, P.seed_hi, P.round);
+	const int c = P.C == P.B ? i : i % P.C;  // (uniform) the candidate this instance rolls out
+	for (int t = 0; t < P.n; t++) samp_perturb_candidate(P.e[t], P.ld, i, c, P.seed_lo, P.seed_hi, P.round);
+}
+
+// cost [M][C] as rows of the cost array: lane c reads cost[s C + c], contiguous across the wavefront for every s
+__global__ void __launch_bounds__(64) saip_sampler_group_cost(const double* __restrict__ cost, int C, int M, int risk, int tail, double* __restrict__ group) {
+	const int c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= C) return;
+	group[c] = samp_group_cost(cost, C, M, c, risk, tail);
 }
 
 __global__ void __launch_bounds__(64) saip_sampler_cost(const SamplerCostParams P) {
@@ -44,8 +56,10 @@ __device__ __forceinline__ double samp_block_sum(double v, double* part) {
 	return (part[0] + part[1]) + (part[2] + part[3]);
 }
 
-__global__ void __launch_bounds__(SAMP_LANES) saip_sampler_weights(const double* __restrict__ cost, int B, double temperature, double* __restrict__ w,
-																	SamplerResult* __restrict__ res, int* __restrict__ best_map) {
+// GROUPED: B is the number of candidates and the map covers n_map >= B instances in scenario blocks of B
+template <bool GROUPED>
+__device__ __forceinline__ void samp_weights_body(const double* __restrict__ cost, int B, double temperature, double* __restrict__ w,
+												  SamplerResult* __restrict__ res, int* __restrict__ best_map, int n_map) {
 	__shared__ double part[4], pm[4];
 	__shared__ int pi[4], pn[4];
 	const int lane = threadIdx.x;
@@ -80,6 +94,8 @@ __global__ void __launch_bounds__(SAMP_LANES) saip_sampler_weights(const double*
 	sw = samp_block_sum(sw, part);
 	sw2 = samp_block_sum(sw2, part);
 	for (int i = lane; i < B; i += SAMP_LANES) best_map[i] = im;
+	if (GROUPED)
+		for (int i = B + lane; i < n_map; i += SAMP_LANES) best_map[i] = samp_group_map(i, B, im);
 	if (lane == 0) {  // one vector store per field
 		res->best = im;
 		res->n_valid = nv;
@@ -87,6 +103,15 @@ __global__ void __launch_bounds__(SAMP_LANES) saip_sampler_weights(const double*
 		res->sum_w = nv ? sw : 0.0;
 		res->ess = nv ? (sw * sw) / sw2 : 0.0;
 	}
+}
+
+__global__ void __launch_bounds__(SAMP_LANES) saip_sampler_weights(const double* __restrict__ cost, int B, double temperature, double* __restrict__ w,
+																	SamplerResult* __restrict__ res, int* __restrict__ best_map) {
+	samp_weights_body<false>(cost, B, temperature, w, res, best_map, B);
+}
+__global__ void __launch_bounds__(SAMP_LANES) saip_sampler_weights_grouped(const double* __restrict__ group, int C, double temperature, double* __restrict__ w,
+																			SamplerResult* __restrict__ res, int* __restrict__ best_map, int B) {
+	samp_weights_body<true>(group, C, temperature, w, res, best_map, B);
 }
 
 __global__ void __launch_bounds__(SAMP_LANES) saip_sampler_update(const SamplerParams P, const double* __restrict__ w, const SamplerResult* __restrict__ res) {
@@ -139,6 +164,33 @@ hipError_t launch_sampler_update(const SamplerParams& P, const double* cost, dou
 	int Kmax = 0;
 	for (int t = 0; t < P.n; t++) Kmax = P.e[t].K > Kmax ? P.e[t].K : Kmax;
 	hipLaunchKernelGGL(saip_sampler_update, dim3(Kmax, P.n), dim3(SAMP_LANES), 0, stream, P, w, res);
+	return hipGetLastError();
+}
+// P.B = C M with M > 1: group cost, weights over the C group costs with the map over B, update over columns 0 .. C - 1
+hipError_t launch_sampler_update_grouped(const SamplerParams& P, const double* cost, int risk, int tail, double* group, double temperature, double* w, SamplerResult* res,
+										 int* best_map, hipStream_t stream) {
+	const int C = P.C, M = P.B / P.C;
+	hipLaunchKernelGGL(saip_sampler_group_cost, dim3((C + 63) / 64), dim3(64), 0, stream, cost, C, M, risk, tail, group);
+	hipError_t e = hipGetLastError();
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(saip_sampler_weights_grouped, dim3(1), dim3(SAMP_LANES), 0, stream, (const double*)group, C, temperature, w, res, best_map, P.B);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	SamplerParams Pc = P;  // the update kernel sees a batch of C
+	Pc.B = C;
+	int Kmax = 0;
+	for (int t = 0; t < P.n; t++) Kmax = P.e[t].K > Kmax ? P.e[t].K : Kmax;
+	hipLaunchKernelGGL(saip_sampler_update, dim3(Kmax, P.n), dim3(SAMP_LANES), 0, stream, Pc, (const double*)w, (const SamplerResult*)res);
+	return hipGetLastError();
+}
+// Scenario sharing: in `rows` rows of [ld], column i takes the bits of column (i / C) C; source columns and columns B .. ld - 1 stay
+__global__ void __launch_bounds__(64) saip_sampler_share_columns(double* __restrict__ a, int rows, int B, int ld, int C) {
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= B || i % C == 0) return;
+	double* row = a + (size_t)blockIdx.y * ld;
+	for (int r = blockIdx.y; r < rows; r += gridDim.y, row += (size_t)gridDim.y * ld) row[i] = row[i - i % C];
+}
+hipError_t launch_sampler_share_columns(double* a, int rows, int B, int ld, int C, hipStream_t stream) {
+	hipLaunchKernelGGL(saip_sampler_share_columns, dim3((B + 63) / 64, rows < 1024 ? rows : 1024), dim3(64), 0, stream, a, rows, B, ld, C);
 	return hipGetLastError();
 }
 hipError_t launch_sampler_shift(const SamplerParams& P, int n, hipStream_t stream) {

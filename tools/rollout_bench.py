@@ -13,7 +13,9 @@
    --sampler attaches a resident rollout sampler to a 16-keyframe position + orientation schedule of the motion-force task and prints the
    event-timed mean of 50 calls each of perturb, cost and update, and beside them the host round trip they replace: rolloutSummary(), the
    NumPy perturb and update of tests/sampler_ref.py, detach and attach of the new keyframes, by wall clock around a synchronise
-   (DESIGN.md 4.11).
+   (DESIGN.md 4.11).  --sampler --scenarios M [--risk mean|max|cvar] [--alpha A] groups the batch into M scenario blocks of B / M candidates
+   before the timing (M = 1, the default, makes no call at all: the ungrouped sampler of any build) and prints M, the risk and, with
+   M > 1, one shareScenarioTables() call over all five attachments drawn per instance, event-timed the same way.
    --contact [--contact-planes P] [--contact-sensor] [--contact-stack 2|13] [--substeps S] times, interleaved in the same run, the
    closed-loop period without and with contact planes attached to the motion-force task (P planes: a table just under the control point
    and P - 1 far walls), and the integrate call alone both ways; --contact-stack 13 runs config 13's closed-loop force stack
@@ -87,6 +89,9 @@ ap.add_argument("--repeats", type=int, default=1)
 ap.add_argument("--goal-schedule", choices=("hold", "linear"), default=None)
 ap.add_argument("--snapshot", action="store_true")
 ap.add_argument("--sampler", action="store_true")
+ap.add_argument("--scenarios", type=int, default=1, metavar="M")
+ap.add_argument("--risk", choices=("mean", "max", "cvar"), default="mean")
+ap.add_argument("--alpha", type=float, default=None)
 ap.add_argument("--contact", action="store_true")
 ap.add_argument("--contact-planes", type=int, default=1)
 ap.add_argument("--contact-sensor", action="store_true")
@@ -185,6 +190,24 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
         ctrl.seedSampler(1)
         ctrl.rolloutAsync(K, 5e-4, 2, gravity=(0, 0, 0))
         w8, target = np.array([1e-4, 1.0, 1.0, 0, 0, 0, 0, 10.0]), nominal[0, :3] + 0.03
+        grouped = ""
+        if args.scenarios > 1:
+            M, n = args.scenarios, d["model"].dof
+            ctrl.setSamplerScenarios(M, args.risk, args.alpha if args.risk == "cvar" else None)
+            # one share call with all five attachments per instance: tables as the --plant, --inertia and --sensing runs draw them
+            ctrl.attachPlant(np.zeros((n, B, 10)) + [1.0, 0, np.inf, 0, 0, 0, -np.inf, np.inf, 0, 0], wrenches=[(d["tasks"][0]["link"], (0, 0, 0), "world", np.zeros((B, 8)))],
+                             per_instance=True)
+            ctrl.attachActuationChain(np.zeros((n, B, 3)) + [0.0, np.inf, 0.0], per_instance=True, depth=2)
+            ctrl.attachInertia(per_instance=True, payload_links=[d["tasks"][0]["link"]])
+            ctrl.attachSensing(joints=np.zeros((n, B, 6)), per_instance=True)
+            ctrl.attachSensingChain(np.zeros((n, B, 4)), per_instance=True, depth=2)
+            ctrl.randomizePlant(1, 0, joints=(np.tile([0.8, 0, np.inf, 0, 0, 0, -np.inf, np.inf, 0, 0], (n, 1)), np.tile([1.0, 0, np.inf, 0.1, 0, 0, -np.inf, np.inf, 0, 0], (n, 1))))
+            ctrl.randomizeInertia(2, 0, bodies=(np.tile([0.8, 0, 0, 0], (n, 1)), np.tile([1.2, 0, 0, 0], (n, 1))))
+            ctrl.sensingRandomize(3, 0, joints=(np.tile([-1e-3, 0, 0, -1e-3, 0, 0], (n, 1)), np.tile([1e-3, 0, 0, 1e-3, 0, 0], (n, 1))))
+            share_us, arrays = timed_us(ctrl.shareScenarioTables), ctrl.shareScenarioTables()
+            for detach in (ctrl.detachSensingChain, ctrl.detachSensing, ctrl.detachInertia, ctrl.detachPlant):
+                detach()
+            grouped = f"; scenarios {M} x {B // M} candidates, risk {args.risk}; share of {arrays} arrays {share_us:.1f} us"
 
         def host_round(rnd):
             S = ctrl.rolloutSummary()
@@ -207,9 +230,11 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
                 host_round(i)
             host = (time.perf_counter() - t0) / 3 * 1e6
             mf.attachSampler(sigma, nominal=nominal, exempt=1)
+            if args.scenarios > 1:                         # the detach above reset the setting
+                ctrl.setSamplerScenarios(args.scenarios, args.risk, args.alpha if args.risk == "cvar" else None)
             print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'}: sampler, {KF} keyframes of position + "
                   f"orientation: perturb {t['perturb']:.1f} us; cost {t['cost']:.1f} us; update {t['update']:.1f} us; host round trip (summary, NumPy perturb + "
-                  f"update, detach + attach) {host:.0f} us")
+                  f"update, detach + attach) {host:.0f} us{grouped}")
         continue
     if args.contact:
         P, sub = args.contact_planes, args.substeps
