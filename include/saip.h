@@ -534,6 +534,53 @@ double* saip_batch_clearance_summary_device(saip_batch*);    /* [4][ld]; NULL wh
 saip_status saip_batch_clearance_summary_reset(saip_batch*);
 double* saip_batch_clearance_centres_device(saip_batch*);    /* [3 S][ld]; NULL unless keep_centres */
 saip_status saip_batch_clearance_add_cost(saip_batch*, double w_penalty, double w_collision, double d_safe);
+/* ---- environment schedules: moving obstacles and contact surfaces inside rollouts.  What goal schedules are to the goals: the obstacle
+ * table of the clearance monitor, the single-point contact planes and the planes of a contact patch become functions of the rollout
+ * period, written from keyframes resident on the device by ONE launch at the head of every period of saip_batch_rollout_async.  At most
+ * SAIP_ENV_MAX_SCHEDULES per batch, one per table.
+ *   target    SAIP_ENV_TARGET_OBSTACLES, _PLANES, or _PATCH (the planes of the patch on `task`; -1: the first patch; ignored otherwise).
+ *   items     the schedule covers items [first, first + n_items) of the table; the others are never written.
+ *   keyframes [K][n_items][W], or [K][n_items][W][B] when the target table is per instance (the layout of the target's own _set_*_host call
+ *             with a leading keyframe index).  W = 8 for an obstacle; W = SAIP_ENV_PLANE_WORDS for a plane: the eight plane words, a
+ *             surface velocity u[3] in the base frame, and one reserved word that must be 0.  Plane normals are normalised as the plane
+ *             table's are.
+ *   timing    the schedule has its own period counter c (0 after _attach; _rewind sets it to any period, so that a receding-horizon
+ *             round starts its prediction at the current time).  A schedule that sees the period index x reads i = x / stride and
+ *             s = (x % stride) / stride, the last keyframe held.  Contact targets see x = c: the planes are held through the period's
+ *             substeps, as a goal is.  The clearance target sees x = c + 1: the monitor runs behind the period's integration and
+ *             looks at the obstacle at the time of the state it looks at.
+ *   modes     SAIP_ENV_HOLD writes keyframe i.  SAIP_ENV_LINEAR writes a + s (b - a) per word, the difference, product and sum each
+ *             rounded once; at s == 0 the row is a exactly; an obstacle's kind is a's; a unit normal (half-space, plane) is interpolated
+ *             the same way and divided by its length.  csrc/saip_env_schedule.h; tests/env_schedule_ref.py restates it bit for bit.
+ *   velocity  for every scheduled plane the launch also writes { v_p[3], w_n } to the velocity table [P][4] / [P][4][ld]:
+ *             v_p = u + w_n n, w_n = (o_b - o_a) / (stride T) in LINEAR between two keyframes (T = sim_dt x substeps), 0 in HOLD and
+ *             past the last keyframe.  The rotation of a normal contributes no velocity.  While the planes of a contact attachment have
+ *             a schedule, its SENSE and APPLY launches (rollouts, saip_batch_integrate, _sense) take v - v_p in place of the point's
+ *             velocity in damping and friction; with v_p = 0 they give the bits of the static planes.
+ * saip_batch_step_async, saip_batch_integrate and saip_batch_clearance_evaluate apply no schedule: they read tables and velocities as last
+ * written.  Without a schedule every entry point enqueues exactly what it did before.  A state snapshot is unchanged: tables are
+ * configuration; pair a restore with _rewind(period).  Detaching the contact planes, a patch or the clearance monitor releases the schedule
+ * on its table first; _set_planes_host / _set_obstacles_host on a scheduled table return SAIP_ERR_ORDER.
+ * SAIP_ERR_ORDER: the target is not attached, a second schedule on a table, any other entry without that schedule.
+ * SAIP_ERR_INVALID_ARGUMENT (the message says what): unknown target or mode, n_keyframes < 1, stride < 1, null keyframes, an item range
+ * outside the table, a word that is not finite, a reserved word that is not 0, a plane the plane table would refuse, a half-space
+ * normal off unit length by more than 1e-6, an obstacle whose kind differs between keyframes, in LINEAR two consecutive normals with
+ * n_a . n_b < 0, a negative period.  Argument and order errors are reported before the device is needed. */
+#define SAIP_ENV_MAX_SCHEDULES 4
+#define SAIP_ENV_PLANE_WORDS 12
+#define SAIP_ENV_TARGET_OBSTACLES 0
+#define SAIP_ENV_TARGET_PLANES 1
+#define SAIP_ENV_TARGET_PATCH 2
+#define SAIP_ENV_HOLD 0
+#define SAIP_ENV_LINEAR 1
+saip_status saip_batch_env_schedule_attach(saip_batch*, int target, int task, int first, int n_items, const double* keyframes, int n_keyframes,
+                                           int stride, int mode);
+saip_status saip_batch_env_schedule_detach(saip_batch*, int target /* -1: every schedule */, int task);
+saip_status saip_batch_env_schedule_rewind(saip_batch*, long long period);
+saip_status saip_batch_env_schedule_info(saip_batch*, int target, int task, int* first, int* n_items, int* n_keyframes, int* stride, int* mode,
+                                         int* per_instance, long long* period);  /* any NULL */
+double* saip_batch_env_schedule_keyframes_device(saip_batch*, int target, int task);  /* NULL without that schedule */
+double* saip_batch_env_schedule_velocity_device(saip_batch*, int target, int task);   /* [P][4] or [P][4][ld]; NULL for obstacles */
 /* ---- plant model: what stands between the commanded torques and the integrator when the robot is not the controller's model --
  * actuator gain, offset and saturation, viscous and Coulomb friction, penalty joint stops and external wrenches on links.  One attachment
  * per batch.  Nothing in it is state: it is configuration plus a host-side period counter, not part of a state snapshot.

@@ -373,6 +373,19 @@ public:
 		check(saip_batch_contact_info(_batch, &task, n_planes, per_instance, nullptr, nullptr));
 		if (task != _id) throw std::runtime_error("the contact planes of this controller are attached to another task");
 	}
+	int contactTarget(int* per_instance = nullptr) {  // whichever of contact planes or contact patch THIS task has, as an environment-schedule target
+		need();
+		int task = -1, per = 0;
+		if (saip_batch_contact_info(_batch, &task, nullptr, &per, nullptr, nullptr) == SAIP_OK && task == _id) {
+			if (per_instance) *per_instance = per;
+			return SAIP_ENV_TARGET_PLANES;
+		}
+		if (saip_batch_contact_patch_info(_batch, _id, nullptr, nullptr, nullptr, &per, nullptr, nullptr) == SAIP_OK) {
+			if (per_instance) *per_instance = per;
+			return SAIP_ENV_TARGET_PATCH;
+		}
+		throw std::runtime_error("this task has neither contact planes nor a contact patch");
+	}
 	void attachSampler(const std::vector<double>& sigma, const std::vector<double>& nominal = {}, int exempt = 1) {
 		need();
 		int first = 0, count = 0, nk = 0;
@@ -495,6 +508,28 @@ public:
 		need();
 		check(saip_batch_contact_patch_summary_reset(_batch, _id));
 	}
+	// ---- environment schedule of this task's contact surfaces (saip.h): the planes of its contact planes or of its contact patch, whichever
+	// it has, move during rollouts.  keyframes: [K][n][12] rows { n[3], offset, k, c, mu, v_s, u[3], 0 } (u: the velocity of the surface in the
+	// base frame), or [K][n][12][B] when the planes are per instance; the schedule covers planes first .. first + n - 1.
+	struct EnvScheduleInfo {
+		int first = 0, n_items = 0, n_keyframes = 0, stride = 1, mode = 0, per_instance = 0;
+		long long period = 0;
+	};
+	void setContactSchedule(const std::vector<double>& keyframes, int n_keyframes, int stride = 1, int mode = SAIP_ENV_HOLD, int first = 0) {
+		int per = 0;
+		const int target = contactTarget(&per);
+		const size_t frame = (size_t)SAIP_ENV_PLANE_WORDS * (per ? (size_t)saip_batch_size(_batch) : 1);
+		if (n_keyframes < 1 || keyframes.empty() || keyframes.size() % ((size_t)n_keyframes * frame) != 0)
+			throw std::invalid_argument("setContactSchedule: expected [K][n][12] keyframes, or [K][n][12][B] when the planes are per instance");
+		check(saip_batch_env_schedule_attach(_batch, target, _id, first, (int)(keyframes.size() / ((size_t)n_keyframes * frame)), keyframes.data(), n_keyframes, stride, mode));
+	}
+	void clearContactSchedule() { check(saip_batch_env_schedule_detach(_batch, contactTarget(), _id)); }
+	EnvScheduleInfo contactScheduleInfo() {
+		EnvScheduleInfo i;
+		check(saip_batch_env_schedule_info(_batch, contactTarget(), _id, &i.first, &i.n_items, &i.n_keyframes, &i.stride, &i.mode, &i.per_instance, &i.period));
+		return i;
+	}
+	double* contactVelocityDevice() { return saip_batch_env_schedule_velocity_device(_batch, contactTarget(), _id); }  // [P][4] or [P][4][ld]; nullptr without a schedule
 	std::vector<double> samplerNominal() {
 		need();
 		check(saip_batch_sampler_info(_batch, _id, nullptr, nullptr, nullptr, nullptr));
@@ -1290,6 +1325,27 @@ public:
 	void clearanceCost(double w_penalty, double w_collision = std::numeric_limits<double>::infinity(), double d_safe = 0.0) {
 		check(saip_batch_clearance_add_cost(_batch, w_penalty, w_collision, d_safe));
 	}
+	// ---- environment schedules: obstacles and contact surfaces that move inside rollouts (saip.h; the contact side: task->setContactSchedule).
+	// keyframes: [K][n][8] obstacle rows, or [K][n][8][B] when the obstacle table is per instance.  The monitor of rollout period c looks at
+	// the state at the END of the period, so it sees the obstacles of period index c + 1; the last keyframe is held.
+	void setObstacleSchedule(const std::vector<double>& keyframes, int n_keyframes, int stride = 1, int mode = SAIP_ENV_HOLD, int first = 0) {
+		const ClearanceInfo ci = clearanceInfo();
+		const size_t frame = (size_t)SAIP_CLEARANCE_OBSTACLE_WORDS * (ci.per_instance ? (size_t)saip_batch_size(_batch) : 1);
+		if (n_keyframes < 1 || keyframes.empty() || keyframes.size() % ((size_t)n_keyframes * frame) != 0)
+			throw std::invalid_argument("setObstacleSchedule: expected [K][n][8] keyframes, or [K][n][8][B] when the obstacles are per instance");
+		check(saip_batch_env_schedule_attach(_batch, SAIP_ENV_TARGET_OBSTACLES, -1, first, (int)(keyframes.size() / ((size_t)n_keyframes * frame)), keyframes.data(),
+											 n_keyframes, stride, mode));
+	}
+	void clearObstacleSchedule() { check(saip_batch_env_schedule_detach(_batch, SAIP_ENV_TARGET_OBSTACLES, -1)); }
+	TemplateTask::EnvScheduleInfo obstacleScheduleInfo() {
+		TemplateTask::EnvScheduleInfo i;
+		check(saip_batch_env_schedule_info(_batch, SAIP_ENV_TARGET_OBSTACLES, -1, &i.first, &i.n_items, &i.n_keyframes, &i.stride, &i.mode, &i.per_instance, &i.period));
+		return i;
+	}
+	void clearEnvironmentSchedules() { check(saip_batch_env_schedule_detach(_batch, -1, -1)); }
+	// the next rollout period is period `period` of the environment schedules: 0 to replay them, the current period to start a
+	// receding-horizon prediction at the current time; what goes with restoreState (tables are not part of a snapshot)
+	void rewindEnvironment(long long period = 0) { check(saip_batch_env_schedule_rewind(_batch, period)); }
 
 	// ---- plant model: actuator limits, friction, joint stops and external wrenches between the commanded torques and the resident
 	// simulator (saip.h).  While attached, integrate() and rolloutAsync() run it in front of every substep (and in front of the contact

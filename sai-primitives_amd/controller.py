@@ -997,6 +997,42 @@ class MotionForceTask(_Task):
         """zero this patch's summaries on the stream (what goes with a snapshot restore: the summaries are not part of a snapshot)"""
         self._need_ctrl()._call("saip_batch_contact_patch_summary_reset", self._id)
 
+    # -- environment schedule of this task's contact surfaces: planes that move inside rollouts (saip.h)
+    def _contact_target(self, who):
+        """(target, per_instance) of whichever of contact planes or contact patch this task has"""
+        ctrl = self._need_ctrl()
+        L, v = capi.lib(), [C.c_int(0) for _ in range(5)]
+        if L.saip_batch_contact_info(ctrl._h, C.byref(v[0]), None, C.byref(v[2]), None, None) == capi.SAIP_OK and v[0].value == self._id:
+            return capi.SAIP_ENV_TARGET_PLANES, bool(v[2].value)
+        if L.saip_batch_contact_patch_info(ctrl._h, self._id, None, None, None, C.byref(v[3]), None, None) == capi.SAIP_OK:
+            return capi.SAIP_ENV_TARGET_PATCH, bool(v[3].value)
+        raise capi.SaipError(f"{who}: task [{self.getTaskName()}] has neither contact planes nor a contact patch")
+
+    def setContactSchedule(self, keyframes, stride=1, mode="hold", first=0):
+        """let the planes of this task's contact planes or contact patch move during rollouts.  keyframes: (K, n, 12), or (K, n, B, 12) when
+        the planes are per instance, rows { n[3], offset, k, c, mu, v_s, u[3], 0 }: the eight plane words and the velocity u of the
+        surface in the base frame (a conveyor).  Period c of a rollout uses keyframe c // stride ("hold") or goes from it towards the next
+        by (c % stride) / stride ("linear"); the last keyframe is held.  The schedule covers planes first .. first + n - 1.  In "linear"
+        a moving offset gives the surface its normal velocity; damping and friction act on the velocity relative to the surface."""
+        ctrl = self._need_ctrl()
+        target, per = self._contact_target("setContactSchedule")
+        ctrl._env_schedule_attach("setContactSchedule", target, self._id, keyframes, capi.SAIP_ENV_PLANE_WORDS, per, stride, mode, first)
+
+    def clearContactSchedule(self):
+        """detach the schedule; the planes keep the values written last"""
+        target, _ = self._contact_target("clearContactSchedule")
+        self._need_ctrl()._call("saip_batch_env_schedule_detach", target, self._id)
+
+    def contactScheduleInfo(self):
+        """dict first, n_items, n_keyframes, stride, mode, per_instance, period"""
+        target, _ = self._contact_target("contactScheduleInfo")
+        return self._need_ctrl()._env_schedule_info(target, self._id)
+
+    def contactVelocityDevice(self):
+        """device pointer of the surface velocities the schedule writes, (P, 4) or (P, 4, ld) rows { v_p[3], w_n }; None without a schedule"""
+        target, _ = self._contact_target("contactVelocityDevice")
+        return capi.lib().saip_batch_env_schedule_velocity_device(self._need_ctrl()._h, target, self._id)
+
     def updateSensedForceAndMoment(self, sensed_force_sensor_frame, sensed_moment_sensor_frame):  # MotionForceTask.cpp:805-828
         self._set_field(30, 3, sensed_force_sensor_frame, "updateSensedForceAndMoment (force)")
         self._set_field(33, 3, sensed_moment_sensor_frame, "updateSensedForceAndMoment (moment)")
@@ -1723,6 +1759,57 @@ class RobotController:
         """cost += w_penalty * summary penalty + (min_distance < d_safe ? w_collision : 0) on the device, after rolloutCost(); an infinite
         cost is an invalid sample to updateSampler(), so the default w_collision makes collision a hard constraint"""
         self._call("saip_batch_clearance_add_cost", float(w_penalty), float(w_collision), float(d_safe))
+
+    # -- environment schedules: obstacles and contact surfaces that move inside rollouts (saip.h)
+    _ENV_MODES = {"hold": capi.SAIP_ENV_HOLD, "linear": capi.SAIP_ENV_LINEAR}
+
+    def _env_schedule_attach(self, who, target, task, keyframes, W, per_instance, stride, mode, first):
+        if mode not in self._ENV_MODES:
+            raise ValueError(f"{who}: unknown mode {mode!r} (one of {sorted(self._ENV_MODES)})")
+        k, B = np.asarray(keyframes, float), self.batch_size
+        if per_instance:
+            if k.ndim != 4 or k.shape[2:] != (B, W):
+                raise ValueError(f"{who}: the table is per instance: keyframes of shape (K, n, {B}, {W}) expected, got {k.shape}")
+            a = np.ascontiguousarray(k.transpose(0, 1, 3, 2))
+        else:
+            if k.ndim != 3 or k.shape[2] != W:
+                raise ValueError(f"{who}: the table is batch-uniform: keyframes of shape (K, n, {W}) expected, got {k.shape}")
+            a = np.ascontiguousarray(k)
+        self._call("saip_batch_env_schedule_attach", target, task, int(first), a.shape[1], _dptr(a), a.shape[0], int(stride), self._ENV_MODES[mode])
+
+    def _env_schedule_info(self, target, task):
+        v = [C.c_int(0) for _ in range(6)]
+        period = C.c_longlong(0)
+        self._call("saip_batch_env_schedule_info", target, task, *(C.byref(x) for x in v), C.byref(period))
+        mode = {m: name for name, m in self._ENV_MODES.items()}[v[4].value]
+        return dict(first=v[0].value, n_items=v[1].value, n_keyframes=v[2].value, stride=v[3].value, mode=mode, per_instance=bool(v[5].value),
+                    period=period.value)
+
+    def setObstacleSchedule(self, keyframes, stride=1, mode="hold", first=0):
+        """let the obstacles of the clearance monitor move during rollouts.  keyframes: (K, n, 8), or (K, n, B, 8) when the obstacle table is
+        per instance, rows as in attachClearance.  The monitor of rollout period c looks at the state at the END of the period, so it sees
+        keyframe (c + 1) // stride ("hold") or that one moved towards the next by ((c + 1) % stride) / stride ("linear"; half-space
+        normals stay unit); the last keyframe is held.  The schedule covers obstacles first .. first + n - 1."""
+        info = self.clearanceInfo()
+        self._env_schedule_attach("setObstacleSchedule", capi.SAIP_ENV_TARGET_OBSTACLES, -1, keyframes, capi.SAIP_CLEARANCE_OBSTACLE_WORDS,
+                                  info["per_instance"], stride, mode, first)
+
+    def clearObstacleSchedule(self):
+        """detach the schedule; the obstacles keep the values written last"""
+        self._call("saip_batch_env_schedule_detach", capi.SAIP_ENV_TARGET_OBSTACLES, -1)
+
+    def obstacleScheduleInfo(self):
+        """dict first, n_items, n_keyframes, stride, mode, per_instance, period"""
+        return self._env_schedule_info(capi.SAIP_ENV_TARGET_OBSTACLES, -1)
+
+    def clearEnvironmentSchedules(self):
+        """detach every environment schedule of the controller"""
+        self._call("saip_batch_env_schedule_detach", -1, -1)
+
+    def rewindEnvironment(self, period=0):
+        """the next rollout period is period `period` of the environment schedules: 0 to replay them, the current period to start a
+        receding-horizon prediction at the current time; what goes with restoreState (tables are not part of a snapshot)"""
+        self._call("saip_batch_env_schedule_rewind", int(period))
 
     # -- plant model: actuator limits, friction, joint stops and external wrenches in front of every integration substep (saip.h)
     PLANT_JOINT_WORDS = ("gain", "bias", "tau_max", "fv", "fc", "v_s", "q_lo", "q_hi", "k_stop", "c_stop")

@@ -102,6 +102,42 @@ SAIP_CT_HD inline void ct_plane_forces(const double* planes, int n_planes, long 
 	out->active = active;
 }
 
+// The same against moving surfaces (saip_env_schedule.h): plane k has the velocity v_p = vel[(k * 4 + e) * stride + col], e = 0..2, in the
+// layout of the planes, and v_r = v - v_p (one rounding per component) takes the place of v in v_n, f_n, v_t and f_t.  With v_p = 0 these are
+// the bits of ct_plane_forces.
+SAIP_CT_HD inline void ct_plane_forces_moving(const double* planes, const double* vel, int n_planes, long long stride, long long col, const double* p,
+											   const double* v, ContactForce* out) {
+#pragma clang fp contract(off)
+	double f[3] = {0.0, 0.0, 0.0}, fn_sum = 0.0, dmin = 0.0;
+	int active = 0;
+	for (int k = 0; k < n_planes; k++) {
+		const double* w = planes + (long long)k * CONTACT_PLANE_WORDS * stride + col;
+		const double* vp = vel + (long long)k * 4 * stride + col;
+		const double n[3] = {w[0], w[stride], w[2 * stride]};
+		const double off = w[3 * stride], ks = w[4 * stride], cd = w[5 * stride], mu = w[6 * stride], vs = w[7 * stride];
+		const double d = ct_dot(n, p) - off;
+		if (k == 0 || d < dmin) dmin = d;
+		if (!(d < 0.0)) continue;
+		active++;
+		const double vr[3] = {v[0] - vp[0], v[1] - vp[stride], v[2] - vp[2 * stride]};
+		const double vn = ct_dot(n, vr);
+		const double fn = fmax(0.0, -ks * d - cd * vn);
+		double vt[3];
+		for (int e = 0; e < 3; e++) vt[e] = vr[e] - vn * n[e];
+		const double s = fmax(sqrt(ct_dot(vt, vt)), vs);
+		const double g = mu * fn;
+		for (int e = 0; e < 3; e++) {
+			const double ft = -(g * vt[e]) / s;
+			f[e] = f[e] + (fn * n[e] + ft);
+		}
+		fn_sum = fn_sum + fn;
+	}
+	for (int e = 0; e < 3; e++) out->f[e] = f[e];
+	out->fn_sum = fn_sum;
+	out->dmin = dmin;
+	out->active = active;
+}
+
 // tau_ext of one joint (column of J_v^T times f): aw the joint's world axis, oj its origin; revolute aw . ((p - oj) x f), prismatic aw . f.
 // A joint that is not an ancestor of the body gets 0: the caller does not ask.
 SAIP_CT_HD inline double ct_joint_torque(bool revolute, const double* aw, const double* oj, const double* p, const double* f) {
@@ -161,6 +197,10 @@ struct ContactParams {
 	double* tau_sim;             // APPLY: [n][ld] commanded + contact torques
 	double* readout;             // [8][ld]: f 3, p 3, smallest d, active planes
 	double* summary;             // APPLY: [4][ld]
+};
+// ... of its MOVING instantiation: the planes have an environment schedule, which writes their velocities
+struct ContactMovingParams : ContactParams {
+	const double* vel;           // [P][4] or [P][4][ld]
 };
 
 }  // namespace saip

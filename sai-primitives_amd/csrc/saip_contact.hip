@@ -7,15 +7,18 @@
 // joint's world axis and origin at hand again and nothing per joint is kept in between (no per-lane arrays, no scratch).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "saip_contact.h"
 #include "saip_fk.h"
 
 namespace saip {
 
 // Every array is [rows][ld], so a wavefront's loads and stores are contiguous.  TREE: kinematic trees -- the walk over the ancestors of the
-// task's body only; the other joints get no contact torque.
-template <bool TREE>
-__global__ void __launch_bounds__(64) saip_contact_apply(const ContactParams P) {
+// task's body only; the other joints get no contact torque.  MOVING: the planes have an environment schedule -- the force is taken against
+// the surface velocities it writes (ct_plane_forces_moving); everything else is the same text.
+template <bool TREE, bool MOVING = false>
+__global__ void __launch_bounds__(64) saip_contact_apply(const std::conditional_t<MOVING, ContactMovingParams, ContactParams> P) {
 	const int b = blockIdx.x * blockDim.x + threadIdx.x;
 	if (b >= P.B) return;
 	const ModelDev& md = *P.model;
@@ -31,7 +34,8 @@ __global__ void __launch_bounds__(64) saip_contact_apply(const ContactParams P) 
 	ct_point(pos, Rc, P.rc, pc);
 	ct_velocity(tv, tw, tc, pc, vc);
 	ContactForce c;
-	ct_plane_forces(P.planes, P.n_planes, P.per_instance ? (long long)ld : 1, P.per_instance ? (long long)b : 0, pc, vc, &c);
+	if constexpr (MOVING) ct_plane_forces_moving(P.planes, P.vel, P.n_planes, P.per_instance ? (long long)ld : 1, P.per_instance ? (long long)b : 0, pc, vc, &c);
+	else ct_plane_forces(P.planes, P.n_planes, P.per_instance ? (long long)ld : 1, P.per_instance ? (long long)b : 0, pc, vc, &c);
 	double* ro = P.readout + b;
 	for (int e = 0; e < 3; e++) {
 		ro[(size_t)e * ld] = c.f[e];
@@ -78,6 +82,11 @@ __global__ void __launch_bounds__(64) saip_contact_apply(const ContactParams P) 
 hipError_t launch_contact_apply(const ContactParams& P, bool tree, hipStream_t stream) {
 	if (tree) hipLaunchKernelGGL(saip_contact_apply<true>, dim3((P.B + 63) / 64), dim3(64), 0, stream, P);
 	else hipLaunchKernelGGL(saip_contact_apply<false>, dim3((P.B + 63) / 64), dim3(64), 0, stream, P);
+	return hipGetLastError();
+}
+hipError_t launch_contact_apply_moving(const ContactMovingParams& P, bool tree, hipStream_t stream) {
+	if (tree) hipLaunchKernelGGL((saip_contact_apply<true, true>), dim3((P.B + 63) / 64), dim3(64), 0, stream, P);
+	else hipLaunchKernelGGL((saip_contact_apply<false, true>), dim3((P.B + 63) / 64), dim3(64), 0, stream, P);
 	return hipGetLastError();
 }
 

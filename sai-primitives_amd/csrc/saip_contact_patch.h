@@ -45,6 +45,18 @@ SAIP_CT_HD inline void cp_slot_eval(const double* planes, int n_planes, long lon
 	ct_cross(d, s->c.f, s->m);
 	s->dcand = s->c.dmin;
 }
+// ... against moving surfaces: cp_slot_eval with ct_plane_forces_moving and the planes' velocity table (layout: the planes')
+SAIP_CT_HD inline void cp_slot_eval_moving(const double* planes, const double* vel, int n_planes, long long stride, long long col, const double* xc,
+											const double* Rc, const double* r, const double* tv, const double* tw, const double* tc, PatchSlot* s) {
+#pragma clang fp contract(off)
+	double v[3], d[3];
+	ct_point(xc, Rc, r, s->p);
+	ct_velocity(tv, tw, tc, s->p, v);
+	ct_plane_forces_moving(planes, vel, n_planes, stride, col, s->p, v, &s->c);
+	for (int e = 0; e < 3; e++) d[e] = s->p[e] - xc[e];
+	ct_cross(d, s->c.f, s->m);
+	s->dcand = s->c.dmin;
+}
 // the order of the smallest-distance fold: candidate (db, ib) replaces (da, ia) when it is deeper, or as deep with the lower index
 SAIP_CT_HD inline bool cp_deeper(double db, int ib, double da, int ia) { return db < da || (db == da && ib < ia); }
 
@@ -147,6 +159,10 @@ struct ContactPatchParams {
 	const double* tau_cmd;          // APPLY: [n][ld] commanded torques (NaN = none)
 	double* tau_sim;                // APPLY: [n][ld] (commanded + patch 0) + patch 1
 	PatchDev patch[PATCH_MAX];
+};
+// ... of its MOVING instantiation: the planes of at least one patch have an environment schedule
+struct ContactPatchMovingParams : ContactPatchParams {
+	const double* vel[PATCH_MAX];   // per patch [P][4] or [P][4][ld]; nullptr: the planes of that patch stand still
 };
 
 }  // namespace saip

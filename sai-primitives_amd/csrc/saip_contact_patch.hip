@@ -11,6 +11,8 @@
 // torque on the joint at hand, and only for the groups in which a point touches.  Nothing per joint or per point is kept in an array.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "saip_contact_patch.h"
 #include "saip_fk.h"
 
@@ -30,8 +32,10 @@ __device__ __forceinline__ int cp_lane_sum(int v) {
 	return v;
 }
 
-template <bool TREE>
-__global__ void __launch_bounds__(64) saip_contact_patch_apply(const ContactPatchParams P) {
+// MOVING: the planes of a patch may have an environment schedule -- such a patch is evaluated against the surface velocities it writes
+// (cp_slot_eval_moving); everything else is the same text.
+template <bool TREE, bool MOVING = false>
+__global__ void __launch_bounds__(64) saip_contact_patch_apply(const std::conditional_t<MOVING, ContactPatchMovingParams, ContactPatchParams> P) {
 	const int lane = threadIdx.x & 7;
 	const int inst = blockIdx.x * 8 + (threadIdx.x >> 3);
 	// a group beyond B evaluates instance B - 1 again and stores nothing: every lane of the wavefront takes every shuffle
@@ -52,7 +56,14 @@ __global__ void __launch_bounds__(64) saip_contact_patch_apply(const ContactPatc
 		PatchSlot s;
 		if (lane < pd.n_points) {
 			const double rl[3] = {pd.r[lane][0], pd.r[lane][1], pd.r[lane][2]};
-			cp_slot_eval(pd.planes, pd.n_planes, pd.per_instance ? (long long)ld : 1, pd.per_instance ? (long long)b : 0, pos, Rc, rl, tv, tw, tc, &s);
+			bool moved = false;
+			if constexpr (MOVING) {
+				if (P.vel[ip]) {
+					cp_slot_eval_moving(pd.planes, P.vel[ip], pd.n_planes, pd.per_instance ? (long long)ld : 1, pd.per_instance ? (long long)b : 0, pos, Rc, rl, tv, tw, tc, &s);
+					moved = true;
+				}
+			}
+			if (!moved) cp_slot_eval(pd.planes, pd.n_planes, pd.per_instance ? (long long)ld : 1, pd.per_instance ? (long long)b : 0, pos, Rc, rl, tv, tw, tc, &s);
 		} else {
 			cp_slot_unused(&s);
 		}
@@ -133,6 +144,12 @@ hipError_t launch_contact_patch_apply(const ContactPatchParams& P, bool tree, hi
 	const unsigned blocks = (unsigned)(((long long)P.B + 7) / 8);
 	if (tree) hipLaunchKernelGGL(saip_contact_patch_apply<true>, dim3(blocks), dim3(64), 0, stream, P);
 	else hipLaunchKernelGGL(saip_contact_patch_apply<false>, dim3(blocks), dim3(64), 0, stream, P);
+	return hipGetLastError();
+}
+hipError_t launch_contact_patch_apply_moving(const ContactPatchMovingParams& P, bool tree, hipStream_t stream) {
+	const unsigned blocks = (unsigned)(((long long)P.B + 7) / 8);
+	if (tree) hipLaunchKernelGGL((saip_contact_patch_apply<true, true>), dim3(blocks), dim3(64), 0, stream, P);
+	else hipLaunchKernelGGL((saip_contact_patch_apply<false, true>), dim3(blocks), dim3(64), 0, stream, P);
 	return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@ static saip_status need_clearance(const saip_batch* b, const char* fn) {
 }
 void saip::eng::clearance_free(saip_batch* b) {
 	auto& C = b->clearance;
+	env_release(b, saip::ENV_TARGET_OBSTACLES, -1);  // an environment schedule writes into the obstacles: it goes first
 	for (void* p : {(void*)C.geom_dev, (void*)C.obst, (void*)C.readout, (void*)C.summary, (void*)C.centres})
 		if (p) (void)hipFree(p);
 	C = saip_batch::Clearance();
@@ -156,6 +157,8 @@ extern "C" saip_status saip_batch_clearance_set_obstacles_host(saip_batch* b, co
 	const auto& C = b->clearance;
 	if (C.geom.O == 0) return fail(SAIP_ERR_ORDER, "%s: the monitor was attached without obstacles", fn);
 	if (!obstacles) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null obstacles", fn);
+	if (env_slot(b, saip::ENV_TARGET_OBSTACLES, -1) >= 0)
+		return fail(SAIP_ERR_ORDER, "%s: the obstacles are written by an environment schedule (saip_batch_env_schedule_detach first)", fn);
 	char msg[160];
 	if (!clearance_check_obstacles(obstacles, C.geom.O, C.per_instance ? (size_t)b->B : 1, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, msg);
 	if ((st = need_ready(b, fn))) return st;

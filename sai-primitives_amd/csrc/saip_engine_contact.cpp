@@ -9,12 +9,13 @@ static saip_status need_contact(const saip_batch* b, const char* fn) {
 }
 void saip::eng::contact_free(saip_batch* b) {
 	auto& C = b->contact;
+	env_release(b, saip::ENV_TARGET_PLANES, -1);  // an environment schedule writes into the planes: it goes first
 	for (void* p : {(void*)C.planes, (void*)C.tau_sim, (void*)C.readout, (void*)C.summary})
 		if (p) (void)hipFree(p);
 	C = saip_batch::Contact();
 }
 // the plane table as the device keeps it: [P][8] or [P][8][B] with every normal normalised; nullptr: fine, else what is wrong
-static const char* contact_check_planes(const double* planes, int P, size_t cols, std::vector<double>& out) {
+const char* saip::eng::contact_check_planes(const double* planes, int P, size_t cols, std::vector<double>& out) {
 	out.assign(planes, planes + (size_t)P * saip::CONTACT_PLANE_WORDS * cols);
 	for (size_t i = 0; i < out.size(); i++)
 		if (!std::isfinite(out[i])) return "a plane value is not finite";
@@ -107,6 +108,8 @@ extern "C" saip_status saip_batch_contact_set_planes_host(saip_batch* b, const d
 	saip_status st = need_contact(b, fn);
 	if (st) return st;
 	if (!planes) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null planes", fn);
+	if (env_slot(b, saip::ENV_TARGET_PLANES, -1) >= 0)
+		return fail(SAIP_ERR_ORDER, "%s: the planes are written by an environment schedule (saip_batch_env_schedule_detach first)", fn);
 	const auto& C = b->contact;
 	std::vector<double> host;
 	if (const char* bad = contact_check_planes(planes, C.n_planes, C.per_instance ? (size_t)b->B : 1, host)) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, bad);
@@ -121,7 +124,7 @@ extern "C" double* saip_batch_contact_summary_device(saip_batch* b) { return b ?
 saip_status saip::eng::contact_launch(saip_batch* b, int mode, double dt) {
 	const auto& C = b->contact;
 	if (saip_status st = ensure_task_constants(b)) return st;
-	saip::ContactParams P;
+	saip::ContactMovingParams P;  // (the static launch takes its ContactParams part)
 	memset(&P, 0, sizeof(P));
 	P.B = b->B;
 	P.ld = b->ld;
@@ -142,7 +145,10 @@ saip_status saip::eng::contact_launch(saip_batch* b, int mode, double dt) {
 	P.tau_sim = C.tau_sim;
 	P.readout = C.readout;
 	P.summary = C.summary;
-	hipError_t e = saip::launch_contact_apply(P, b->model->dev.is_tree != 0, b->stream);
+	// planes with an environment schedule move: the MOVING instantiation reads the velocities the schedule writes
+	P.vel = env_plane_velocity(b, saip::ENV_TARGET_PLANES, -1);
+	const bool tree = b->model->dev.is_tree != 0;
+	hipError_t e = P.vel ? saip::launch_contact_apply_moving(P, tree, b->stream) : saip::launch_contact_apply(P, tree, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "contact launch failed: %s", hipGetErrorString(e));
 	return SAIP_OK;
 }
@@ -189,6 +195,7 @@ static int patch_slot(const saip_batch* b, int task, const char* fn, saip_status
 }
 void saip::eng::patch_free(saip_batch* b, int slot) {
 	auto& C = b->patch[slot];
+	env_release(b, saip::ENV_TARGET_PATCH, C.task);  // an environment schedule writes into the planes: it goes first
 	for (void* p : {(void*)C.planes, (void*)C.readout, (void*)C.summary})
 		if (p) (void)hipFree(p);
 	for (int i = slot; i + 1 < b->n_patch; i++) b->patch[i] = b->patch[i + 1];
@@ -265,6 +272,8 @@ extern "C" saip_status saip_batch_contact_patch_set_planes_host(saip_batch* b, i
 	if (slot < 0) return st;
 	if (!planes) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null planes", fn);
 	const auto& C = b->patch[slot];
+	if (env_slot(b, saip::ENV_TARGET_PATCH, C.task) >= 0)
+		return fail(SAIP_ERR_ORDER, "%s: the planes of task %d are written by an environment schedule (saip_batch_env_schedule_detach first)", fn, C.task);
 	std::vector<double> host;
 	if (const char* bad = contact_check_planes(planes, C.n_planes, C.per_instance ? (size_t)b->B : 1, host)) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, bad);
 	if ((st = need_ready(b, fn))) return st;
@@ -283,7 +292,8 @@ extern "C" double* saip_batch_contact_patch_torques_device(saip_batch* b) { retu
 // one launch of the patch kernel at the resident state, for every patch; dt: the substep an APPLY launch stands in front of
 saip_status saip::eng::patch_launch(saip_batch* b, int mode, double dt) {
 	if (saip_status st = ensure_task_constants(b)) return st;
-	saip::ContactPatchParams P;
+	saip::ContactPatchMovingParams P;  // (the static launch takes its ContactPatchParams part)
+	bool moving = false;
 	memset(&P, 0, sizeof(P));
 	P.B = b->B;
 	P.ld = b->ld;
@@ -310,8 +320,11 @@ saip_status saip::eng::patch_launch(saip_batch* b, int mode, double dt) {
 		D.goal = b->tasks[C.task].goal_dev;
 		D.readout = C.readout;
 		D.summary = C.summary;
+		P.vel[i] = env_plane_velocity(b, saip::ENV_TARGET_PATCH, C.task);
+		moving = moving || P.vel[i];
 	}
-	hipError_t e = saip::launch_contact_patch_apply(P, b->model->dev.is_tree != 0, b->stream);
+	const bool tree = b->model->dev.is_tree != 0;
+	hipError_t e = moving ? saip::launch_contact_patch_apply_moving(P, tree, b->stream) : saip::launch_contact_patch_apply(P, tree, b->stream);
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "contact patch launch failed: %s", hipGetErrorString(e));
 	return SAIP_OK;
 }

@@ -21,6 +21,7 @@
 #include "saip_contact.h"
 #include "saip_contact_patch.h"
 #include "saip_clearance.h"
+#include "saip_env_schedule.h"
 #include "saip_plant.h"
 #include "saip_plant_chain.h"
 #include "saip_inertia.h"
@@ -57,6 +58,9 @@ hipError_t launch_sampler_share_columns(double* a, int rows, int B, int ld, int 
 hipError_t launch_sampler_shift(const SamplerParams& P, int n, hipStream_t stream);
 hipError_t launch_contact_apply(const ContactParams& P, bool tree, hipStream_t stream);
 hipError_t launch_contact_patch_apply(const ContactPatchParams& P, bool tree, hipStream_t stream);
+hipError_t launch_contact_apply_moving(const ContactMovingParams& P, bool tree, hipStream_t stream);
+hipError_t launch_contact_patch_apply_moving(const ContactPatchMovingParams& P, bool tree, hipStream_t stream);
+hipError_t launch_env_schedule(const EnvScheduleParams& P, hipStream_t stream);
 hipError_t launch_clearance_eval(const ClearanceParams& P, bool tree, hipStream_t stream);
 hipError_t launch_clearance_add_cost(int B, int ld, const double* summary, double* cost, double w_penalty, double w_collision, double d_safe, hipStream_t stream);
 hipError_t launch_clearance_summary_reset(int B, int ld, double* summary, hipStream_t stream);
@@ -231,6 +235,17 @@ struct saip_batch {
 		double* summary = nullptr;           // [4][ld]
 		double* centres = nullptr;           // [3 S][ld], keep_centres only
 	} clearance;
+	// saip_batch_env_schedule_attach: time-varying obstacle and plane tables of the rollout periods (saip_env_schedule.hip), at most one per
+	// table.  Keyframes and plane velocities are the schedule's own allocations (freed by _detach, or with the attachment whose table it
+	// writes), not part of `allocs` or of a snapshot: tables are configuration.
+	struct EnvSchedule {
+		bool attached = false;
+		int target = 0, task = -1, first = 0, n_items = 0, K = 0, stride = 1, mode = 0, per_instance = 0;
+		double* key = nullptr;               // [K][n_items][W] or [K][n_items][W][ld]
+		double* vel = nullptr;               // planes: [P][4] or [P][4][ld] over the whole table (zero outside the scheduled items)
+	} env[saip::ENV_MAX_SCHEDULES];
+	int n_env = 0;                           // attached environment schedules
+	long long env_period = 0;                // the rollout period c the next scheduled period belongs to (_rewind sets it)
 	// The optional second stage of the sensing model and of the plant model: per joint a delay line and filters, W words per joint (a
 	// ChainKind below says which).  The only attachments with state: taps, filt and primed are on the snapshot directory while attached;
 	// the table is configuration.  Nothing of a chain lives in a host scalar but the sensing chain's sample time, which its carrier keeps.
@@ -373,6 +388,12 @@ void patch_free(saip_batch* b, int slot);
 saip_status contact_launch(saip_batch* b, int mode, double dt);
 saip_status patch_launch(saip_batch* b, int mode, double dt);
 bool patch_any_sensor(const saip_batch* b);
+const char* contact_check_planes(const double* planes, int P, size_t cols, std::vector<double>& out);
+// ---- saip_engine_env.cpp
+int env_slot(const saip_batch* b, int target, int task);            // the schedule on that table (task: ENV_TARGET_PATCH only), -1: none
+void env_release(saip_batch* b, int target, int task);              // ... freed, if there is one; the stream is idle
+const double* env_plane_velocity(const saip_batch* b, int target, int task);  // nullptr: those planes have no schedule
+saip_status env_apply(saip_batch* b, double T);
 // ---- saip_engine_clearance.cpp
 void clearance_free(saip_batch* b);
 saip_status clearance_launch(saip_batch* b, int mode, double dt);

@@ -398,6 +398,9 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 	const int sense_slots = b->sensing.attached ? sensing_sensor_slots(b, true, true) : 0;
 	auto period = [&](const bool more = false) -> saip_status {  // more: another period follows inside this call
 		if (scheduled && (st = apply_schedules(b))) return st;
+		// environment schedules: this period's planes (held through its substeps) and the obstacles at the time of the state the monitor will
+		// look at; the launch reads no state, so the fused forms below stay in use
+		if (b->n_env > 0 && (st = env_apply(b, sim_dt * substeps))) return st;
 		// contact planes with the simulated sensor: the sensed wrench of this period's state, in front of the OTGs (which pass it on) and the cycle
 		if (b->contact.attached && b->contact.sensor && (st = contact_launch(b, saip::CONTACT_SENSE, 0.0))) return st;
 		if (patch_sensor && (st = patch_launch(b, saip::CONTACT_SENSE, 0.0))) return st;

@@ -41,7 +41,11 @@
    on), and the event-timed mean of 200 measurements alone both ways.
    --plant --plant-chain DEPTH [--plant-wrenches W] [--substeps S] times, interleaved in the same run, the closed-loop period with that plant
    model alone and with a per-instance actuation chain of DEPTH taps in front of it (delays 0..DEPTH across the instances, rate limit and
-   lag on), and the event-timed mean of 200 one-substep integrate calls both ways."""
+   lag on), and the event-timed mean of 200 one-substep integrate calls both ways.
+   --env-schedule {obstacles,planes,both} [--env-mode hold|linear] [--substeps S] times, interleaved in the same run, the closed-loop period
+   with a clearance monitor (8 spheres, 4 obstacles) and / or one per-instance contact plane attached, without and with an environment
+   schedule of three keyframes over the timed rollout on their tables, and the event-timed mean of 200 one-substep integrate calls both
+   ways: with planes that is the static against the MOVING contact launch."""
 import argparse
 import os
 import sys
@@ -103,6 +107,8 @@ ap.add_argument("--clearance", action="store_true")
 ap.add_argument("--clearance-spheres", type=int, default=8)
 ap.add_argument("--clearance-obstacles", type=int, default=4)
 ap.add_argument("--clearance-pairs", type=int, default=0)
+ap.add_argument("--env-schedule", choices=("obstacles", "planes", "both"), default=None)
+ap.add_argument("--env-mode", choices=("hold", "linear"), default="linear")
 ap.add_argument("--plant", action="store_true")
 ap.add_argument("--plant-wrenches", type=int, choices=range(5), default=1)
 ap.add_argument("--plant-chain", type=int, choices=range(9), default=None, metavar="DEPTH")
@@ -235,6 +241,63 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
             print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'}: sampler, {KF} keyframes of position + "
                   f"orientation: perturb {t['perturb']:.1f} us; cost {t['cost']:.1f} us; update {t['update']:.1f} us; host round trip (summary, NumPy perturb + "
                   f"update, detach + attach) {host:.0f} us{grouped}")
+        continue
+    if args.env_schedule:
+        sub, mode = args.substeps, args.env_mode
+        with_o, with_p = args.env_schedule in ("obstacles", "both"), args.env_schedule in ("planes", "both")
+        rng = np.random.default_rng(0)
+        names = [f"link{i}" for i in range(1, 8)] + ["end-effector"]
+        spheres = [(names[s % 8], rng.uniform(-0.05, 0.05, 3), 0.05) for s in range(8)]
+        obst = np.zeros((4, 8))
+        obst[:, 1:4] = rng.uniform(-0.8, 0.8, (4, 3))
+        obst[:, 4:7] = obst[:, 1:4] + rng.uniform(-0.3, 0.3, (4, 3))
+        obst[:, 7] = 0.03
+        obst[3] = [1.0, 0.0, 0.0, 1.0, -0.2, 0.0, 0.0, 0.0]                   # a floor
+        ko = np.repeat(obst[None], 3, axis=0)                                 # the capsules drift 5 cm per keyframe, the floor rises 1 cm
+        ko[1:, :3, 1:7] += np.array([0.05, 0.1])[:, None, None]
+        ko[1:, 3, 4] += np.array([0.01, 0.02])
+        p0 = robot.position(d["tasks"][0]["link"], tuple(d["tasks"][0]["pos_in_link"]))
+        planes = np.zeros((1, B, 8))
+        planes[0] = [0.0, 0.0, 1.0, 0.0, 2.0e4, 400.0, 0.3, 1e-3]
+        planes[0, :, 3] = p0[:, 2] + 1e-3                                     # a table 1 mm above every control point ...
+        kp = np.zeros((3, 1, B, 12))
+        kp[:, 0, :, :8] = planes[0]
+        kp[:, 0, :, 3] += np.array([0.0, 1e-3, 0.0])[:, None]                 # ... that rises 1 mm and comes back, on a belt along +x
+        kp[:, 0, :, 8] = 0.05
+        timed_us, _ = stream_timer(ctrl)
+
+        def period_us():
+            ctrl.rewindEnvironment(0)
+            t0 = time.perf_counter()
+            ctrl.rolloutAsync(K, 5e-4, sub, gravity=(0, 0, 0))
+            ctrl.synchronize()
+            return (time.perf_counter() - t0) / K * 1e6
+
+        def substep_us():
+            return timed_us(lambda: ctrl.integrate(5e-4, 1, gravity=(0, 0, 0)), 200)
+
+        for _ in range(args.repeats):
+            if with_o:
+                ctrl.attachClearance(spheres, obst, margin=0.05)
+            if with_p:
+                mf.attachContactPlanes(planes, sensor=False, per_instance=True)
+            period_us()
+            static, static_s = period_us(), substep_us()
+            if with_o:
+                ctrl.setObstacleSchedule(ko, stride=K // 2, mode=mode)        # two keyframe intervals span the K periods of a timed rollout
+            if with_p:
+                mf.setContactSchedule(kp, stride=K // 2, mode=mode)
+            period_us()
+            sched, moving_s = period_us(), substep_us()
+            ctrl.clearEnvironmentSchedules()
+            again = period_us()
+            if with_o:
+                ctrl.detachClearance()
+            if with_p:
+                mf.detachContactPlanes()
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {sub}, env schedule "
+                  f"{args.env_schedule} ({mode}): closed-loop period with the attachment(s) and no schedule {static:.1f} us; scheduled {sched:.1f} us; "
+                  f"unscheduled again {again:.1f} us; one substep on the stream, static / with the schedule attached {static_s:.2f} / {moving_s:.2f} us")
         continue
     if args.contact:
         P, sub = args.contact_planes, args.substeps
