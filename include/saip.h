@@ -534,6 +534,59 @@ double* saip_batch_clearance_summary_device(saip_batch*);    /* [4][ld]; NULL wh
 saip_status saip_batch_clearance_summary_reset(saip_batch*);
 double* saip_batch_clearance_centres_device(saip_batch*);    /* [3 S][ld]; NULL unless keep_centres */
 saip_status saip_batch_clearance_add_cost(saip_batch*, double w_penalty, double w_collision, double d_safe);
+/* ---- link contact: world-fixed obstacles push back on the robot's link spheres, so that an elbow that meets the table stops there in
+ * the simulation.  One attachment per batch; it owns its copies of every table (it shares nothing with the clearance monitor).
+ *   spheres    n_spheres (1..SAIP_LINK_CONTACT_MAX_SPHERES), as saip_batch_clearance_attach takes them (batch-uniform, sorted by body here).
+ *   obstacles  n_obstacles (1..SAIP_LINK_CONTACT_MAX_OBSTACLES) in the clearance monitor's eight words: [O][8] or [O][8][B] (per_instance).
+ *   materials  [O][4] = { k, c, mu, v_s } per obstacle, batch-uniform: stiffness, damping, friction, slip-regularisation speed.
+ * Item (s, o) has the monitor's signed distance d and a direction n: the half-space normal, or u / |u| of the capsule (u the vector from the
+ * closest axis point to the centre; with |u| == 0, the centre exactly on the axis, there is no direction and the item pushes nothing).  It
+ * is active iff d < 0; then with v the velocity of the sphere's centre, vn = n.v:
+ *   f_n = max(0, (-k d) - c vn)     v_t = v - vn n     f_t = -(mu f_n) v_t / max(|v_t|, v_s) (0 when mu == 0)     f = f_n n + f_t
+ * F_s = sum of f over the active obstacles, acting at the sphere's centre, and tau_sim = u0 + sum_s J_v(c_s)^T F_s, u0 the commanded torques
+ * (the plant's actuated torques when a plant is attached; NaN -> 0).  Every product and sum is rounded once, in a fixed order and a fixed
+ * eight-lane split (csrc/saip_link_contact.h; tests/link_contact_ref.py restates it in NumPy bit for bit).
+ *   while attached, every integration substep of saip_batch_integrate and saip_batch_rollout_async is: the plant launch (if attached), the
+ *        link-contact launch, the contact-plane or patch launch (if attached; it builds on link contact's tau_sim), the integrate launch
+ *        with the last buffer written.  Neither fused form is used.  _evaluate enqueues one launch at the resident state that writes the
+ *        readout (and the kept arrays) only.
+ *   readout [8][ld], of the LAST launch: rows 0..2 the net force sum_s F_s; 3 the smallest d over all items; 4 its item s O + o (as a
+ *        double, s the caller's sphere index; the lowest among equals); 5 active items; 6 sum f_n; 7 the largest single-item |f|.  An instance
+ *        with a sphere centre that is not finite is invalid: rows 0..3, 6, 7 NaN, item -1, count 0, tau_sim = u0.
+ *   summaries [4][ld], advanced once per substep: sum dt sum f_n (NaN is sticky); the largest single-item |f|; the largest penetration
+ *        max(0, -d); substeps with an active item.  _summary_reset zeroes them on the stream; pair it with a snapshot restore: nothing of
+ *        the attachment is state.
+ *   keep: _keep_device is [9 S][ld]: centres (row 3 s + e), velocities (3 (S + s) + e), F_s (3 (2 S + s) + e) of the last launch; else NULL.
+ *   saip_batch_link_contact_add_cost: cost[i] = cost[i] + (w_impulse S0[i] + w_peak S1[i]) on the sampler's cost; a NaN S0 gives a NaN cost.
+ * Limits: an explicit penalty is stable only roughly while k dt^2 / m_eff <~ 1; the force acts at the centre, not at the surface point.
+ * Without an attachment every entry point enqueues exactly what it did before.  SAIP_ERR_INVALID_ARGUMENT (the message names the sphere,
+ * the obstacle or material, and the word): a NaN anywhere, a value that is not finite, a radius below 0, a half-space normal off unit
+ * length by more than 1e-6, an unknown kind, a link index out of range, k, c or mu negative or not finite, mu > 0 with v_s <= 0, 0 spheres
+ * or obstacles or counts above the maxima, a NaN weight.  SAIP_ERR_ORDER: before finalize, a model-only batch, a second _attach, any other
+ * entry without an attachment, _add_cost without a sampler.  Argument and order errors are reported before the device is needed, and
+ * nothing is written on refusal. */
+#define SAIP_LINK_CONTACT_MAX_SPHERES 32
+#define SAIP_LINK_CONTACT_MAX_OBSTACLES 16
+#define SAIP_LINK_CONTACT_OBSTACLE_WORDS 8
+#define SAIP_LINK_CONTACT_MATERIAL_WORDS 4
+#define SAIP_LINK_CONTACT_READOUT_ROWS 8
+#define SAIP_LINK_CONTACT_SUMMARY_ROWS 4
+saip_status saip_batch_link_contact_attach(saip_batch*, int n_spheres, const int* links, const double* centres /* [S][3] */, const double* radii,
+                                           int n_obstacles, const double* obstacles, const double* materials /* [O][4] */, int per_instance, int keep);
+saip_status saip_batch_link_contact_detach(saip_batch*);
+saip_status saip_batch_link_contact_info(saip_batch*, int* n_spheres, int* n_obstacles, int* per_instance, int* keep);  /* any NULL */
+saip_status saip_batch_link_contact_set_obstacles_host(saip_batch*, const double* obstacles);
+saip_status saip_batch_link_contact_set_materials_host(saip_batch*, const double* materials);
+double* saip_batch_link_contact_obstacles_device(saip_batch*);  /* [O][8] or [O][8][ld]; NULL when detached */
+saip_status saip_batch_link_contact_evaluate(saip_batch*);
+saip_status saip_batch_link_contact_readout_host(saip_batch*, double* out /* [8][B] */);  /* synchronous */
+double* saip_batch_link_contact_readout_device(saip_batch*);    /* [8][ld]; NULL when detached */
+saip_status saip_batch_link_contact_summary_host(saip_batch*, double* out /* [4][B] */);  /* synchronous */
+double* saip_batch_link_contact_summary_device(saip_batch*);    /* [4][ld]; NULL when detached */
+saip_status saip_batch_link_contact_summary_reset(saip_batch*);
+saip_status saip_batch_link_contact_add_cost(saip_batch*, double w_impulse, double w_peak);
+double* saip_batch_link_contact_torques_device(saip_batch*);    /* [dof][ld] tau_sim of the last APPLY launch; NULL when detached */
+double* saip_batch_link_contact_keep_device(saip_batch*);       /* [9 S][ld]; NULL unless keep */
 /* ---- environment schedules: moving obstacles and contact surfaces inside rollouts.  What goal schedules are to the goals: the obstacle
  * table of the clearance monitor, the single-point contact planes and the planes of a contact patch become functions of the rollout
  * period, written from keyframes resident on the device by ONE launch at the head of every period of saip_batch_rollout_async.  At most

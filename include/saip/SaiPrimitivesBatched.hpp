@@ -1325,6 +1325,71 @@ public:
 	void clearanceCost(double w_penalty, double w_collision = std::numeric_limits<double>::infinity(), double d_safe = 0.0) {
 		check(saip_batch_clearance_add_cost(_batch, w_penalty, w_collision, d_safe));
 	}
+	// ---- link contact: world-fixed obstacles push back on the robot's link spheres in front of every integration substep (saip.h).  While
+	// attached integrate() and rolloutAsync() add sum_s J_v(c_s)^T F_s to the torques they integrate and advance linkContactSummary();
+	// linkContactCost() adds it to the sampler's cost, after rolloutCost() as clearanceCost() is.
+	struct LinkContactInfo {
+		int n_spheres = 0, n_obstacles = 0, per_instance = 0, keep = 0;
+	};
+	// obstacles: [O][8] rows as attachClearance takes them, or [O][8][B] with per_instance; materials: [O][4] rows { k, c, mu, v_s }
+	void attachLinkContact(const std::vector<ClearanceSphere>& spheres, const std::vector<double>& obstacles, const std::vector<double>& materials,
+						   bool per_instance = false, bool keep = false) {
+		const size_t per = (size_t)SAIP_LINK_CONTACT_OBSTACLE_WORDS * (per_instance ? (size_t)_robot->batchSize() : 1);
+		if (obstacles.size() % per) throw std::invalid_argument("attachLinkContact: expected [O][8] obstacles, or [O][8][B] per instance");
+		if (materials.size() != obstacles.size() / per * SAIP_LINK_CONTACT_MATERIAL_WORDS) throw std::invalid_argument("attachLinkContact: expected [O][4] materials");
+		std::vector<int> links;
+		std::vector<double> centres, radii;
+		for (const auto& s : spheres) {
+			links.push_back(_robot->linkIndex(s.link));
+			centres.insert(centres.end(), s.centre.begin(), s.centre.end());
+			radii.push_back(s.radius);
+		}
+		check(saip_batch_link_contact_attach(_batch, (int)spheres.size(), links.data(), centres.data(), radii.data(), (int)(obstacles.size() / per),
+											 obstacles.empty() ? nullptr : obstacles.data(), materials.empty() ? nullptr : materials.data(), per_instance ? 1 : 0, keep ? 1 : 0));
+	}
+	void detachLinkContact() { check(saip_batch_link_contact_detach(_batch)); }
+	LinkContactInfo linkContactInfo() {
+		LinkContactInfo i;
+		check(saip_batch_link_contact_info(_batch, &i.n_spheres, &i.n_obstacles, &i.per_instance, &i.keep));
+		return i;
+	}
+	void setLinkContactObstacles(const std::vector<double>& obstacles) {
+		const LinkContactInfo i = linkContactInfo();
+		if (obstacles.size() != (size_t)i.n_obstacles * SAIP_LINK_CONTACT_OBSTACLE_WORDS * (i.per_instance ? (size_t)_robot->batchSize() : 1))
+			throw std::invalid_argument("setLinkContactObstacles: the shape of the attached obstacle table expected");
+		check(saip_batch_link_contact_set_obstacles_host(_batch, obstacles.data()));
+	}
+	void setLinkContactMaterials(const std::vector<double>& materials) {
+		const LinkContactInfo i = linkContactInfo();
+		if (materials.size() != (size_t)i.n_obstacles * SAIP_LINK_CONTACT_MATERIAL_WORDS) throw std::invalid_argument("setLinkContactMaterials: expected [O][4] materials");
+		check(saip_batch_link_contact_set_materials_host(_batch, materials.data()));
+	}
+	// one evaluation at the current state: linkContactReadout() (and the kept arrays) only, torques and summaries stay
+	void evaluateLinkContact() {
+		linkContactInfo();  // without an attachment: that error, before the device is needed
+		pushState();
+		check(saip_batch_link_contact_evaluate(_batch));
+	}
+	// [8][B]: the net force (3), the smallest signed distance, its item s O + o, the active items, sum f_n, the largest single-item |f| -- of
+	// the last launch; waits for the stream
+	std::vector<double> linkContactReadout() {
+		std::vector<double> out((size_t)SAIP_LINK_CONTACT_READOUT_ROWS * _robot->batchSize());
+		check(saip_batch_link_contact_readout_host(_batch, out.data()));
+		return out;
+	}
+	// [4][B]: sum dt sum f_n, the largest single-item |f|, the largest penetration, substeps with an active item; waits for the stream
+	std::vector<double> linkContactSummary() {
+		std::vector<double> out((size_t)SAIP_LINK_CONTACT_SUMMARY_ROWS * _robot->batchSize());
+		check(saip_batch_link_contact_summary_host(_batch, out.data()));
+		return out;
+	}
+	// pair it with restoreState: the summaries are not part of a snapshot
+	void resetLinkContactSummary() { check(saip_batch_link_contact_summary_reset(_batch)); }
+	double* linkContactObstaclesDevice() { return saip_batch_link_contact_obstacles_device(_batch); }
+	double* linkContactTorquesDevice() { return saip_batch_link_contact_torques_device(_batch); }  // [dof][ld] tau_sim of the last integrated substep
+	double* linkContactKeepDevice() { return saip_batch_link_contact_keep_device(_batch); }        // [9 S][ld]; nullptr unless keep
+	// cost += w_impulse * summary impulse + w_peak * summary peak force, after rolloutCost()
+	void linkContactCost(double w_impulse, double w_peak = 0.0) { check(saip_batch_link_contact_add_cost(_batch, w_impulse, w_peak)); }
 	// ---- environment schedules: obstacles and contact surfaces that move inside rollouts (saip.h; the contact side: task->setContactSchedule).
 	// keyframes: [K][n][8] obstacle rows, or [K][n][8][B] when the obstacle table is per instance.  The monitor of rollout period c looks at
 	// the state at the END of the period, so it sees the obstacles of period index c + 1; the last keyframe is held.

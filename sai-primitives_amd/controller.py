@@ -1760,6 +1760,99 @@ class RobotController:
         cost is an invalid sample to updateSampler(), so the default w_collision makes collision a hard constraint"""
         self._call("saip_batch_clearance_add_cost", float(w_penalty), float(w_collision), float(d_safe))
 
+    # -- link contact: world-fixed obstacles push back on the robot's link spheres in front of every integration substep (saip.h)
+    def attachLinkContact(self, spheres, obstacles, materials, per_instance=False, keep=False):
+        """let obstacles push back on the robot.  spheres: up to 32 of (link name, centre in the link frame (3), radius); obstacles: up to
+        16 rows as in attachClearance, of shape (O, 8), or (O, B, 8) with per_instance; materials: (O, 4) rows { k, c, mu, v_s }
+        (stiffness, damping, friction, slip-regularisation speed).  While attached every integration substep of integrate() and
+        rolloutAsync() adds sum_s J_v(c_s)^T F_s to the torques it integrates and advances linkContactSummary(); keep: centres,
+        velocities and sphere forces of the last launch stay on the device (linkContactKeepDevice)."""
+        spheres = list(spheres)
+        links = np.empty(len(spheres), np.int32)
+        centres, radii = np.zeros((len(spheres), 3)), np.zeros(len(spheres))
+        for s, sph in enumerate(spheres):
+            if len(sph) != 3:
+                raise ValueError(f"attachLinkContact: sphere {s}: (link, centre, radius) expected")
+            links[s] = self._robot.linkIndex(sph[0])
+            if links[s] < 0:
+                raise ValueError(f"attachLinkContact: sphere {s}: unknown link [{sph[0]}]")
+            c = np.asarray(sph[1], float).reshape(-1)
+            if c.shape != (3,):
+                raise ValueError(f"attachLinkContact: sphere {s}: a centre of shape (3,) expected, got {c.shape}")
+            centres[s], radii[s] = c, float(sph[2])
+        a = self._clearance_obstacles(obstacles, per_instance, self.batch_size, "attachLinkContact")
+        m = np.ascontiguousarray(materials, float)
+        if m.shape != (a.shape[0], capi.SAIP_LINK_CONTACT_MATERIAL_WORDS):
+            raise ValueError(f"attachLinkContact: materials of shape ({a.shape[0]}, {capi.SAIP_LINK_CONTACT_MATERIAL_WORDS}) expected, got {m.shape}")
+        self._call("saip_batch_link_contact_attach", len(spheres), links.ctypes.data_as(C.POINTER(C.c_int)), _dptr(centres), _dptr(radii), a.shape[0], _dptr(a),
+                   _dptr(m), int(bool(per_instance)), int(bool(keep)))
+
+    def linkContactInfo(self):
+        """dict n_spheres, n_obstacles, per_instance, keep"""
+        v = [C.c_int(0) for _ in range(4)]
+        self._call("saip_batch_link_contact_info", C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(v[3]))
+        return dict(n_spheres=v[0].value, n_obstacles=v[1].value, per_instance=bool(v[2].value), keep=bool(v[3].value))
+
+    def detachLinkContact(self):
+        self._call("saip_batch_link_contact_detach")
+
+    def setLinkContactObstacles(self, obstacles):
+        """replace the obstacle table (same shape as attached); takes effect with the next launch"""
+        info = self.linkContactInfo()
+        a = self._clearance_obstacles(obstacles, info["per_instance"], self.batch_size, "setLinkContactObstacles", info["n_obstacles"])
+        self._call("saip_batch_link_contact_set_obstacles_host", _dptr(a))
+
+    def setLinkContactMaterials(self, materials):
+        """replace the material table (O, 4); takes effect with the next launch"""
+        info = self.linkContactInfo()
+        m = np.ascontiguousarray(materials, float)
+        if m.shape != (info["n_obstacles"], capi.SAIP_LINK_CONTACT_MATERIAL_WORDS):
+            raise ValueError(f"setLinkContactMaterials: materials of shape ({info['n_obstacles']}, {capi.SAIP_LINK_CONTACT_MATERIAL_WORDS}) expected, got {m.shape}")
+        self._call("saip_batch_link_contact_set_materials_host", _dptr(m))
+
+    def evaluateLinkContact(self):
+        """enqueue one evaluation at the current state: linkContactReadout() (and the kept arrays) only, torques and summaries stay"""
+        self.linkContactInfo()  # without an attachment: that error, before the device is needed
+        self._push_state()
+        self._call("saip_batch_link_contact_evaluate")
+
+    def linkContactReadout(self):
+        """dict of the last link-contact launch: force (B, 3) the net force on the robot, distance (B,) the smallest signed distance over
+        all items, item (B,) its number, closest: per instance (sphere, obstacle) or None (invalid instance), active (B,) active items,
+        normal_force (B,) sum f_n, peak_force (B,) the largest single-item |f| (waits for the engine stream)"""
+        info = self.linkContactInfo()
+        out = np.empty((capi.SAIP_LINK_CONTACT_READOUT_ROWS, self.batch_size))
+        self._call("saip_batch_link_contact_readout_host", _dptr(out))
+        O = info["n_obstacles"]
+        item = out[4].astype(int)
+        closest = [None if k < 0 else (int(k) // O, int(k) % O) for k in item]
+        return dict(force=out[0:3].T.copy(), distance=out[3].copy(), item=item, closest=closest, active=out[5].astype(int), normal_force=out[6].copy(),
+                    peak_force=out[7].copy())
+
+    def linkContactSummary(self):
+        """dict over the integrated substeps: impulse (B,) sum dt sum f_n (NaN once an instance was invalid), peak_force (B,),
+        max_penetration (B,), substeps_in_contact (B,) (waits for the engine stream)"""
+        self.linkContactInfo()
+        out = np.empty((capi.SAIP_LINK_CONTACT_SUMMARY_ROWS, self.batch_size))
+        self._call("saip_batch_link_contact_summary_host", _dptr(out))
+        return dict(impulse=out[0].copy(), peak_force=out[1].copy(), max_penetration=out[2].copy(), substeps_in_contact=out[3].astype(int))
+
+    def resetLinkContactSummary(self):
+        """summaries back to 0; pair it with restoreState (the summaries are not part of a snapshot)"""
+        self._call("saip_batch_link_contact_summary_reset")
+
+    def linkContactTorquesDevice(self):
+        """device pointer of the (dof, ld) commanded + link-contact torques of the last integrated substep; None when detached"""
+        return capi.lib().saip_batch_link_contact_torques_device(self._h)
+
+    def linkContactKeepDevice(self):
+        """device pointer of the (9 S, ld) centres, velocities and sphere forces of the last launch; None unless attached with keep"""
+        return capi.lib().saip_batch_link_contact_keep_device(self._h)
+
+    def linkContactCost(self, w_impulse, w_peak=0.0):
+        """cost += w_impulse * summary impulse + w_peak * summary peak force on the device, after rolloutCost()"""
+        self._call("saip_batch_link_contact_add_cost", float(w_impulse), float(w_peak))
+
     # -- environment schedules: obstacles and contact surfaces that move inside rollouts (saip.h)
     _ENV_MODES = {"hold": capi.SAIP_ENV_HOLD, "linear": capi.SAIP_ENV_LINEAR}
 

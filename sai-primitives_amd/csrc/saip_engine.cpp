@@ -133,6 +133,7 @@ extern "C" void saip_batch_destroy(saip_batch* b) {
 		contact_free(b);
 		while (b->n_patch > 0) patch_free(b, b->n_patch - 1);
 		clearance_free(b);
+		link_contact_free(b);
 		plant_free(b);
 		inertia_free(b);
 		sensing_free(b);

@@ -15,7 +15,7 @@ void saip::eng::clearance_free(saip_batch* b) {
 	C = saip_batch::Clearance();
 }
 // the obstacle table [O][8] or [O][8][B]; false: `msg` says what is wrong with which entry
-static bool clearance_check_obstacles(const double* obst, int O, size_t cols, char* msg, size_t len) {
+bool saip::eng::clearance_check_obstacles(const double* obst, int O, size_t cols, char* msg, size_t len) {
 	for (int o = 0; o < O; o++)
 		for (size_t i = 0; i < cols; i++) {
 			const double* w = obst + (size_t)o * saip::CLEARANCE_OBSTACLE_WORDS * cols + i;

@@ -141,7 +141,7 @@ saip_status saip::eng::contact_launch(saip_batch* b, int mode, double dt) {
 	P.dq = b->dq;
 	P.planes = C.planes;
 	P.goal = b->tasks[C.task].goal_dev;
-	P.tau_cmd = b->plant.attached ? b->plant.tau_act : commanded_tau(b);  // (read by APPLY only, which follows the plant launch)
+	P.tau_cmd = contact_tau_cmd(b);  // (read by APPLY only, which follows the plant and link-contact launches)
 	P.tau_sim = C.tau_sim;
 	P.readout = C.readout;
 	P.summary = C.summary;
@@ -305,7 +305,7 @@ saip_status saip::eng::patch_launch(saip_batch* b, int mode, double dt) {
 	P.tasks = b->tasks_dev;
 	P.q = b->q;
 	P.dq = b->dq;
-	P.tau_cmd = b->plant.attached ? b->plant.tau_act : commanded_tau(b);  // (read by APPLY only, which follows the plant launch)
+	P.tau_cmd = contact_tau_cmd(b);  // (read by APPLY only, which follows the plant and link-contact launches)
 	P.tau_sim = b->patch_tau_sim;
 	for (int i = 0; i < b->n_patch; i++) {
 		const auto& C = b->patch[i];

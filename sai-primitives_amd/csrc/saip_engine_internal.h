@@ -21,6 +21,7 @@
 #include "saip_contact.h"
 #include "saip_contact_patch.h"
 #include "saip_clearance.h"
+#include "saip_link_contact.h"
 #include "saip_env_schedule.h"
 #include "saip_plant.h"
 #include "saip_plant_chain.h"
@@ -64,6 +65,9 @@ hipError_t launch_env_schedule(const EnvScheduleParams& P, hipStream_t stream);
 hipError_t launch_clearance_eval(const ClearanceParams& P, bool tree, hipStream_t stream);
 hipError_t launch_clearance_add_cost(int B, int ld, const double* summary, double* cost, double w_penalty, double w_collision, double d_safe, hipStream_t stream);
 hipError_t launch_clearance_summary_reset(int B, int ld, double* summary, hipStream_t stream);
+hipError_t launch_link_contact_apply(const LinkContactParams& P, bool tree, hipStream_t stream);
+hipError_t launch_link_contact_summary_reset(int B, int ld, double* summary, hipStream_t stream);
+hipError_t launch_link_contact_add_cost(int B, int ld, const double* summary, double* cost, double w_impulse, double w_peak, hipStream_t stream);
 hipError_t launch_plant_apply(const PlantParams& P, bool tree, hipStream_t stream);
 hipError_t launch_plant_randomize(const PlantRandomParams& P, hipStream_t stream);
 hipError_t launch_plant_chain_apply(const PlantChainParams& C, bool tree, hipStream_t stream);
@@ -235,6 +239,21 @@ struct saip_batch {
 		double* summary = nullptr;           // [4][ld]
 		double* centres = nullptr;           // [3 S][ld], keep_centres only
 	} clearance;
+	// saip_batch_link_contact_attach: obstacles push back on link spheres (saip_link_contact.hip), at most one per batch, in front of every
+	// integration substep.  Nothing in it is state: its arrays are configuration, scratch, readout and summaries, its own copies (it does not
+	// alias the clearance monitor's tables), freed by _detach, not part of `allocs` or of a snapshot.
+	struct LinkContact {
+		bool attached = false;
+		int per_instance = 0, keep = 0;
+		saip::LinkContactGeom geom;          // the host copy of *geom_dev (zeroed by _attach)
+		saip::LinkContactGeom* geom_dev = nullptr;
+		double* obst = nullptr;              // [O][8] (batch-uniform) or [O][8][ld]
+		double* mat = nullptr;               // [O][4]
+		double* tau_sim = nullptr;           // [n][ld] commanded (or actuated) + link-contact torques of the substep being integrated
+		double* readout = nullptr;           // [8][ld]
+		double* summary = nullptr;           // [4][ld]
+		double* keep_dev = nullptr;          // [9 S][ld], keep only
+	} link_contact;
 	// saip_batch_env_schedule_attach: time-varying obstacle and plane tables of the rollout periods (saip_env_schedule.hip), at most one per
 	// table.  Keyframes and plane velocities are the schedule's own allocations (freed by _detach, or with the attachment whose table it
 	// writes), not part of `allocs` or of a snapshot: tables are configuration.
@@ -397,6 +416,12 @@ saip_status env_apply(saip_batch* b, double T);
 // ---- saip_engine_clearance.cpp
 void clearance_free(saip_batch* b);
 saip_status clearance_launch(saip_batch* b, int mode, double dt);
+bool clearance_check_obstacles(const double* obst, int O, size_t cols, char* msg, size_t len);  // false: `msg` says what is wrong with which entry
+// ---- saip_engine_link_contact.cpp
+void link_contact_free(saip_batch* b);
+saip_status link_contact_launch(saip_batch* b, int mode, double dt);
+// the torques the contact planes or patches build on: link contact's, else the plant's, else the commanded ones
+inline const double* contact_tau_cmd(const saip_batch* b) { return b->link_contact.attached ? b->link_contact.tau_sim : b->plant.attached ? b->plant.tau_act : commanded_tau(b); }
 // ---- saip_engine_chain.cpp: the host side of a chain (saip_batch::Chain), written once.  What differs between the two is a ChainKind;
 // the extern "C" entries stay with the carriers (saip_engine_sensing.cpp, saip_engine_plant.cpp), which pick the struct and the kind
 struct ChainKind {

@@ -20,18 +20,21 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 	S.inertia_stride = b->inertia.attached && b->inertia.per_instance ? b->ld : 1;
 	hipError_t e;
 	const bool tree = b->model->dev.is_tree != 0;  // trees: the lane-per-instance tree kernel, whatever the dof (the eight-lane step is chain-only)
-	if (b->contact.attached || b->n_patch > 0 || b->plant.attached) {
+	if (b->contact.attached || b->n_patch > 0 || b->plant.attached || b->link_contact.attached) {
 		// contact planes: the penalty force is re-evaluated in front of every substep (held over a control period it is unstable at
 		// useful stiffness), and the integrator takes commanded + contact torques; never fused with the next period's OTG step.
 		// Contact patches take the same place with their own kernel.  A plant model stands in front of either: it turns the commanded
 		// torques into actuated ones, which the contact launch (when there is one) takes in place of the commanded torques; the
-		// integrator reads the last buffer written.  The whole call belongs to one period of the plant.
-		const bool patches = b->n_patch > 0, contact = patches || b->contact.attached;
+		// integrator reads the last buffer written.  The whole call belongs to one period of the plant.  Link contact stands between the
+		// two: it adds the obstacles' push on the link spheres to the plant's (or the commanded) torques, and the contact launch builds on
+		// its buffer (contact_tau_cmd).
+		const bool patches = b->n_patch > 0, contact = patches || b->contact.attached, links = b->link_contact.attached;
 		S.substeps = 1;
-		S.tau = patches ? b->patch_tau_sim : contact ? b->contact.tau_sim : b->plant.tau_act;
+		S.tau = patches ? b->patch_tau_sim : contact ? b->contact.tau_sim : links ? b->link_contact.tau_sim : b->plant.tau_act;
 		for (int s = 0; s < substeps; s++) {
 			saip_status st = b->plant.attached ? plant_launch(b, dt, s) : SAIP_OK;  // s == 0: the actuation chain advances its delay line
 			if (st) return st;
+			if (links && (st = link_contact_launch(b, saip::LINK_CONTACT_APPLY, dt))) return st;
 			if (contact) st = patches ? patch_launch(b, saip::CONTACT_APPLY, dt) : contact_launch(b, saip::CONTACT_APPLY, dt);
 			if (st) return st;
 			e = saip::launch_integrate(S, tree, b->stream);
@@ -393,7 +396,8 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 	// an inertia table rules out both fused forms as well: they integrate with the model's inertial parameters
 	// a sensing model too: the fused cycle would compute from the measured copy and integrate it, and the next period's OTG step would
 	// run ahead of the measurement it belongs behind
-	const bool contact = b->contact.attached || b->n_patch > 0 || b->plant.attached || b->inertia.attached || b->sensing.attached;
+	// link contact as well: like the contact planes it sits in front of every integration substep
+	const bool contact = b->contact.attached || b->n_patch > 0 || b->plant.attached || b->inertia.attached || b->sensing.attached || b->link_contact.attached;
 	const bool patch_sensor = patch_any_sensor(b);
 	const int sense_slots = b->sensing.attached ? sensing_sensor_slots(b, true, true) : 0;
 	auto period = [&](const bool more = false) -> saip_status {  // more: another period follows inside this call

@@ -26,6 +26,10 @@
    --clearance [--clearance-spheres S] [--clearance-obstacles O] [--clearance-pairs P] times, interleaved in the same run, the closed-loop
    period without and with a clearance monitor of S link spheres, O batch-uniform obstacles (capsules, every fourth a half-space) and P self
    pairs, and prints the event-timed mean of 200 back-to-back evaluations alone.
+   --link-contact [--lc-spheres S] [--lc-obstacles O] [--lc-per-instance] [--substeps N] times, interleaved in the same run, the closed-loop
+   period without and with link contact of S link spheres against O obstacles (capsules, every fourth a floor; soft materials with
+   friction), and prints the event-timed mean of 200 back-to-back EVALUATE launches alone and of 200 one-substep integrate calls both
+   ways: their difference is the APPLY launch.
    --plant [--plant-wrenches W] [--substeps S] times, interleaved in the same run, the closed-loop period without and with a per-instance
    plant model (tight actuators, friction, stops at the model's limits and W payload-like wrenches, 0..4) and the event-timed mean of 200
    one-substep integrate calls both ways: the difference is the plant launch alone.
@@ -107,6 +111,10 @@ ap.add_argument("--clearance", action="store_true")
 ap.add_argument("--clearance-spheres", type=int, default=8)
 ap.add_argument("--clearance-obstacles", type=int, default=4)
 ap.add_argument("--clearance-pairs", type=int, default=0)
+ap.add_argument("--link-contact", action="store_true")
+ap.add_argument("--lc-spheres", type=int, default=8)
+ap.add_argument("--lc-obstacles", type=int, default=4)
+ap.add_argument("--lc-per-instance", action="store_true")
 ap.add_argument("--env-schedule", choices=("obstacles", "planes", "both"), default=None)
 ap.add_argument("--env-mode", choices=("hold", "linear"), default="linear")
 ap.add_argument("--plant", action="store_true")
@@ -398,6 +406,52 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
             print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {args.substeps}: "
                   f"closed-loop period {plain:.1f} us; with a clearance monitor of {S} spheres, {O} obstacles, {P} pairs {with_c:.1f} us; without it again "
                   f"{again:.1f} us; one evaluation alone {alone:.2f} us ({under} of {B} instances under the margin)")
+        continue
+    if args.link_contact:
+        S, O = args.lc_spheres, args.lc_obstacles
+        rng = np.random.default_rng(0)
+        names = [f"link{i}" for i in range(1, 8)] + ["end-effector"]
+        spheres = [(names[s % 8], rng.uniform(-0.05, 0.05, 3), 0.05) for s in range(S)]
+        obst = np.zeros((O, 8))
+        obst[:, 1:4] = rng.uniform(-0.8, 0.8, (O, 3))
+        obst[:, 4:7] = obst[:, 1:4] + rng.uniform(-0.3, 0.3, (O, 3))
+        obst[:, 7] = 0.03
+        obst[3::4] = [1.0, 0.0, 0.0, 1.0, -0.2, 0.0, 0.0, 0.0]               # every fourth: a floor
+        mats = np.tile([2.0e3, 40.0, 0.3, 1e-3], (O, 1))                     # soft: k dt^2 / m_eff stays far below 1 at dt = 5e-4
+        if args.lc_per_instance:
+            obst = np.ascontiguousarray(np.repeat(obst[:, None, :], B, axis=1))
+        timed_us, _ = stream_timer(ctrl)
+
+        def period_us():
+            t0 = time.perf_counter()
+            ctrl.rolloutAsync(K, 5e-4, args.substeps, gravity=(0, 0, 0))
+            ctrl.synchronize()
+            return (time.perf_counter() - t0) / K * 1e6
+
+        def integrate_us():
+            return timed_us(lambda: ctrl._call("saip_batch_integrate", 5e-4, 1, None, 0.0), 200)
+
+        def evaluate_us():
+            return timed_us(lambda: ctrl._call("saip_batch_link_contact_evaluate"), 200, first=ctrl.evaluateLinkContact)
+
+        for _ in range(args.repeats):
+            snap = ctrl.saveState()
+            plain, plain_i = period_us(), integrate_us()
+            ctrl.restoreState(snap)
+            ctrl.attachLinkContact(spheres, obst, mats, per_instance=args.lc_per_instance)
+            period_us()
+            ctrl.restoreState(snap)
+            ctrl.resetLinkContactSummary()
+            with_c, with_i, alone = period_us(), integrate_us(), evaluate_us()
+            touched = int((ctrl.linkContactSummary()["substeps_in_contact"] > 0).sum())
+            ctrl.detachLinkContact()
+            ctrl.restoreState(snap)
+            again = period_us()
+            ctrl.restoreState(snap)
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {args.substeps}: "
+                  f"closed-loop period {plain:.1f} us, integrate {plain_i:.2f} us; with link contact of {S} spheres, {O} "
+                  f"{'per-instance' if args.lc_per_instance else 'batch-uniform'} obstacles: period {with_c:.1f} us, integrate {with_i:.2f} us; without it again "
+                  f"{again:.1f} us; one EVALUATE launch alone {alone:.2f} us ({touched} of {B} instances touched)")
         continue
     if args.plant:
         Wn = args.plant_wrenches
