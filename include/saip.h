@@ -881,6 +881,98 @@ saip_status saip_batch_sensing_chain_reset(saip_batch*);
 double* saip_batch_sensing_chain_table_device(saip_batch*);  /* NULL when detached */
 saip_status saip_batch_sensing_chain_state_host(saip_batch*, double* taps, double* filt, int* primed);  /* synchronous */
 saip_status saip_batch_sensing_chain_state_device(saip_batch*, double** taps, double** filt, int** primed);  /* the arrays, [rows][ld]; taps NULL at depth 0 */
+/* ---- resident guards: event-triggered phases and goal switching inside rollouts.  The policy of a rollout stops being open loop in time:
+ * every instance carries a phase 0 .. P-1, a table of guards (transitions) moves it on what the instance itself senses, and a table of
+ * phases says what a phase does to the goal of ONE motion-force task ("descend until touch, then stop, then retract 5 cm").  One
+ * attachment per batch.  Task parametrisation stays batch-uniform: a guard switches the goal, not the control law.
+ *   guards   n_guards (1..SAIP_GUARD_MAX_GUARDS) rows of SAIP_GUARD_WORDS doubles { from, to, signal, axis, cmp, threshold, hold, blank }:
+ *            [G][8], or [G][8][B] with per_instance.  All words but threshold are integer-valued.
+ *            signal  SAIP_GUARD_PERIODS     periods the instance has spent in its phase (`since` below)
+ *                    SAIP_GUARD_FORCE       goal rows 30..32 (sensed force, sensor frame) as the control law reads them: axis 0..2 a
+ *                                           component, axis 3 sqrt((f0 f0 + f1 f1) + f2 f2), every product and sum rounded on its own
+ *                    SAIP_GUARD_MOMENT      the same on rows 33..35
+ *                    SAIP_GUARD_POSITION    world position of the task's control point, axis 0..2
+ *                    SAIP_GUARD_POS_ERROR   norm of the selection-projected position error against the task's goal rows as they stand
+ *                    SAIP_GUARD_ORI_ERROR   ... of the orientation error (both: the bits of rows 0..5 of the task diagnostics, squared,
+ *                                           summed and rooted as the recorder's summaries are).  "As they stand" is before
+ *                                           this evaluation writes: in a HOLD or OFFSET phase rows 0..11 are what the previous
+ *                                           evaluation wrote, unless something in front of the guard wrote them since -- a goal
+ *                                           schedule on the position rows does so in every period, and the error is then against
+ *                                           the schedule's goal of the period, not against the held pose the task tracks.  A guard
+ *                                           meant as "settled at the held pose" belongs on a task without such a schedule.
+ *                    SAIP_GUARD_JOINT_SPEED max_j |dq_j|
+ *            cmp     SAIP_GUARD_GE (signal >= threshold) or SAIP_GUARD_LE; a NaN signal satisfies neither.
+ *            hold    >= 1, a debounce: the condition must be true in `hold` consecutive evaluations.
+ *            blank   >= 0, a blanking time: the guard is evaluated only once since >= blank (a contact transient is not an event).
+ *   phases   n_phases (1..SAIP_GUARD_MAX_PHASES) rows of SAIP_GUARD_PHASE_WORDS doubles { mode, dx, dy, dz }, batch-uniform.
+ *            SAIP_GUARD_FREE    the evaluation writes no goal row: whatever a schedule or the host wrote stands.  Phase 0 must be FREE.
+ *            SAIP_GUARD_HOLD    in every period goal rows 0..11 take the pose latched at the transition into the phase, rows 12..23 take 0.
+ *            SAIP_GUARD_OFFSET  HOLD with the latched position plus (dx, dy, dz) in the world frame, each sum rounded once.
+ *   one evaluation of one instance (csrc/saip_guard.h; tests/guard_ref.py restates it in NumPy bit for bit):
+ *            p = phase; fired = -1
+ *            for g = 0 .. G-1:  if from[g] != p or since < blank[g]: run[g] = 0
+ *                               else: run[g] = cond(g) ? run[g] + 1 : 0;  if fired < 0 and run[g] >= hold[g]: fired = g
+ *            if fired >= 0:     fires[fired] += 1; phase = to[fired]; since = 0; every run[g] = 0
+ *                               if entry[phase] < 0: entry[phase] = clock;  latch[0..11] = the pose this evaluation computed
+ *            else:              since += 1
+ *            the mode of the (new) phase is applied to the goal rows; clock += 1
+ *            At most one transition per period.  _attach and _reset leave phase = since = clock = run = fires = 0, entry[0] = 0,
+ *            entry[p > 0] = -1, latch = 0.  There is no host-side counter: clock is a per-instance device word.
+ *   reads    what the controller reads: the measured q, dq while a sensing model is attached (behind its chain), else the resident state;
+ *            goal rows 30..35 as the simulated sensor and the sensing model left them.  The pose is computed only when a guard
+ *            (POSITION, *_ERROR) or a phase (HOLD, OFFSET) needs it; a launch that computes none leaves the latch as it is.
+ *   where    in a period of saip_batch_rollout_async: behind the goal schedules, the environment schedules, the simulated-sensor launches
+ *            and the sensing launch, in front of the period's OTG step and cycle -- an internal OTG sees a guard's goal change as it sees
+ *            a host setGoal and replans, which makes HOLD a smooth stop.  One extra launch per period; while attached the integration is
+ *            not fused with the next period's OTG step (as with goal schedules).  saip_batch_guard_evaluate enqueues the same launch on
+ *            its own: { saip_batch_contact_sense, saip_batch_guard_evaluate, saip_batch_step_async, saip_batch_integrate } leaves the bits
+ *            of a rollout period.  Without the attachment every entry point enqueues exactly what it did before.
+ *   readout  [SAIP_GUARD_READOUT_ROWS][ld] of the last launch: force norm, moment norm, position error norm, orientation error norm,
+ *            joint speed, position 3.  A row the launch did not need holds NaN.
+ *   state    phase, since, clock [B]; run, fires [G][B]; entry [P][B] (the clock at the first entry into a phase, -1: never); latch [12][B]
+ *            (position 3, rotation 9 row-major).  While attached a state snapshot carries it as segments guard.phase, guard.since,
+ *            guard.clock, guard.run, guard.entry, guard.fires, guard.latch; a snapshot of another guard layout is refused (SAIP_ERR_ORDER,
+ *            the segment named).
+ *   saip_batch_guard_set_guards_host replaces the table and keeps the state.  A writer through saip_batch_guard_guards_device keeps to
+ *   the signals of the table last uploaded from the host: the launch gathers only what that table needs.
+ *   saip_batch_guard_add_cost: cost[i] = cost[i] + (entry[phase][i] >= 0 ? w_time (double)entry[phase][i] : w_miss) on the sampler's
+ *   per-instance cost; w_miss = +inf makes "never got there" an invalid sample.
+ * Only columns 0 .. B-1 of any array are written.
+ * SAIP_ERR_ORDER: before finalize, on a model-only batch, a second attach, any other entry without the attachment, _add_cost without a
+ * sampler.  SAIP_ERR_INVALID_ARGUMENT (the message names the guard or phase, the word and, for a per-instance table, the instance): a task
+ * that is not a motion-force task, n_guards or n_phases outside 1..8, from / to outside the phases, an unknown signal, axis, cmp or mode,
+ * a threshold or offset that is not finite, hold < 1, blank < 0, an integer word that is not an integer, phase 0 not FREE, null tables,
+ * a phase outside the table or a NaN weight in _add_cost.  Argument and order errors are reported before the device is needed and write
+ * nothing. */
+#define SAIP_GUARD_MAX_PHASES 8
+#define SAIP_GUARD_MAX_GUARDS 8
+#define SAIP_GUARD_WORDS 8
+#define SAIP_GUARD_PHASE_WORDS 4
+#define SAIP_GUARD_READOUT_ROWS 8
+#define SAIP_GUARD_PERIODS 0
+#define SAIP_GUARD_FORCE 1
+#define SAIP_GUARD_MOMENT 2
+#define SAIP_GUARD_POSITION 3
+#define SAIP_GUARD_POS_ERROR 4
+#define SAIP_GUARD_ORI_ERROR 5
+#define SAIP_GUARD_JOINT_SPEED 6
+#define SAIP_GUARD_GE 0
+#define SAIP_GUARD_LE 1
+#define SAIP_GUARD_FREE 0
+#define SAIP_GUARD_HOLD 1
+#define SAIP_GUARD_OFFSET 2
+saip_status saip_batch_guard_attach(saip_batch*, int task, int n_guards, const double* guards, int per_instance, int n_phases, const double* phases);
+saip_status saip_batch_guard_detach(saip_batch*);
+saip_status saip_batch_guard_info(saip_batch*, int* task, int* n_guards, int* per_instance, int* n_phases, int* needs_pose);  /* any NULL */
+saip_status saip_batch_guard_set_guards_host(saip_batch*, const double* guards);
+double* saip_batch_guard_guards_device(saip_batch*);  /* [G][8] or [G][8][ld]; NULL when detached */
+saip_status saip_batch_guard_reset(saip_batch*);      /* on the stream */
+saip_status saip_batch_guard_evaluate(saip_batch*);
+saip_status saip_batch_guard_state_host(saip_batch*, int* phase, int* since, int* clock, int* run, int* entry, int* fires, double* latch);  /* any NULL; synchronous */
+saip_status saip_batch_guard_state_device(saip_batch*, int** phase, int** since, int** clock, int** run, int** entry, int** fires, double** latch);  /* the arrays, [rows][ld] */
+saip_status saip_batch_guard_readout_host(saip_batch*, double* out /* [8][B] */);  /* synchronous */
+double* saip_batch_guard_readout_device(saip_batch*);  /* [8][ld]; NULL when detached */
+saip_status saip_batch_guard_add_cost(saip_batch*, int phase, double w_time, double w_miss);
 /* ---- rollout recorder: a per-period trajectory log and running summaries of saip_batch_rollout_async, kept on the device (the
  * reference's example loops print or log the same quantities every period: state, torques, position / orientation error).  A recorder
  * is attached to a finalized batch and stays attached across rollout calls until detached.  It observes rollout periods only

@@ -444,6 +444,40 @@ public:
 		contactMine();
 		check(saip_batch_contact_summary_reset(_batch));
 	}
+	// ---- guards (saip.h): event-triggered phases of the rollout periods on this task's goal.  A guard moves an instance from one phase to
+	// another on what the instance senses; a phase leaves the goal alone (FREE), holds the pose latched at the transition into it (HOLD) or
+	// that pose moved by an offset in the world frame (OFFSET).  Phase 0 must be FREE.  A motion-force task only.
+	struct Guard {
+		int from = 0, to = 0, signal = SAIP_GUARD_PERIODS, axis = 0, cmp = SAIP_GUARD_GE;
+		double threshold = 0.0;
+		int hold = 1, blank = 0;
+	};
+	struct GuardPhase {
+		int mode = SAIP_GUARD_FREE;
+		std::array<double, 3> offset = {0.0, 0.0, 0.0};
+	};
+	void attachGuards(const std::vector<Guard>& guards, const std::vector<GuardPhase>& phases) {
+		need();
+		std::vector<double> g, p;
+		for (const auto& x : guards) g.insert(g.end(), {(double)x.from, (double)x.to, (double)x.signal, (double)x.axis, (double)x.cmp, x.threshold, (double)x.hold, (double)x.blank});
+		for (const auto& x : phases) p.insert(p.end(), {(double)x.mode, x.offset[0], x.offset[1], x.offset[2]});
+		check(saip_batch_guard_attach(_batch, _id, (int)guards.size(), g.empty() ? nullptr : g.data(), 0, (int)phases.size(), p.empty() ? nullptr : p.data()));
+	}
+	// the raw tables: guards [G][8], or [G][8][B] with per_instance; phases [P][4]
+	void attachGuards(const std::vector<double>& guards, int n_guards, const std::vector<double>& phases, int n_phases, bool per_instance = false) {
+		need();
+		const size_t cols = per_instance ? (size_t)saip_batch_size(_batch) : 1;
+		if (n_guards < 1 || guards.size() != (size_t)n_guards * SAIP_GUARD_WORDS * cols || n_phases < 1 || phases.size() != (size_t)n_phases * SAIP_GUARD_PHASE_WORDS)
+			throw std::invalid_argument("attachGuards: expected [n_guards][8] guards, or [n_guards][8][B] per instance, and [n_phases][4] phases");
+		check(saip_batch_guard_attach(_batch, _id, n_guards, guards.data(), per_instance ? 1 : 0, n_phases, phases.data()));
+	}
+	void detachGuards() {
+		need();
+		int task = -1;
+		check(saip_batch_guard_info(_batch, &task, nullptr, nullptr, nullptr, nullptr));
+		if (task != _id) throw std::runtime_error("the guards of this controller are attached to another task");
+		check(saip_batch_guard_detach(_batch));
+	}
 	// ---- contact patches (saip.h): 1..8 contact points (`points`, [n][3], in this task's control frame) on this task's body against the
 	// patch's own planes (format of attachContactPlanes), the net force and moment fed to the integrator and to the simulated sensor.  Up
 	// to two patches per controller, on different motion-force tasks; never together with attachContactPlanes.
@@ -1390,6 +1424,54 @@ public:
 	double* linkContactKeepDevice() { return saip_batch_link_contact_keep_device(_batch); }        // [9 S][ld]; nullptr unless keep
 	// cost += w_impulse * summary impulse + w_peak * summary peak force, after rolloutCost()
 	void linkContactCost(double w_impulse, double w_peak = 0.0) { check(saip_batch_link_contact_add_cost(_batch, w_impulse, w_peak)); }
+	// ---- guards: event-triggered phases inside rollouts (task->attachGuards; saip.h).  rolloutAsync() evaluates them in every period in
+	// front of the OTG step and the cycle; evaluateGuards() does the same for a host-driven loop { contactSense, evaluateGuards, stepAsync,
+	// integrate }.
+	struct GuardInfo {
+		int task = -1, n_guards = 0, per_instance = 0, n_phases = 0, needs_pose = 0;
+	};
+	struct GuardState {
+		std::vector<int> phase, since, clock, run, entry, fires;  // [B], [B], [B], [G][B], [P][B], [G][B]
+		std::vector<double> latch;                                // [12][B]: position 3, rotation 9 row-major
+	};
+	GuardInfo guardInfo() {
+		GuardInfo i;
+		check(saip_batch_guard_info(_batch, &i.task, &i.n_guards, &i.per_instance, &i.n_phases, &i.needs_pose));
+		return i;
+	}
+	void evaluateGuards() {
+		guardInfo();  // without an attachment: that error, before the device is needed
+		pushState();
+		check(saip_batch_guard_evaluate(_batch));
+	}
+	void resetGuards() { check(saip_batch_guard_reset(_batch)); }
+	// waits for the stream
+	GuardState guardState() {
+		const GuardInfo i = guardInfo();
+		const size_t B = (size_t)_robot->batchSize();
+		GuardState s;
+		s.phase.resize(B);
+		s.since.resize(B);
+		s.clock.resize(B);
+		s.run.resize(i.n_guards * B);
+		s.entry.resize(i.n_phases * B);
+		s.fires.resize(i.n_guards * B);
+		s.latch.resize(12 * B);
+		check(saip_batch_guard_state_host(_batch, s.phase.data(), s.since.data(), s.clock.data(), s.run.data(), s.entry.data(), s.fires.data(), s.latch.data()));
+		return s;
+	}
+	// [8][B]: force norm, moment norm, position error norm, orientation error norm, joint speed, position 3 -- of the last launch, NaN where
+	// the tables did not need the quantity; waits for the stream
+	std::vector<double> guardReadout() {
+		std::vector<double> out((size_t)SAIP_GUARD_READOUT_ROWS * _robot->batchSize());
+		check(saip_batch_guard_readout_host(_batch, out.data()));
+		return out;
+	}
+	double* guardTableDevice() { return saip_batch_guard_guards_device(_batch); }  // [G][8] or [G][8][ld]; nullptr when detached
+	// cost += w_time * (period of the first entry into `phase`), or w_miss where the instance never got there, after rolloutCost()
+	void guardCost(int phase, double w_time, double w_miss = std::numeric_limits<double>::infinity()) {
+		check(saip_batch_guard_add_cost(_batch, phase, w_time, w_miss));
+	}
 	// ---- environment schedules: obstacles and contact surfaces that move inside rollouts (saip.h; the contact side: task->setContactSchedule).
 	// keyframes: [K][n][8] obstacle rows, or [K][n][8][B] when the obstacle table is per instance.  The monitor of rollout period c looks at
 	// the state at the END of the period, so it sees the obstacles of period index c + 1; the last keyframe is held.

@@ -926,6 +926,78 @@ class MotionForceTask(_Task):
         self._contact_info()
         self._need_ctrl()._call("saip_batch_contact_summary_reset")
 
+    # -- guards: event-triggered phases and goal switching inside rollouts (saip.h)
+    _GUARD_SIGNALS = {"periods": capi.SAIP_GUARD_PERIODS, "force": capi.SAIP_GUARD_FORCE, "moment": capi.SAIP_GUARD_MOMENT, "position": capi.SAIP_GUARD_POSITION,
+                      "pos_error": capi.SAIP_GUARD_POS_ERROR, "ori_error": capi.SAIP_GUARD_ORI_ERROR, "joint_speed": capi.SAIP_GUARD_JOINT_SPEED}
+    _GUARD_AXES = {"x": 0, "y": 1, "z": 2, "norm": 3}
+    _GUARD_CMPS = {">=": capi.SAIP_GUARD_GE, "<=": capi.SAIP_GUARD_LE}
+    _GUARD_MODES = {"free": capi.SAIP_GUARD_FREE, "hold": capi.SAIP_GUARD_HOLD, "offset": capi.SAIP_GUARD_OFFSET}
+
+    @classmethod
+    def _guard_rows(cls, guards, per_instance, B, who):
+        """the guard table as the C ABI takes it: (G, 8), or (G, 8, B) per instance.  A guard is a dict from, to, signal (a name or its
+        number), axis ('x', 'y', 'z', 'norm' or a number; default 0), cmp ('>=' or '<='), threshold, hold (default 1), blank (default 0);
+        with per_instance any value may be a (B,) array."""
+        guards = list(guards)
+        out = np.zeros((len(guards), capi.SAIP_GUARD_WORDS, B if per_instance else 1))
+        for g, d in enumerate(guards):
+            unknown = set(d) - {"from", "to", "signal", "axis", "cmp", "threshold", "hold", "blank"}
+            if unknown:
+                raise ValueError(f"{who}: guard {g}: unknown keys {sorted(unknown)}")
+            for key in ("from", "to", "signal", "threshold"):
+                if key not in d:
+                    raise ValueError(f"{who}: guard {g}: key [{key}] is missing")
+            sig, axis, cmp = d["signal"], d.get("axis", 0), d.get("cmp", ">=")
+            for name, val, table in (("signal", sig, cls._GUARD_SIGNALS), ("axis", axis, cls._GUARD_AXES), ("cmp", cmp, cls._GUARD_CMPS)):
+                if isinstance(val, str) and val not in table:
+                    raise ValueError(f"{who}: guard {g}: unknown {name} {val!r} (one of {sorted(table)})")
+            words = (d["from"], d["to"], cls._GUARD_SIGNALS.get(sig, sig) if isinstance(sig, str) else sig, cls._GUARD_AXES.get(axis, axis) if isinstance(axis, str) else axis,
+                     cls._GUARD_CMPS.get(cmp, cmp) if isinstance(cmp, str) else cmp, d["threshold"], d.get("hold", 1), d.get("blank", 0))
+            for k, w in enumerate(words):
+                w = np.asarray(w, float)
+                if w.ndim and not (per_instance and w.shape == (B,)):
+                    raise ValueError(f"{who}: guard {g}: a scalar{' or a (%d,) array' % B if per_instance else ''} expected for word {k}, got shape {w.shape}")
+                out[g, k, :] = w
+        return np.ascontiguousarray(out if per_instance else out[:, :, 0])
+
+    def attachGuards(self, guards, phases, per_instance=False):
+        """make the rollout closed loop in time: every instance carries a phase, `guards` move it on what the instance senses, `phases`
+        say what a phase does to this task's goal.  guards: 1..8 dicts (see _guard_rows), e.g. dict(**{'from': 0}, to=1, signal='force',
+        axis='norm', cmp='>=', threshold=5.0, hold=2); phases: 1..8 dicts mode ('free', 'hold', 'offset') and, for 'offset', offset (3,)
+        in the world frame.  Phase 0 must be 'free'.  A 'hold' phase keeps the pose latched at the transition into it, 'offset' that pose
+        moved by the offset.  rolloutAsync() evaluates the guards in every period in front of the OTG step and the cycle;
+        ctrl.evaluateGuards() does the same for a host-driven loop."""
+        ctrl = self._need_ctrl()
+        a = self._guard_rows(guards, per_instance, ctrl.batch_size, "attachGuards")
+        phases = list(phases)
+        ph = np.zeros((len(phases), capi.SAIP_GUARD_PHASE_WORDS))
+        for p, d in enumerate(phases):
+            mode = d.get("mode", "free")
+            if isinstance(mode, str) and mode not in self._GUARD_MODES:
+                raise ValueError(f"attachGuards: phase {p}: unknown mode {mode!r} (one of {sorted(self._GUARD_MODES)})")
+            ph[p, 0] = self._GUARD_MODES[mode] if isinstance(mode, str) else mode
+            off = np.asarray(d.get("offset", (0.0, 0.0, 0.0)), float).reshape(-1)
+            if off.shape != (3,):
+                raise ValueError(f"attachGuards: phase {p}: an offset of shape (3,) expected, got {off.shape}")
+            ph[p, 1:] = off
+        ctrl._call("saip_batch_guard_attach", self._id, a.shape[0], _dptr(a), int(bool(per_instance)), ph.shape[0], _dptr(ph))
+
+    def detachGuards(self):
+        ctrl = self._need_ctrl()
+        info = ctrl.guardInfo()
+        if info["task"] != self._id:
+            raise capi.SaipError(f"the guards of this controller are attached to task {info['task']}, not to [{self.getTaskName()}]")
+        ctrl._call("saip_batch_guard_detach")
+
+    def setGuards(self, guards):
+        """replace the guard table (as many guards as attached); phases, counters and latches stay"""
+        ctrl = self._need_ctrl()
+        info = ctrl.guardInfo()
+        a = self._guard_rows(guards, info["per_instance"], ctrl.batch_size, "setGuards")
+        if a.shape[0] != info["n_guards"]:
+            raise ValueError(f"setGuards: {info['n_guards']} guards expected, got {a.shape[0]}")
+        ctrl._call("saip_batch_guard_set_guards_host", _dptr(a))
+
     # -- contact patches: up to eight contact points on this task's body, net force and moment, a wrench sensor (saip.h)
     def attachContactPatch(self, points, planes, sensor=True, per_instance=False):
         """multi-point contact: `points` (n, 3), 1..8 offsets in this task's control frame, against the patch's own 1..4 planes (format of
@@ -1658,6 +1730,48 @@ class RobotController:
         self._call("saip_batch_contact_patch_info", -1, None, None, None, None, None, None)  # without a patch: that error, before the device is needed
         self._push_state()
         self._call("saip_batch_contact_patch_sense")
+
+    # -- guards: event-triggered phases inside rollouts (task.attachGuards; saip.h)
+    def guardInfo(self):
+        """dict task, n_guards, per_instance, n_phases, needs_pose"""
+        v = [C.c_int(0) for _ in range(5)]
+        self._call("saip_batch_guard_info", *(C.byref(x) for x in v))
+        return dict(task=v[0].value, n_guards=v[1].value, per_instance=bool(v[2].value), n_phases=v[3].value, needs_pose=bool(v[4].value))
+
+    def evaluateGuards(self):
+        """enqueue one evaluation of the guards at the current state: what a rollout period does in front of its OTG step and cycle, for a
+        host-driven loop { contactSense, evaluateGuards, stepAsync, integrate }"""
+        self.guardInfo()  # without an attachment: that error, before the device is needed
+        self._push_state()
+        self._call("saip_batch_guard_evaluate")
+
+    def resetGuards(self):
+        """every instance back to phase 0 with counters, entry times and latches cleared, on the engine stream"""
+        self._call("saip_batch_guard_reset")
+
+    def guardState(self):
+        """dict phase (B,), since (B,), clock (B,), run (G, B), entry (P, B) (the period of the first entry into a phase, -1: never),
+        fires (G, B), latch (12, B) (position 3, rotation 9 row-major) (waits for the engine stream)"""
+        info = self.guardInfo()
+        B, G, P = self.batch_size, info["n_guards"], info["n_phases"]
+        a = dict(phase=np.zeros(B, np.int32), since=np.zeros(B, np.int32), clock=np.zeros(B, np.int32), run=np.zeros((G, B), np.int32),
+                 entry=np.zeros((P, B), np.int32), fires=np.zeros((G, B), np.int32), latch=np.zeros((12, B)))
+        ip = C.POINTER(C.c_int)
+        self._call("saip_batch_guard_state_host", *(a[k].ctypes.data_as(ip) for k in ("phase", "since", "clock", "run", "entry", "fires")), _dptr(a["latch"]))
+        return a
+
+    def guardReadout(self):
+        """dict of what the last guard launch saw: force, moment, pos_error, ori_error (norms), joint_speed (B,) and position (B, 3); NaN
+        where the guard and phase tables did not need the quantity (waits for the engine stream)"""
+        self.guardInfo()
+        out = np.empty((capi.SAIP_GUARD_READOUT_ROWS, self.batch_size))
+        self._call("saip_batch_guard_readout_host", _dptr(out))
+        return dict(force=out[0].copy(), moment=out[1].copy(), pos_error=out[2].copy(), ori_error=out[3].copy(), joint_speed=out[4].copy(), position=out[5:8].T.copy())
+
+    def guardCost(self, phase, w_time, w_miss=float("inf")):
+        """cost += w_time * (period of the first entry into `phase`), or w_miss where the instance never got there, on the device, after
+        rolloutCost(); the default w_miss makes "never got there" an invalid sample to updateSampler()"""
+        self._call("saip_batch_guard_add_cost", int(phase), float(w_time), float(w_miss))
 
     # -- clearance monitor: link spheres against world-fixed obstacles and against each other, inside rollouts (saip.h)
     @staticmethod

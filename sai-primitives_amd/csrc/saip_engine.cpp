@@ -137,6 +137,7 @@ extern "C" void saip_batch_destroy(saip_batch* b) {
 		plant_free(b);
 		inertia_free(b);
 		sensing_free(b);
+		guard_free(b);
 		if (b->stream) (void)hipStreamDestroy(b->stream);
 	}
 	delete b;

@@ -28,6 +28,7 @@
 #include "saip_inertia.h"
 #include "saip_sense.h"
 #include "saip_sense_chain.h"
+#include "saip_guard.h"
 
 namespace saip {
 hipError_t launch_cycle_wg(const CycleParams& P, bool tree, hipStream_t stream);
@@ -77,6 +78,9 @@ hipError_t launch_sense_apply(const SenseParams& P, hipStream_t stream);
 hipError_t launch_sense_randomize(const SenseRandomParams& P, hipStream_t stream);
 hipError_t launch_sense_chain_apply(const SenseChainParams& C, hipStream_t stream);
 hipError_t launch_sense_chain_randomize(const SenseChainRandomParams& P, hipStream_t stream);
+hipError_t launch_guard_apply(const GuardParams& P, bool tree, hipStream_t stream);
+hipError_t launch_guard_reset(const GuardParams& P, hipStream_t stream);
+hipError_t launch_guard_add_cost(int B, const int* entry_row, double* cost, double w_time, double w_miss, hipStream_t stream);
 }  // namespace saip
 
 using saip::CycleParams;
@@ -323,6 +327,20 @@ struct saip_batch {
 		Chain chain;                         // saip_batch_sensing_chain_attach: the sensing chain (saip_sense_chain.hip), snapshot segments sense.chain.*
 		double chain_sample_time = 0;        // what its finite-difference velocity divides by; 0 while no chain is attached
 	} sensing;
+	// saip_batch_guard_attach: event-triggered phases of the rollout periods (saip_guard.hip), at most one per batch, on one motion-force
+	// task.  The tables are configuration and the readout is scratch; phase, since, clock, run, entry, fires and latch are state: on the
+	// snapshot directory while attached (segments guard.*).  Nothing of it lives in a host scalar: the period counter `clock` is a
+	// per-instance device word.  Its arrays are its own (freed by _detach), not part of `allocs`.
+	struct Guard {
+		bool attached = false;
+		int task = -1, G = 0, P = 0, per_instance = 0;
+		int need_guards = 0, need_phases = 0;  // GUARD_NEED_* bits of the guard table's signals and of the phase table's modes
+		double* guards = nullptr;            // [G][8] (batch-uniform) or [G][8][ld]
+		double* phases = nullptr;            // [P][4]
+		int* ints = nullptr;                 // [3 + 2 G + P][ld]: phase, since, clock, run [G], entry [P], fires [G]
+		double* latch = nullptr;             // [12][ld]
+		double* readout = nullptr;           // [8][ld]
+	} guard;
 };
 
 namespace saip {
@@ -460,6 +478,10 @@ void sensing_free(saip_batch* b);
 int sensing_sensor_slots(const saip_batch* b, bool planes, bool patches);
 saip_status sensing_launch(saip_batch* b, int mode, int slot_mask);
 saip_status sensing_refresh(saip_batch* b);
+// ---- saip_engine_guard.cpp
+void guard_free(saip_batch* b);
+saip_status guard_launch(saip_batch* b);
+void guard_segments(const saip_batch* b, saip::GuardParams* P);  // where the state arrays live (the snapshot directory)
 // ---- saip_engine_rollout.cpp
 void record_free(saip_batch* b);
 void schedule_release(saip_batch* b, int task);

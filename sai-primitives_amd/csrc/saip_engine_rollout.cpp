@@ -389,7 +389,8 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 	for (int i = 0; i < 3; i++) sim.gravity[i] = gravity ? gravity[i] : b->model->dev.gravity[i];
 	// with a goal schedule attached every period starts with the launch that writes its goals, and the integration is never fused with
 	// the next period's OTG step (which would read the next goal before it is written)
-	const bool scheduled = b->n_sched > 0;
+	// guards attached: the same for the integration, since the guard may rewrite the goal the next period's OTG step has to read
+	const bool scheduled = b->n_sched > 0, goals_written = scheduled || b->guard.attached;
 	// with contact planes attached neither fused form is used: the contact force sits between the cycle and every integration substep
 	// (contact patches: the same, with their kernel)
 	// a plant model does the same: it sits between the cycle and every integration substep
@@ -412,6 +413,9 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 		if (b->sensing.attached &&
 			(st = sensing_launch(b, (b->sensing.epoch != b->state_epoch ? saip::SENSE_MODE_JOINTS : 0) | saip::SENSE_MODE_WRENCH, sense_slots)))
 			return st;
+		// guards: this period's evaluation behind everything that writes what it reads (goals, sensed wrench, measurement) and in front of
+		// the OTG step and the cycle, which see a goal it writes as they see a host setGoal
+		if (b->guard.attached && (st = guard_launch(b))) return st;
 		// no internal OTG in the stack: the cycle launch integrates the state itself when it can (eight-lane kernel, no slow path behind)
 		bool integrated = false;
 		saip_status s2 = launch_cycle(b, false, (!any_otg && b->model->n == 7 && !contact) ? &sim : nullptr, &integrated);
@@ -422,7 +426,7 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 		if (integrated) {  // the bookkeeping of enqueue_integrate
 			b->models_valid = false;
 			b->state_epoch++;
-		} else if ((s2 = enqueue_integrate(b, sim_dt, substeps, gravity, damping, more && !scheduled))) {
+		} else if ((s2 = enqueue_integrate(b, sim_dt, substeps, gravity, damping, more && !goals_written))) {
 			b->otg_prelaunched = false;
 			return s2;
 		}

@@ -71,6 +71,18 @@ static void snapshot_directory(const saip_batch* b, std::vector<SnapSegHost>& D)
 		soa(p + "filt", H.filt, K.filt_rows * n, 8);
 		soa(p + "primed", H.primed, n, 4);
 	}
+	// the guards: phase, counters and latch of every instance; absent while detached, like the chains
+	if (b->guard.attached) {
+		saip::GuardParams P;
+		guard_segments(b, &P);
+		soa("guard.phase", P.phase, 1, 4);
+		soa("guard.since", P.since, 1, 4);
+		soa("guard.clock", P.clock, 1, 4);
+		soa("guard.run", P.run, P.G, 4);
+		soa("guard.entry", P.entry, P.P, 4);
+		soa("guard.fires", P.fires, P.G, 4);
+		soa("guard.latch", P.latch, saip::GUARD_LATCH_ROWS, 8);
+	}
 }
 static_assert(sizeof(saip::ShState) % 4 == 0, "ShState is moved as 4- or 8-byte words");
 static uint64_t snapshot_fingerprint(const saip_batch* b, const std::vector<SnapSegHost>& D) {

@@ -1,0 +1,42 @@
+"""Resident guards through the header-only C++ facade (tests/cpp/guard_example.cpp): it compiles against the header and links, its host
+checks pass without a device, and on the GPU a timed stop and retract inside a rollout at B = 70; the example checks itself."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import workloads as W
+from test_rollout_record_cpu import _robot_file
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "sai-primitives_amd")
+
+
+def build_example(tmp_path):
+    exe = str(tmp_path / "guard_example")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-o", exe, os.path.join(ROOT, "tests", "cpp", "guard_example.cpp"),
+                           "-L" + PKG, "-lsaip", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    return exe
+
+
+def test_cpp_guard_example_host_checks(tmp_path):
+    import sai_primitives_amd as sp
+    sp.build_library()
+    exe = build_example(tmp_path)
+    out = subprocess.run([exe, _robot_file(tmp_path), "cfgonly"], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and "GUARD_CFG_OK" in out.stdout, out.stdout + out.stderr
+
+
+@pytest.mark.gpu
+def test_cpp_guard_rollout(tmp_path):
+    import sai_primitives_amd as sp
+    sp.build_library()
+    exe = build_example(tmp_path)
+    B, K = 70, 12
+    q = W.make_inputs(2, B)["q"]
+    qf = tmp_path / "q.bin"
+    np.ascontiguousarray(q.T).tofile(qf)
+    out = subprocess.run([exe, _robot_file(tmp_path), "run", str(B), str(K), str(qf)], capture_output=True, text=True, timeout=300)
+    print(out.stdout)
+    assert out.returncode == 0 and "GUARD_RUN_OK" in out.stdout, out.stdout + out.stderr

@@ -49,7 +49,10 @@
    --env-schedule {obstacles,planes,both} [--env-mode hold|linear] [--substeps S] times, interleaved in the same run, the closed-loop period
    with a clearance monitor (8 spheres, 4 obstacles) and / or one per-instance contact plane attached, without and with an environment
    schedule of three keyframes over the timed rollout on their tables, and the event-timed mean of 200 one-substep integrate calls both
-   ways: with planes that is the static against the MOVING contact launch."""
+   ways: with planes that is the static against the MOVING contact launch.
+   --guards times, interleaved in the same run, the closed-loop period without and with resident guards on the motion-force task (a force
+   guard into a HOLD phase, a timed guard into an OFFSET phase, so that the launch walks the kinematics and writes the goal) and the
+   event-timed mean of 200 back-to-back evaluations alone."""
 import argparse
 import os
 import sys
@@ -115,6 +118,7 @@ ap.add_argument("--link-contact", action="store_true")
 ap.add_argument("--lc-spheres", type=int, default=8)
 ap.add_argument("--lc-obstacles", type=int, default=4)
 ap.add_argument("--lc-per-instance", action="store_true")
+ap.add_argument("--guards", action="store_true")
 ap.add_argument("--env-schedule", choices=("obstacles", "planes", "both"), default=None)
 ap.add_argument("--env-mode", choices=("hold", "linear"), default="linear")
 ap.add_argument("--plant", action="store_true")
@@ -406,6 +410,40 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
             print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {args.substeps}: "
                   f"closed-loop period {plain:.1f} us; with a clearance monitor of {S} spheres, {O} obstacles, {P} pairs {with_c:.1f} us; without it again "
                   f"{again:.1f} us; one evaluation alone {alone:.2f} us ({under} of {B} instances under the margin)")
+        continue
+    if args.guards:
+        # the sensed force is 0 without a contact: "norm >= 0" fires in the first period, HOLD for 100 periods, then OFFSET for the rest
+        guards = [{"from": 0, "to": 1, "signal": "force", "axis": "norm", "cmp": ">=", "threshold": 0.0},
+                  {"from": 1, "to": 2, "signal": "periods", "threshold": 100}]
+        phases = [dict(mode="free"), dict(mode="hold"), dict(mode="offset", offset=(0.0, 0.0, 0.01))]
+        timed_us, _ = stream_timer(ctrl)
+
+        def period_us():
+            t0 = time.perf_counter()
+            ctrl.rolloutAsync(K, 5e-4, args.substeps, gravity=(0, 0, 0))
+            ctrl.synchronize()
+            return (time.perf_counter() - t0) / K * 1e6
+
+        for _ in range(args.repeats):
+            snap = ctrl.saveState()
+            plain = period_us()
+            ctrl.restoreState(snap)
+            snap.close()
+            mf.attachGuards(guards, phases)
+            snap = ctrl.saveState()
+            period_us()
+            ctrl.restoreState(snap)
+            ctrl.resetGuards()
+            with_g = period_us()
+            alone = timed_us(lambda: ctrl._call("saip_batch_guard_evaluate"), 200, first=ctrl.evaluateGuards)
+            offset = int((ctrl.guardState()["phase"] == 2).sum())
+            ctrl.restoreState(snap)
+            snap.close()
+            mf.detachGuards()
+            again = period_us()
+            print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {args.substeps}: "
+                  f"closed-loop period {plain:.1f} us; with guards (force -> HOLD -> OFFSET) {with_g:.1f} us; without them again {again:.1f} us; "
+                  f"one evaluation alone {alone:.2f} us ({offset} of {B} instances ended in the OFFSET phase)")
         continue
     if args.link_contact:
         S, O = args.lc_spheres, args.lc_obstacles
