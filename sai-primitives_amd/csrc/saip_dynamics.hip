@@ -8,7 +8,7 @@
 //   dq <- dq + dt qdd ;  q <- q + dt dq     (semi-implicit Euler, `substeps` times per call with the torque held)
 //
 // One lane per instance (7-dof chains run saip_dynamics_oct.hip instead: eight lanes per instance).  Bias forces by one recursive Newton-Euler pass in world coordinates, M(q) from composite rigid bodies
-// (spatial inertias about the world origin, suffix sums along the chain), Cholesky solve.  Per-body arrays are lane-private
+// (spatial inertias about the joint origins, suffix sums along the chain), Cholesky solve.  Per-body arrays are lane-private
 // (scratch for NMAX = 32, mostly registers for NMAX = 8); the kernel is FP64-latency bound like the cycle kernels and is not on the
 // benchmarked path.
 #include <hip/hip_runtime.h>

@@ -207,10 +207,14 @@ __device__ void rnea_tree(const ModelDev& md, int n, const Chain<NMAX>& K, const
 
 }  // namespace
 
-// Joint-space inertia from composite rigid bodies in world coordinates (serial chain: every later body is a descendant).
-// Spatial inertia about the world origin O: mass m, first moment hm = m c, rotational inertia Io = R I R^T + m (c.c 1 - c c^T).
-// Column j: momentum of the composite body j.. under the unit motion of joint j, (p, L_O) = Ic_j s_j with s_j = (z_j, o_j x z_j) for a
-// revolute and (0, z_j) for a prismatic joint; M_ij = s_i . (L_O, p) for i <= j.
+// Joint-space inertia from composite rigid bodies in world axes (serial chain: every later body is a descendant).
+// Spatial inertia of the composite j.. about the origin o_j of its own joint: mass cm, first moment ch = sum m (c - o_j), rotational inertia
+// cI = sum R I R^T + m (r.r 1 - r r^T), r = c - o_j.  Going from joint j + 1 to joint j the reference point moves by d = o_{j+1} - o_j:
+// cI += 2 (g.d) 1 - g d^T - d g^T with g = ch + cm d / 2, then ch += cm d.  Column j: momentum of the composite under the unit motion of joint
+// j, (p, L) = Ic_j s_j with s_j = (z_j, 0) for a revolute and (0, z_j) for a prismatic joint; M_ij = s_i . (L, p) for i <= j, where joint i
+// moves the point o_j with (o_i - o_j) x z_i.
+// (Not about the world origin: there every entry carries a rounding of eps m |c|^2, |c| the distance from the origin, which swamps a small
+// distal inertia -- the last wrist joint of a 6R arm of the PUMA layout, M_66 = 1.5e-4 at 1.5 m, was off by 3e2 n eps of its own sum.)
 template <int NMAX, class IN = ModelInertials>
 __device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, const int n, const Chain<NMAX>& K, double (&M)[NMAX][NMAX], const IN in = IN()) {
 	double cm = 0.0;
@@ -219,9 +223,22 @@ __device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, const int n,
 #pragma unroll
 	for (int jj = 0; jj < n; jj++) {
 		const int j = n - 1 - jj;
+		const V3 oj = K.o[j];
+		if (jj > 0) {  // the composite j + 1.. about o_j
+			const V3 d = K.o[j + 1] - oj;
+			const V3 g = ch + (0.5 * cm) * d;
+			const double gd = dot(g, d);
+			cI[0] += 2.0 * (gd - g.x * d.x);
+			cI[1] += 2.0 * (gd - g.y * d.y);
+			cI[2] += 2.0 * (gd - g.z * d.z);
+			cI[3] -= g.x * d.y + g.y * d.x;
+			cI[4] -= g.x * d.z + g.z * d.x;
+			cI[5] -= g.y * d.z + g.z * d.y;
+			ch = ch + cm * d;
+		}
 		// add body j to the composite
 		const double m = in.mass(md, j);
-		const V3 c = K.c[j];
+		const V3 c = K.c[j] - oj;
 		const double* R = K.R[j];
 		double I6s[6];
 		const double* I6 = in.inertia(md, j, I6s);
@@ -245,7 +262,7 @@ __device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, const int n,
 		// unit motion of joint j
 		const bool rev = md.jtype[j] == 1;
 		const V3 wj = rev ? K.z[j] : v3(0, 0, 0);
-		const V3 vj = rev ? cross(K.o[j], K.z[j]) : K.z[j];
+		const V3 vj = rev ? v3(0, 0, 0) : K.z[j];
 		const V3 p = cm * vj + cross(wj, ch);
 		const V3 L = v3(cI[0] * wj.x + cI[3] * wj.y + cI[4] * wj.z, cI[3] * wj.x + cI[1] * wj.y + cI[5] * wj.z, cI[4] * wj.x + cI[5] * wj.y + cI[2] * wj.z) +
 					 cross(ch, vj);
@@ -254,7 +271,7 @@ __device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, const int n,
 			if (i > j) continue;
 			const bool ri = md.jtype[i] == 1;
 			const V3 wi = ri ? K.z[i] : v3(0, 0, 0);
-			const V3 vi = ri ? cross(K.o[i], K.z[i]) : K.z[i];
+			const V3 vi = ri ? cross(K.o[i] - oj, K.z[i]) : K.z[i];
 			const double v = dot(wi, L) + dot(vi, p);
 			M[i][j] = v;
 			M[j][i] = v;
@@ -262,15 +279,12 @@ __device__ __forceinline__ void mass_matrix_crb(const ModelDev& md, const int n,
 	}
 }
 
-// mass_matrix_crb of a kinematic tree: the composite of body j sums its subtree (ModelDev::desc) and M_ij, i < j, is nonzero only for i an
-// ancestor of j (ModelDev::anc)
+// mass_matrix_crb of a kinematic tree: the composite of body j sums its subtree (ModelDev::desc), every body about o_j, and M_ij, i < j, is
+// nonzero only for i an ancestor of j (ModelDev::anc)
 template <int NMAX, class IN = ModelInertials>
 __device__ void mass_matrix_crb_tree(const ModelDev& md, const int n, const Chain<NMAX>& K, double (&M)[NMAX][NMAX], const IN in = IN()) {
 	double bm[NMAX], bI[NMAX][6];
-	V3 bh[NMAX];
-	for (int j = 0; j < n; j++) {  // spatial inertia of body j about the world origin
-		const double m = in.mass(md, j);
-		const V3 c = K.c[j];
+	for (int j = 0; j < n; j++) {  // mass of body j and its rotational inertia about its centre of mass, world axes
 		const double* R = K.R[j];
 		double I6s[6];
 		const double* I6 = in.inertia(md, j, I6s);
@@ -280,29 +294,36 @@ __device__ void mass_matrix_crb_tree(const ModelDev& md, const int n, const Chai
 			RI[3 * r + 1] = R[3 * r] * I6[3] + R[3 * r + 1] * I6[1] + R[3 * r + 2] * I6[5];
 			RI[3 * r + 2] = R[3 * r] * I6[4] + R[3 * r + 1] * I6[5] + R[3 * r + 2] * I6[2];
 		}
-		const double cc = dot(c, c);
-		bI[j][0] = RI[0] * R[0] + RI[1] * R[1] + RI[2] * R[2] + m * (cc - c.x * c.x);
-		bI[j][1] = RI[3] * R[3] + RI[4] * R[4] + RI[5] * R[5] + m * (cc - c.y * c.y);
-		bI[j][2] = RI[6] * R[6] + RI[7] * R[7] + RI[8] * R[8] + m * (cc - c.z * c.z);
-		bI[j][3] = RI[0] * R[3] + RI[1] * R[4] + RI[2] * R[5] - m * c.x * c.y;
-		bI[j][4] = RI[0] * R[6] + RI[1] * R[7] + RI[2] * R[8] - m * c.x * c.z;
-		bI[j][5] = RI[3] * R[6] + RI[4] * R[7] + RI[5] * R[8] - m * c.y * c.z;
-		bm[j] = m;
-		bh[j] = m * c;
+		bI[j][0] = RI[0] * R[0] + RI[1] * R[1] + RI[2] * R[2];
+		bI[j][1] = RI[3] * R[3] + RI[4] * R[4] + RI[5] * R[5];
+		bI[j][2] = RI[6] * R[6] + RI[7] * R[7] + RI[8] * R[8];
+		bI[j][3] = RI[0] * R[3] + RI[1] * R[4] + RI[2] * R[5];
+		bI[j][4] = RI[0] * R[6] + RI[1] * R[7] + RI[2] * R[8];
+		bI[j][5] = RI[3] * R[6] + RI[4] * R[7] + RI[5] * R[8];
+		bm[j] = in.mass(md, j);
 	}
 	for (int j = 0; j < n; j++) {
 		double cm = 0.0, cI[6] = {0, 0, 0, 0, 0, 0};
 		V3 ch = v3(0, 0, 0);
+		const V3 oj = K.o[j];
 		const uint32_t dm = md.desc[j];
 		for (int l = j; l < n; l++) {
 			if (!((dm >> l) & 1u)) continue;
-			cm += bm[l];
-			ch = ch + bh[l];
-			for (int e = 0; e < 6; e++) cI[e] += bI[l][e];
+			const double m = bm[l];
+			const V3 c = K.c[l] - oj;
+			const double cc = dot(c, c);
+			cm += m;
+			ch = ch + m * c;
+			cI[0] += bI[l][0] + m * (cc - c.x * c.x);
+			cI[1] += bI[l][1] + m * (cc - c.y * c.y);
+			cI[2] += bI[l][2] + m * (cc - c.z * c.z);
+			cI[3] += bI[l][3] - m * c.x * c.y;
+			cI[4] += bI[l][4] - m * c.x * c.z;
+			cI[5] += bI[l][5] - m * c.y * c.z;
 		}
 		const bool rev = md.jtype[j] == 1;
 		const V3 wj = rev ? K.z[j] : v3(0, 0, 0);
-		const V3 vj = rev ? cross(K.o[j], K.z[j]) : K.z[j];
+		const V3 vj = rev ? v3(0, 0, 0) : K.z[j];
 		const V3 p = cm * vj + cross(wj, ch);
 		const V3 L = v3(cI[0] * wj.x + cI[3] * wj.y + cI[4] * wj.z, cI[3] * wj.x + cI[1] * wj.y + cI[5] * wj.z, cI[4] * wj.x + cI[5] * wj.y + cI[2] * wj.z) +
 					 cross(ch, vj);
@@ -312,7 +333,7 @@ __device__ void mass_matrix_crb_tree(const ModelDev& md, const int n, const Chai
 			if ((am >> i) & 1u) {
 				const bool ri = md.jtype[i] == 1;
 				const V3 wi = ri ? K.z[i] : v3(0, 0, 0);
-				const V3 vi = ri ? cross(K.o[i], K.z[i]) : K.z[i];
+				const V3 vi = ri ? cross(K.o[i] - oj, K.z[i]) : K.z[i];
 				v = dot(wi, L) + dot(vi, p);
 			}
 			M[i][j] = v;

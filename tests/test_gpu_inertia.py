@@ -130,7 +130,7 @@ def test_one_step_matches_the_oracle_of_every_instance(sp, name, B, ld):
             ref = np.concatenate([rs.forward_dynamics(models[i], q[i:i + 1], dq[i:i + 1], tau[i:i + 1], g=grav, damping=damping) for i in range(B)])
             err = np.abs(qdd - ref).max() / max(1.0, np.abs(ref).max())
             print(name, B, "gravity", grav, "max rel qdd error", err)
-            assert err < 1e-6
+            assert err < 1e-8
     ctrl.detachInertia()
 
 
@@ -150,7 +150,7 @@ def test_one_step_with_a_batch_uniform_table(sp):
         ref = RS.forward_dynamics(model, q, dq, tau, g=grav, damping=damping)
         err = np.abs(qdd - ref).max() / max(1.0, np.abs(ref).max())
         print("batch-uniform table, gravity", grav, "max rel qdd error", err)
-        assert err < 1e-6
+        assert err < 1e-8
 
 
 # ------------------------------------------------------------------ 2. the table is used
@@ -178,10 +178,10 @@ def test_a_payload_in_the_hand_changes_the_acceleration(sp):
     err = np.abs(qdd - ref).max() / max(1.0, np.abs(ref).max())
     print("payload oracle against bare oracle, per instance:", apart.min(), "..", apart.max(), "| device against the payload oracle", err)
     assert (apart > 1e-3).all()
-    assert err < 1e-6
+    assert err < 1e-8
     ctrl.detachInertia()
     qdd0 = _one_step(robot, ctrl, d["q"], dq, tau, grav, damping)
-    assert np.abs(qdd0 - bare).max() / max(1.0, np.abs(bare).max()) < 1e-6          # detached: the model's robot again
+    assert np.abs(qdd0 - bare).max() / max(1.0, np.abs(bare).max()) < 1e-8          # detached: the model's robot again
 
 
 # ------------------------------------------------------------------ 3. the neutral table

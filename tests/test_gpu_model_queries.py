@@ -152,11 +152,11 @@ def test_dynamics_match_numpy(sp, name):
     # b = C(q, dq) dq: the Lagrangian expression of forward_dynamics with tau = 0 and no gravity is qdd = -M^-1 b
     qdd0 = RS.forward_dynamics(m, q, dq, np.zeros_like(q), g=(0.0, 0.0, 0.0))
     bref = -np.einsum("bij,bj->bi", Mref, qdd0)
-    ok, err = _close(b, bref, 1e-7)
+    ok, err = _close(b, bref, 1e-8)
     assert ok, err
     # M^-1 (tau - b - g) is the forward dynamics
     tau = np.random.default_rng(5).uniform(-20, 20, size=q.shape)
-    ok, err = _close(np.einsum("bij,bj->bi", Minv, tau - b - g), RS.forward_dynamics(m, q, dq, tau), 1e-7)
+    ok, err = _close(np.einsum("bij,bj->bi", Minv, tau - b - g), RS.forward_dynamics(m, q, dq, tau), 1e-8)
     assert ok, err
     # b vanishes exactly at rest
     robot.setDq(np.zeros_like(dq))

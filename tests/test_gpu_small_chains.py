@@ -247,7 +247,7 @@ def test_dynamics_and_integration_small_and_fixed_link_chains(sp, key, B):
         ref = RS.forward_dynamics(m, q, dq, tau, g=grav, damping=damping)
         err = np.abs((dq1 - dq) / dt - ref).max() / max(1.0, np.abs(ref).max())
         errs[f"qdd {'gravity' if damping == 0 else 'damped'}"] = err
-        assert err < 1e-6, (key, B, grav, err)
+        assert err < 1e-8, (key, B, grav, err)
         assert np.abs(q1 - (q + dt * dq1)).max() < 1e-15
     print(f"dynamics n={n} ({key}) B={B}: " + ", ".join(f"{k} {v:.1e}" for k, v in errs.items()))
 

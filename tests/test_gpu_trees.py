@@ -276,7 +276,7 @@ def test_tree_model_queries_and_integrate(sp, case):
         q1, dq1 = ctrl.pullState()
         ref = RS.forward_dynamics(m, q, dq, tau)
         qdd = (dq1 - dq) / dt
-        assert np.abs(qdd - ref).max() / max(1.0, np.abs(ref).max()) < 1e-6
+        assert np.abs(qdd - ref).max() / max(1.0, np.abs(ref).max()) < 1e-8
 
 
 def test_tree_pose_and_reinit(sp):
