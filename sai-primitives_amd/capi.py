@@ -8,7 +8,7 @@ import subprocess
 _DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_DIR, "libsaip.so")
 SOURCES = ["csrc/saip_engine.cpp", "csrc/saip_engine_model.cpp", "csrc/saip_engine_contact.cpp", "csrc/saip_engine_clearance.cpp", "csrc/saip_engine_link_contact.cpp", "csrc/saip_engine_env.cpp", "csrc/saip_engine_chain.cpp", "csrc/saip_engine_plant.cpp", "csrc/saip_engine_inertia.cpp", "csrc/saip_engine_sensing.cpp", "csrc/saip_engine_guard.cpp", "csrc/saip_engine_rollout.cpp", "csrc/saip_engine_snapshot.cpp", "csrc/saip_engine_sampler.cpp", "csrc/saip_engine_query.cpp", "csrc/saip_comm.cpp", "csrc/saip_kernel_wg.hip", "csrc/saip_kernel_lane.hip", "csrc/saip_kernel_lane_lean.hip", "csrc/saip_kernel_oct.hip", "csrc/saip_kernel_octjf.hip", "csrc/saip_kernel_wave.hip", "csrc/saip_otg.hip", "csrc/saip_dynamics.hip", "csrc/saip_dynamics_oct.hip", "csrc/saip_task_diag.hip", "csrc/saip_model_query.hip", "csrc/saip_rollout_record.hip", "csrc/saip_goal_schedule.hip", "csrc/saip_state_snapshot.hip", "csrc/saip_sampler.hip", "csrc/saip_contact.hip", "csrc/saip_contact_patch.hip", "csrc/saip_clearance.hip", "csrc/saip_link_contact.hip", "csrc/saip_env_schedule.hip", "csrc/saip_plant.hip", "csrc/saip_inertia.hip", "csrc/saip_sense.hip", "csrc/saip_sense_chain.hip", "csrc/saip_guard.hip"]
-HEADERS = ["csrc/saip_device.h", "csrc/saip_cycle_plan.h", "csrc/saip_engine_internal.h", "csrc/saip_state_snapshot.h", "csrc/saip_sampler.h", "csrc/saip_contact.h", "csrc/saip_contact_patch.h", "csrc/saip_clearance.h", "csrc/saip_link_contact.h", "csrc/saip_env_schedule.h", "csrc/saip_plant.h", "csrc/saip_plant_chain.h", "csrc/saip_inertia.h", "csrc/saip_sense.h", "csrc/saip_sense_chain.h", "csrc/saip_guard.h", "csrc/saip_law.h", "csrc/saip_wg_linalg.h", "csrc/saip_wg_cycle.h", "csrc/saip_fk.h", "csrc/saip_oct_common.h", "csrc/saip_oct_joint_tails.h", "csrc/saip_oct_slow_tail.h", "csrc/saip_wave_prims.h", "csrc/saip_dynamics_oct_body.h", "csrc/saip_otg3.h", "csrc/saip_otg3_step1.h", "csrc/saip_otg3_step2.h", "csrc/saip_rbd.h", "../include/saip.h"]
+HEADERS = ["csrc/saip_device.h", "csrc/saip_cycle_plan.h", "csrc/saip_period_plan.h", "csrc/saip_engine_internal.h", "csrc/saip_state_snapshot.h", "csrc/saip_sampler.h", "csrc/saip_contact.h", "csrc/saip_contact_patch.h", "csrc/saip_clearance.h", "csrc/saip_link_contact.h", "csrc/saip_env_schedule.h", "csrc/saip_plant.h", "csrc/saip_plant_chain.h", "csrc/saip_inertia.h", "csrc/saip_sense.h", "csrc/saip_sense_chain.h", "csrc/saip_guard.h", "csrc/saip_law.h", "csrc/saip_wg_linalg.h", "csrc/saip_wg_cycle.h", "csrc/saip_fk.h", "csrc/saip_oct_common.h", "csrc/saip_oct_joint_tails.h", "csrc/saip_oct_slow_tail.h", "csrc/saip_wave_prims.h", "csrc/saip_dynamics_oct_body.h", "csrc/saip_otg3.h", "csrc/saip_otg3_step1.h", "csrc/saip_otg3_step2.h", "csrc/saip_rbd.h", "../include/saip.h"]
 
 SAIP_OK, SAIP_ERR_INVALID_ARGUMENT, SAIP_ERR_UNSUPPORTED, SAIP_ERR_NO_DEVICE, SAIP_ERR_DEVICE, SAIP_ERR_ORDER = range(6)
 SAIP_MAX_QUERY_FRAMES = 8

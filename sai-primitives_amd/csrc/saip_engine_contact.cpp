@@ -141,8 +141,8 @@ saip_status saip::eng::contact_launch(saip_batch* b, int mode, double dt) {
 	P.dq = b->dq;
 	P.planes = C.planes;
 	P.goal = b->tasks[C.task].goal_dev;
-	P.tau_cmd = contact_tau_cmd(b);  // (read by APPLY only, which follows the plant and link-contact launches)
-	P.tau_sim = C.tau_sim;
+	P.tau_cmd = tau_buffer(b, sim_plan(b).contact_in);  // (read by APPLY only, which follows the plant and link-contact launches)
+	P.tau_sim = tau_buffer(b, saip::TauBuf::Planes);
 	P.readout = C.readout;
 	P.summary = C.summary;
 	// planes with an environment schedule move: the MOVING instantiation reads the velocities the schedule writes
@@ -305,8 +305,8 @@ saip_status saip::eng::patch_launch(saip_batch* b, int mode, double dt) {
 	P.tasks = b->tasks_dev;
 	P.q = b->q;
 	P.dq = b->dq;
-	P.tau_cmd = contact_tau_cmd(b);  // (read by APPLY only, which follows the plant and link-contact launches)
-	P.tau_sim = b->patch_tau_sim;
+	P.tau_cmd = tau_buffer(b, sim_plan(b).contact_in);  // (read by APPLY only, which follows the plant and link-contact launches)
+	P.tau_sim = tau_buffer(b, saip::TauBuf::Patches);
 	for (int i = 0; i < b->n_patch; i++) {
 		const auto& C = b->patch[i];
 		saip::PatchDev& D = P.patch[i];

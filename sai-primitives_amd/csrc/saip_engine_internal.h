@@ -16,6 +16,7 @@
 #include "../../include/saip.h"
 #include "saip_device.h"
 #include "saip_cycle_plan.h"
+#include "saip_period_plan.h"
 #include "saip_state_snapshot.h"
 #include "saip_sampler.h"
 #include "saip_contact.h"
@@ -438,8 +439,6 @@ bool clearance_check_obstacles(const double* obst, int O, size_t cols, char* msg
 // ---- saip_engine_link_contact.cpp
 void link_contact_free(saip_batch* b);
 saip_status link_contact_launch(saip_batch* b, int mode, double dt);
-// the torques the contact planes or patches build on: link contact's, else the plant's, else the commanded ones
-inline const double* contact_tau_cmd(const saip_batch* b) { return b->link_contact.attached ? b->link_contact.tau_sim : b->plant.attached ? b->plant.tau_act : commanded_tau(b); }
 // ---- saip_engine_chain.cpp: the host side of a chain (saip_batch::Chain), written once.  What differs between the two is a ChainKind;
 // the extern "C" entries stay with the carriers (saip_engine_sensing.cpp, saip_engine_plant.cpp), which pick the struct and the kind
 struct ChainKind {
@@ -483,6 +482,8 @@ void guard_free(saip_batch* b);
 saip_status guard_launch(saip_batch* b);
 void guard_segments(const saip_batch* b, saip::GuardParams* P);  // where the state arrays live (the snapshot directory)
 // ---- saip_engine_rollout.cpp
+saip::SimPlan sim_plan(const saip_batch* b);                // plan_sim of the batch's attach flags, as they are now
+double* tau_buffer(const saip_batch* b, saip::TauBuf which);  // the one place that knows which array a name of the torque chain is
 void record_free(saip_batch* b);
 void schedule_release(saip_batch* b, int task);
 inline double sched_max_abs(const double* a, int n) {

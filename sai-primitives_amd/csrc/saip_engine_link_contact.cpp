@@ -167,8 +167,8 @@ saip_status saip::eng::link_contact_launch(saip_batch* b, int mode, double dt) {
 	P.dq = b->dq;
 	P.obst = C.obst;
 	P.mat = C.mat;
-	P.tau_cmd = b->plant.attached ? b->plant.tau_act : commanded_tau(b);  // (read by APPLY only, which follows the plant launch)
-	P.tau_sim = C.tau_sim;
+	P.tau_cmd = tau_buffer(b, sim_plan(b).link_contact_in);  // (read by APPLY only, which follows the plant launch)
+	P.tau_sim = tau_buffer(b, saip::TauBuf::LinkContact);
 	P.readout = C.readout;
 	P.summary = C.summary;
 	P.keep = C.keep_dev;

@@ -270,7 +270,7 @@ saip_status saip::eng::plant_launch(saip_batch* b, double dt, int substep) {
 	P.tau_cmd = commanded_tau(b);
 	P.joints = C.joints;
 	P.wrenches = C.wrenches;
-	P.tau_act = C.tau_act;
+	P.tau_act = tau_buffer(b, saip::TauBuf::Plant);
 	P.summary = C.summary;
 	for (int k = 0; k < C.n_wrenches; k++) P.site[k] = C.site[k];
 	hipError_t e;

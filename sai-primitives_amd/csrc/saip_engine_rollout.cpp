@@ -1,7 +1,41 @@
 #include "saip_engine_internal.h"
 
+// ---- the period plan (saip_period_plan.h): the facts of a batch, and the buffer behind each name of the torque chain
+saip::SimPlan saip::eng::sim_plan(const saip_batch* b) {
+	saip::SimFacts F;
+	F.planes = b->contact.attached;
+	F.patches = b->n_patch > 0;
+	F.plant = b->plant.attached;
+	F.link_contact = b->link_contact.attached;
+	F.inertia = b->inertia.attached;
+	F.sensing = b->sensing.attached;
+	F.goals_written = b->n_sched > 0 || b->guard.attached;
+	for (const auto& T : b->tasks) F.any_otg = F.any_otg || T.otg_enabled;
+	F.tree = b->model->dev.is_tree != 0;
+	F.n = b->model->n;
+	return saip::plan_sim(F);
+}
+double* saip::eng::tau_buffer(const saip_batch* b, saip::TauBuf which) {
+	switch (which) {
+		case saip::TauBuf::Plant: return b->plant.tau_act;
+		case saip::TauBuf::LinkContact: return b->link_contact.tau_sim;
+		case saip::TauBuf::Planes: return b->contact.tau_sim;
+		case saip::TauBuf::Patches: return b->patch_tau_sim;
+		default: return commanded_tau(b);
+	}
+}
+// the state moved: like after robot->setQ(), updateControllerTaskModels() is due; the integration closed one period of the plant's wrench
+// windows and of the sensing model's noise counter
+static void state_moved(saip_batch* b) {
+	if (b->plant.attached) b->plant.period++;
+	if (b->sensing.attached) b->sensing.period++;
+	b->models_valid = false;
+	b->state_epoch++;
+}
+
 // ---- the step after the path: forward dynamics + semi-implicit Euler on the resident state (saip_dynamics.hip)
-static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, const double* gravity, double damping, bool with_next_otg = false) {
+// fuse_next_otg: the caller's half of SimPlan::may_fuse_next_otg (another period follows); otg_pair_ready has the last word
+static saip_status enqueue_integrate(saip_batch* b, const saip::SimPlan& plan, double dt, int substeps, const double* gravity, double damping, bool fuse_next_otg = false) {
 	SimParams S;
 	S.B = b->B;
 	S.ld = b->ld;
@@ -13,40 +47,27 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 	S.model = b->model_dev;
 	S.q = b->q;
 	S.dq = b->dq;
-	S.tau = commanded_tau(b);
+	S.tau = tau_buffer(b, plan.integrator_in);
 	S.ddq = nullptr;
 	// the inertia table of the simulated robot, on every path below but the fused one (which is not taken while it is attached)
 	S.inertia = b->inertia.attached ? b->inertia.rows : nullptr;
 	S.inertia_stride = b->inertia.attached && b->inertia.per_instance ? b->ld : 1;
-	hipError_t e;
+	hipError_t e = hipSuccess;
 	const bool tree = b->model->dev.is_tree != 0;  // trees: the lane-per-instance tree kernel, whatever the dof (the eight-lane step is chain-only)
-	if (b->contact.attached || b->n_patch > 0 || b->plant.attached || b->link_contact.attached) {
-		// contact planes: the penalty force is re-evaluated in front of every substep (held over a control period it is unstable at
-		// useful stiffness), and the integrator takes commanded + contact torques; never fused with the next period's OTG step.
-		// Contact patches take the same place with their own kernel.  A plant model stands in front of either: it turns the commanded
-		// torques into actuated ones, which the contact launch (when there is one) takes in place of the commanded torques; the
-		// integrator reads the last buffer written.  The whole call belongs to one period of the plant.  Link contact stands between the
-		// two: it adds the obstacles' push on the link spheres to the plant's (or the commanded) torques, and the contact launch builds on
-		// its buffer (contact_tau_cmd).
-		const bool patches = b->n_patch > 0, contact = patches || b->contact.attached, links = b->link_contact.attached;
+	if (plan.per_substep) {
+		// every substep: the attached stages in the order of the torque chain, each at the state of that substep, then one step of the
+		// integrator on the last buffer written.  The whole call belongs to one period of the plant.
 		S.substeps = 1;
-		S.tau = patches ? b->patch_tau_sim : contact ? b->contact.tau_sim : links ? b->link_contact.tau_sim : b->plant.tau_act;
-		for (int s = 0; s < substeps; s++) {
+		for (int s = 0; s < substeps && e == hipSuccess; s++) {
 			saip_status st = b->plant.attached ? plant_launch(b, dt, s) : SAIP_OK;  // s == 0: the actuation chain advances its delay line
 			if (st) return st;
-			if (links && (st = link_contact_launch(b, saip::LINK_CONTACT_APPLY, dt))) return st;
-			if (contact) st = patches ? patch_launch(b, saip::CONTACT_APPLY, dt) : contact_launch(b, saip::CONTACT_APPLY, dt);
+			if (b->link_contact.attached && (st = link_contact_launch(b, saip::LINK_CONTACT_APPLY, dt))) return st;
+			if (b->n_patch > 0) st = patch_launch(b, saip::CONTACT_APPLY, dt);
+			else if (b->contact.attached) st = contact_launch(b, saip::CONTACT_APPLY, dt);
 			if (st) return st;
 			e = saip::launch_integrate(S, tree, b->stream);
-			if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "integrate launch failed: %s", hipGetErrorString(e));
 		}
-		if (b->plant.attached) b->plant.period++;
-		if (b->sensing.attached) b->sensing.period++;
-		b->models_valid = false;
-		b->state_epoch++;
-		return SAIP_OK;
-	}
-	if (with_next_otg && S.n == 7 && !tree && !b->inertia.attached && !b->sensing.attached && otg_pair_ready(b)) {
+	} else if (fuse_next_otg && otg_pair_ready(b)) {
 		// rollouts: this integration and the NEXT period's trajectory generation in one launch (they are independent)
 		e = saip::launch_integrate_otg_pair(S, b->tasks[0].otg, b->tasks[1].otg, b->B, b->ld, b->stream);
 		b->otg_prelaunched = true;
@@ -54,16 +75,14 @@ static saip_status enqueue_integrate(saip_batch* b, double dt, int substeps, con
 		e = saip::launch_integrate(S, tree, b->stream);
 	}
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "integrate launch failed: %s", hipGetErrorString(e));
-	if (b->sensing.attached) b->sensing.period++;
-	b->models_valid = false;  // the state moved: like after robot->setQ(), updateControllerTaskModels() is due
-	b->state_epoch++;
+	state_moved(b);
 	return SAIP_OK;
 }
 extern "C" saip_status saip_batch_integrate(saip_batch* b, double dt, int substeps, const double* gravity, double damping) {
 	saip_status st = need_ready(b, "saip_batch_integrate");
 	if (st) return st;
 	if (!(dt > 0) || substeps < 1 || damping < 0) return fail(SAIP_ERR_INVALID_ARGUMENT, "saip_batch_integrate: dt > 0, substeps >= 1, damping >= 0 required");
-	return enqueue_integrate(b, dt, substeps, gravity, damping);
+	return enqueue_integrate(b, sim_plan(b), dt, substeps, gravity, damping);
 }
 // ---- rollout recorder (saip_rollout_record.hip): per-period trajectory log and running summaries of saip_batch_rollout_async
 static int record_rows(unsigned channels, int n) {
@@ -383,26 +402,14 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 	saip_status st = need_ready(b, "saip_batch_rollout_async");
 	if (st) return st;
 	if (steps < 1 || !(sim_dt > 0) || substeps < 1 || damping < 0) return fail(SAIP_ERR_INVALID_ARGUMENT, "saip_batch_rollout_async: bad arguments");
-	bool any_otg = false;
-	for (auto& T : b->tasks) any_otg = any_otg || T.otg_enabled;
 	SimRequest sim = {substeps, sim_dt, damping, {0, 0, 0}};
 	for (int i = 0; i < 3; i++) sim.gravity[i] = gravity ? gravity[i] : b->model->dev.gravity[i];
-	// with a goal schedule attached every period starts with the launch that writes its goals, and the integration is never fused with
-	// the next period's OTG step (which would read the next goal before it is written)
-	// guards attached: the same for the integration, since the guard may rewrite the goal the next period's OTG step has to read
-	const bool scheduled = b->n_sched > 0, goals_written = scheduled || b->guard.attached;
-	// with contact planes attached neither fused form is used: the contact force sits between the cycle and every integration substep
-	// (contact patches: the same, with their kernel)
-	// a plant model does the same: it sits between the cycle and every integration substep
-	// an inertia table rules out both fused forms as well: they integrate with the model's inertial parameters
-	// a sensing model too: the fused cycle would compute from the measured copy and integrate it, and the next period's OTG step would
-	// run ahead of the measurement it belongs behind
-	// link contact as well: like the contact planes it sits in front of every integration substep
-	const bool contact = b->contact.attached || b->n_patch > 0 || b->plant.attached || b->inertia.attached || b->sensing.attached || b->link_contact.attached;
+	const saip::SimPlan plan = sim_plan(b);  // once per call: nothing attaches or detaches between its periods
 	const bool patch_sensor = patch_any_sensor(b);
 	const int sense_slots = b->sensing.attached ? sensing_sensor_slots(b, true, true) : 0;
 	auto period = [&](const bool more = false) -> saip_status {  // more: another period follows inside this call
-		if (scheduled && (st = apply_schedules(b))) return st;
+		// goal schedules: every period starts with the launch that writes its goals
+		if (b->n_sched > 0 && (st = apply_schedules(b))) return st;
 		// environment schedules: this period's planes (held through its substeps) and the obstacles at the time of the state the monitor will
 		// look at; the launch reads no state, so the fused forms below stay in use
 		if (b->n_env > 0 && (st = env_apply(b, sim_dt * substeps))) return st;
@@ -418,15 +425,14 @@ extern "C" saip_status saip_batch_rollout_async(saip_batch* b, int steps, double
 		if (b->guard.attached && (st = guard_launch(b))) return st;
 		// no internal OTG in the stack: the cycle launch integrates the state itself when it can (eight-lane kernel, no slow path behind)
 		bool integrated = false;
-		saip_status s2 = launch_cycle(b, false, (!any_otg && b->model->n == 7 && !contact) ? &sim : nullptr, &integrated);
+		saip_status s2 = launch_cycle(b, false, plan.offer_cycle_sim ? &sim : nullptr, &integrated);
 		if (s2) {
 			b->otg_prelaunched = false;  // a failed period must not leave the next standalone cycle believing its OTG step has already run
 			return s2;
 		}
-		if (integrated) {  // the bookkeeping of enqueue_integrate
-			b->models_valid = false;
-			b->state_epoch++;
-		} else if ((s2 = enqueue_integrate(b, sim_dt, substeps, gravity, damping, more && !goals_written))) {
+		if (integrated) {
+			state_moved(b);  // (no plant and no sensing model on this branch: the plan offers it with neither attached, so their counters stay)
+		} else if ((s2 = enqueue_integrate(b, plan, sim_dt, substeps, gravity, damping, more && plan.may_fuse_next_otg))) {
 			b->otg_prelaunched = false;
 			return s2;
 		}

@@ -25,6 +25,7 @@ import trees as TR
 import workloads as W
 from test_gpu_batch_layout import _DevBuf, _d2h, _h2d, _same_bits
 from test_gpu_clearance import _chain30w, _query_centres, _spheres
+from test_gpu_guard import GUARDS, PHASES
 from test_gpu_rollout_record import _panda
 
 pytestmark = pytest.mark.gpu
@@ -648,6 +649,76 @@ def test_rollout_equals_the_host_driven_loop(sp, otg, B, ld):
     ctrl.rolloutAsync(K, DT, SUB, gravity=GRAV)
     touched = a["summary"][:, 3] > 0
     assert not _same_bits(ctrl.pullState()[0][touched], a["q"][touched])
+
+
+def _stacked(B, ld, otg, K):
+    """every stage of a period at once on the moving Panda in contact: a plant, link contact, contact planes with the simulated sensor under
+    the tool (every instance starts 2 mm inside), a sensing model with a joint table and a wrench table, the guards of
+    tests/test_gpu_guard.py on the sensed force, and the recorder"""
+    robot, ctrl, objs, mf, m, sph, ob, mat = _panda_in_contact(B, ld, otg)
+    table = PL.neutral(7)
+    table[:, PL.GAIN], table[:, PL.TAU_MAX], table[:, PL.FV] = 0.9, 15.0, 0.5
+    ctrl.attachPlant(table)
+    planes = np.zeros((1, B, 8))
+    planes[0] = [0, 0, 1, 0, 2.0e4, 400.0, 0.3, 1e-3]
+    planes[0, :, 3] = robot.position("end-effector", (0, 0, 0.07))[:, 2] + 2e-3
+    mf.attachContactPlanes(planes, sensor=True, per_instance=True)
+    mf.attachGuards(GUARDS, PHASES)
+    ctrl.recordRollouts(K, 1, ("q", "dq", "tau"), task=mf)
+    joints = np.zeros((7, 6))
+    joints[:, 0], joints[:, 1], joints[:, 2], joints[:, 5] = 0.01, 2 * np.pi / 2 ** 14, 1e-3, 1e-3       # offset, resolution, noise on q and dq
+    wrench = np.zeros((6, 3))
+    wrench[:, 0], wrench[:3, 1], wrench[:, 2] = 0.2, 0.25, 0.05
+    ctrl.attachSensing(joints, wrenches={mf: wrench}, seed=5)
+    return robot, ctrl, objs, mf, _Outputs(ctrl, len(sph), 7, ld, False)
+
+
+def _stacked_final(ctrl, objs, mf, out, ld):
+    """_final, and what every other attachment of _stacked has to show"""
+    B = ctrl.batch_size
+    a = _final(ctrl, objs, out)
+    a["plant_act"] = _d2h(ctrl.plantTorquesDevice(), (7, ld))[:, :B].T
+    a["planes_sim"] = _d2h(mf.contactTorquesDevice(), (7, ld))[:, :B].T
+    a["q_meas"], a["dq_meas"] = ctrl.measuredState()
+    for name, d in (("plant", ctrl.plantSummary()), ("planes", mf.contactReadout()), ("planes_sum", mf.contactSummary()), ("guard", ctrl.guardState()),
+                    ("guard_ro", ctrl.guardReadout())):
+        a.update({f"{name}.{k}": v for k, v in d.items()})
+    a["periods"] = [ctrl.plantInfo()["period"], ctrl.sensingInfo()["period"]]
+    return a
+
+
+@pytest.mark.parametrize("B,ld", [(65, 128), (3, 64)])
+@pytest.mark.parametrize("otg", [False, True])
+def test_stacked_rollout_equals_the_host_driven_loop(sp, otg, B, ld):
+    """plant + link contact + contact planes with the sensor + sensing model + guards + recorder: K periods in one rolloutAsync against the
+    host-driven loop { contactSense, measureState, evaluateGuards, stepAsync, integrate }, bit for bit in the state, the torques, the goals,
+    every attachment's buffer, readout and summary, the guard state and the two period counters.  The recorder acts inside rollouts only:
+    its log is compared with what the host loop pulls after every integrate."""
+    K = 6
+    robot, ctrl, objs, mf, out = _stacked(B, ld, otg, K)
+    ctrl.rolloutAsync(K, DT, SUB, gravity=GRAV)
+    roll, log = _stacked_final(ctrl, objs, mf, out, ld), ctrl.rolloutLog()
+    robot, ctrl, objs, mf, out = _stacked(B, ld, otg, K)
+    pulled = dict(q=[], dq=[], tau=[], status=[])
+    for _ in range(K):
+        ctrl.contactSense()
+        ctrl.measureState()
+        ctrl.evaluateGuards()
+        ctrl.stepAsync()
+        ctrl.integrate(DT, SUB, gravity=GRAV)
+        ctrl.synchronize()
+        for key, val in zip(("q", "dq", "tau", "status"), (*ctrl.pullState(), ctrl.getTorques(), ctrl.status)):
+            pulled[key].append(np.array(val, float))
+    _equal_runs(roll, _stacked_final(ctrl, objs, mf, out, ld))
+    assert np.array_equal(log["period"], np.arange(1, K + 1))
+    for key in pulled:
+        assert _same(log[key], np.stack(pulled[key])), key
+    # conditions, so that nothing above holds vacuously: every stage acted
+    assert roll["periods"] == [K, K] and np.isfinite(roll["q"]).all()
+    assert (roll["summary"][:, 3] > 0).any() and (roll["plant.friction_loss"] > 0).all() and (roll["planes_sum.max_force"] > 1.0).any()
+    assert (roll["guard.entry"][1] >= 0).any() and (roll["guard.clock"] == K).all()
+    assert not _same(roll["q_meas"], roll["q"]) and np.abs(roll["goals"][0][:, 30:33]).max() > 1.0
+    assert not _same(roll["plant_act"], roll["sim"]) and not _same(roll["sim"], roll["planes_sim"])
 
 
 @pytest.mark.parametrize("B,ld", [(65, 128)])
