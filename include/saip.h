@@ -587,6 +587,55 @@ saip_status saip_batch_link_contact_summary_reset(saip_batch*);
 saip_status saip_batch_link_contact_add_cost(saip_batch*, double w_impulse, double w_peak);
 double* saip_batch_link_contact_torques_device(saip_batch*);    /* [dof][ld] tau_sim of the last APPLY launch; NULL when detached */
 double* saip_batch_link_contact_keep_device(saip_batch*);       /* [9 S][ld]; NULL unless keep */
+/* ---- link object: a free rigid body that the robot's link spheres push, the optional second stage of link contact ("push the part to the
+ * target" inside a rollout).  At most one per batch; it needs link contact and is detached with it.  The launch with the object replaces
+ * the link-contact launch: the launch count of a substep does not change.
+ *   state     [13][ld] per instance: p[3] of the body origin (world = the robot's base frame), unit quaternion (w, x, y, z) body to world,
+ *             v[3], omega[3] (world frame).  State in the sense of the snapshots: segment link_object.state while attached.  _attach leaves
+ *             the body frame on the world frame, at rest; _set_state_host takes [13] (per_instance 0: every instance) or [13][B] and
+ *             normalises the quaternion.
+ *   inertial  { m, Ix, Iy, Iz } (principal moments in body axes), [4] or [4][B] (per_instance), all > 0 and finite.
+ *   shape     n_spheres (1..SAIP_LINK_OBJECT_MAX_SPHERES) of { centre[3] in the body frame, radius >= 0 }, batch-uniform; material[4] =
+ *             { k, c, mu, v_s } of robot-object contact, under the rules of a link-contact material row.
+ * Every APPLY substep (saip_batch_integrate, every rollout substep), at the state of that substep: object sphere p has c_p = p + R r_p,
+ * v_p = v + omega x (c_p - p).  Robot sphere s against object sphere p is the link-contact item against the sphere obstacle (c_p, radius_p)
+ * with the object's material and the velocity v_s - v_p: f acts on the robot sphere (F_s sums the world obstacles first, then p = 0..P-1),
+ * -f on the object at c_p.  Object sphere p meets every link-contact obstacle with that obstacle's material.  The body integrates
+ * m g + the world items + the reactions with semi-implicit Euler (csrc/saip_link_object.h has the order of every operation;
+ * tests/link_object_ref.py restates it in NumPy bit for bit).  The link-contact readout and summaries keep speaking of the world obstacles
+ * alone; the robot's torque loop runs when a world item or an object item is active.  _evaluate never advances the object.
+ *   readout [12][ld] of the LAST launch: 0..2 net force of the robot on the object; 3..5 its moment about p; 6..8 net force of the world on
+ *        the object; 9 the smallest robot-object distance; 10 its item s P + p (s the caller's robot sphere; lowest among equals); 11 active
+ *        robot-object items.  An instance with a robot sphere centre or an object state word that is not finite is invalid: every row NaN,
+ *        tau_sim = u0, the state is not written.
+ *   summaries [4][ld], advanced once per substep: sum dt sum f_n over the robot-object items (NaN is sticky); the largest robot-object
+ *        penetration; the largest object-world penetration; substeps with an active robot-object item.
+ *   saip_batch_link_object_add_cost: cost[i] += w_pos |p - target_p|^2 + w_ori (1 - (q . q_t)^2) (the second term only with a target
+ *        quaternion, normalised here); a state that is not finite costs +inf.
+ * SAIP_ERR_INVALID_ARGUMENT (the message names the sphere, the word and the instance): a centre or radius that is not finite, a radius below
+ * 0, a material word against the rules, an inertial word that is not > 0 and finite, a zero or non-finite quaternion, 0 spheres or more than
+ * the maximum, a null table, a NaN weight, a target that is not finite.  SAIP_ERR_ORDER: before finalize, a model-only batch, _attach without
+ * link contact or twice, any other entry without an attachment, _add_cost without a sampler.  Argument and order errors are reported before
+ * the device is needed, and nothing is written on refusal. */
+#define SAIP_LINK_OBJECT_MAX_SPHERES 8
+#define SAIP_LINK_OBJECT_STATE_ROWS 13
+#define SAIP_LINK_OBJECT_INERTIAL_WORDS 4
+#define SAIP_LINK_OBJECT_READOUT_ROWS 12
+#define SAIP_LINK_OBJECT_SUMMARY_ROWS 4
+saip_status saip_batch_link_object_attach(saip_batch*, int n_spheres, const double* centres /* [P][3] */, const double* radii, const double* material /* [4] */,
+                                          const double* inertial /* [4] or [4][B] */, int per_instance);
+saip_status saip_batch_link_object_detach(saip_batch*);
+saip_status saip_batch_link_object_info(saip_batch*, int* n_spheres, int* per_instance);  /* any NULL */
+saip_status saip_batch_link_object_set_state_host(saip_batch*, const double* state /* [13] or [13][B] */, int per_instance);
+saip_status saip_batch_link_object_state_host(saip_batch*, double* out /* [13][B] */);  /* synchronous */
+double* saip_batch_link_object_state_device(saip_batch*);      /* [13][ld]; NULL when detached */
+saip_status saip_batch_link_object_set_inertial_host(saip_batch*, const double* inertial);
+saip_status saip_batch_link_object_readout_host(saip_batch*, double* out /* [12][B] */);  /* synchronous */
+double* saip_batch_link_object_readout_device(saip_batch*);    /* [12][ld]; NULL when detached */
+saip_status saip_batch_link_object_summary_host(saip_batch*, double* out /* [4][B] */);  /* synchronous */
+double* saip_batch_link_object_summary_device(saip_batch*);    /* [4][ld]; NULL when detached */
+saip_status saip_batch_link_object_summary_reset(saip_batch*);
+saip_status saip_batch_link_object_add_cost(saip_batch*, const double* target_p /* [3] */, double w_pos, const double* target_quat /* [4] or NULL */, double w_ori);
 /* ---- environment schedules: moving obstacles and contact surfaces inside rollouts.  What goal schedules are to the goals: the obstacle
  * table of the clearance monitor, the single-point contact planes and the planes of a contact patch become functions of the rollout
  * period, written from keyframes resident on the device by ONE launch at the head of every period of saip_batch_rollout_async.  At most

@@ -1424,6 +1424,61 @@ public:
 	double* linkContactKeepDevice() { return saip_batch_link_contact_keep_device(_batch); }        // [9 S][ld]; nullptr unless keep
 	// cost += w_impulse * summary impulse + w_peak * summary peak force, after rolloutCost()
 	void linkContactCost(double w_impulse, double w_peak = 0.0) { check(saip_batch_link_contact_add_cost(_batch, w_impulse, w_peak)); }
+	// ---- link object: a free rigid body the robot's link spheres push, the second stage of link contact (saip.h).  While attached every
+	// integration substep lets the robot and the link-contact obstacles push the body and integrates it; its state is part of a snapshot.
+	struct ObjectSphere {
+		double centre[3];  // in the body frame
+		double radius;
+	};
+	struct LinkObjectInfo {
+		int n_spheres = 0, per_instance = 0;
+	};
+	// material: [4] { k, c, mu, v_s }; inertial: [4] { m, Ix, Iy, Iz }, or [4][B] with per_instance
+	void attachLinkObject(const std::vector<ObjectSphere>& spheres, const std::vector<double>& material, const std::vector<double>& inertial, bool per_instance = false) {
+		if (material.size() != SAIP_LINK_CONTACT_MATERIAL_WORDS) throw std::invalid_argument("attachLinkObject: expected a [4] material");
+		if (inertial.size() != (size_t)SAIP_LINK_OBJECT_INERTIAL_WORDS * (per_instance ? (size_t)_robot->batchSize() : 1))
+			throw std::invalid_argument("attachLinkObject: expected [4] inertial words, or [4][B] per instance");
+		std::vector<double> centres, radii;
+		for (const auto& s : spheres) {
+			centres.insert(centres.end(), s.centre, s.centre + 3);
+			radii.push_back(s.radius);
+		}
+		check(saip_batch_link_object_attach(_batch, (int)spheres.size(), centres.data(), radii.data(), material.data(), inertial.data(), per_instance ? 1 : 0));
+	}
+	void detachLinkObject() { check(saip_batch_link_object_detach(_batch)); }
+	LinkObjectInfo linkObjectInfo() {
+		LinkObjectInfo i;
+		check(saip_batch_link_object_info(_batch, &i.n_spheres, &i.per_instance));
+		return i;
+	}
+	// [13] for every instance, or [13][B]: p, quaternion (w, x, y, z) body to world (normalised by the engine), v, omega (world frame)
+	void setObjectState(const std::vector<double>& state) {
+		const size_t R = SAIP_LINK_OBJECT_STATE_ROWS;
+		if (state.size() != R && state.size() != R * (size_t)_robot->batchSize()) throw std::invalid_argument("setObjectState: expected a [13] or [13][B] state");
+		check(saip_batch_link_object_set_state_host(_batch, state.data(), state.size() == R ? 0 : 1));
+	}
+	std::vector<double> objectState() {  // [13][B]
+		std::vector<double> out((size_t)SAIP_LINK_OBJECT_STATE_ROWS * _robot->batchSize());
+		check(saip_batch_link_object_state_host(_batch, out.data()));
+		return out;
+	}
+	std::vector<double> objectReadout() {  // [12][B]: robot-on-object force 3, moment 3, world force 3, distance, item, active items
+		std::vector<double> out((size_t)SAIP_LINK_OBJECT_READOUT_ROWS * _robot->batchSize());
+		check(saip_batch_link_object_readout_host(_batch, out.data()));
+		return out;
+	}
+	std::vector<double> objectSummary() {  // [4][B]: impulse, largest robot-object penetration, largest object-world penetration, substeps in contact
+		std::vector<double> out((size_t)SAIP_LINK_OBJECT_SUMMARY_ROWS * _robot->batchSize());
+		check(saip_batch_link_object_summary_host(_batch, out.data()));
+		return out;
+	}
+	void resetObjectSummary() { check(saip_batch_link_object_summary_reset(_batch)); }
+	double* objectStateDevice() { return saip_batch_link_object_state_device(_batch); }  // [13][ld]; nullptr when detached
+	// cost += w_pos |p - target_p|^2 + w_ori (1 - (q . target_quat)^2), after rolloutCost(); target_quat empty: the position term alone
+	void objectCost(const std::array<double, 3>& target_p, double w_pos, const std::vector<double>& target_quat = {}, double w_ori = 0.0) {
+		if (!target_quat.empty() && target_quat.size() != 4) throw std::invalid_argument("objectCost: expected a [4] target quaternion, or none");
+		check(saip_batch_link_object_add_cost(_batch, target_p.data(), w_pos, target_quat.empty() ? nullptr : target_quat.data(), w_ori));
+	}
 	// ---- guards: event-triggered phases inside rollouts (task->attachGuards; saip.h).  rolloutAsync() evaluates them in every period in
 	// front of the OTG step and the cycle; evaluateGuards() does the same for a host-driven loop { contactSense, evaluateGuards, stepAsync,
 	// integrate }.

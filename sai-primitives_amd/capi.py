@@ -8,7 +8,7 @@ import subprocess
 _DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_DIR, "libsaip.so")
 SOURCES = ["csrc/saip_engine.cpp", "csrc/saip_engine_model.cpp", "csrc/saip_engine_contact.cpp", "csrc/saip_engine_clearance.cpp", "csrc/saip_engine_link_contact.cpp", "csrc/saip_engine_env.cpp", "csrc/saip_engine_chain.cpp", "csrc/saip_engine_plant.cpp", "csrc/saip_engine_inertia.cpp", "csrc/saip_engine_sensing.cpp", "csrc/saip_engine_guard.cpp", "csrc/saip_engine_rollout.cpp", "csrc/saip_engine_snapshot.cpp", "csrc/saip_engine_sampler.cpp", "csrc/saip_engine_query.cpp", "csrc/saip_comm.cpp", "csrc/saip_kernel_wg.hip", "csrc/saip_kernel_lane.hip", "csrc/saip_kernel_lane_lean.hip", "csrc/saip_kernel_oct.hip", "csrc/saip_kernel_octjf.hip", "csrc/saip_kernel_wave.hip", "csrc/saip_otg.hip", "csrc/saip_dynamics.hip", "csrc/saip_dynamics_oct.hip", "csrc/saip_task_diag.hip", "csrc/saip_model_query.hip", "csrc/saip_rollout_record.hip", "csrc/saip_goal_schedule.hip", "csrc/saip_state_snapshot.hip", "csrc/saip_sampler.hip", "csrc/saip_contact.hip", "csrc/saip_contact_patch.hip", "csrc/saip_clearance.hip", "csrc/saip_link_contact.hip", "csrc/saip_env_schedule.hip", "csrc/saip_plant.hip", "csrc/saip_inertia.hip", "csrc/saip_sense.hip", "csrc/saip_sense_chain.hip", "csrc/saip_guard.hip"]
-HEADERS = ["csrc/saip_device.h", "csrc/saip_cycle_plan.h", "csrc/saip_period_plan.h", "csrc/saip_engine_internal.h", "csrc/saip_state_snapshot.h", "csrc/saip_sampler.h", "csrc/saip_contact.h", "csrc/saip_contact_patch.h", "csrc/saip_clearance.h", "csrc/saip_link_contact.h", "csrc/saip_env_schedule.h", "csrc/saip_plant.h", "csrc/saip_plant_chain.h", "csrc/saip_inertia.h", "csrc/saip_sense.h", "csrc/saip_sense_chain.h", "csrc/saip_guard.h", "csrc/saip_law.h", "csrc/saip_wg_linalg.h", "csrc/saip_wg_cycle.h", "csrc/saip_fk.h", "csrc/saip_oct_common.h", "csrc/saip_oct_joint_tails.h", "csrc/saip_oct_slow_tail.h", "csrc/saip_wave_prims.h", "csrc/saip_dynamics_oct_body.h", "csrc/saip_otg3.h", "csrc/saip_otg3_step1.h", "csrc/saip_otg3_step2.h", "csrc/saip_rbd.h", "../include/saip.h"]
+HEADERS = ["csrc/saip_device.h", "csrc/saip_cycle_plan.h", "csrc/saip_period_plan.h", "csrc/saip_engine_internal.h", "csrc/saip_state_snapshot.h", "csrc/saip_sampler.h", "csrc/saip_contact.h", "csrc/saip_contact_patch.h", "csrc/saip_clearance.h", "csrc/saip_link_contact.h", "csrc/saip_link_object.h", "csrc/saip_env_schedule.h", "csrc/saip_plant.h", "csrc/saip_plant_chain.h", "csrc/saip_inertia.h", "csrc/saip_sense.h", "csrc/saip_sense_chain.h", "csrc/saip_guard.h", "csrc/saip_law.h", "csrc/saip_wg_linalg.h", "csrc/saip_wg_cycle.h", "csrc/saip_fk.h", "csrc/saip_oct_common.h", "csrc/saip_oct_joint_tails.h", "csrc/saip_oct_slow_tail.h", "csrc/saip_wave_prims.h", "csrc/saip_dynamics_oct_body.h", "csrc/saip_otg3.h", "csrc/saip_otg3_step1.h", "csrc/saip_otg3_step2.h", "csrc/saip_rbd.h", "../include/saip.h"]
 
 SAIP_OK, SAIP_ERR_INVALID_ARGUMENT, SAIP_ERR_UNSUPPORTED, SAIP_ERR_NO_DEVICE, SAIP_ERR_DEVICE, SAIP_ERR_ORDER = range(6)
 SAIP_MAX_QUERY_FRAMES = 8
@@ -26,6 +26,8 @@ SAIP_CLEARANCE_OBSTACLE_WORDS, SAIP_CLEARANCE_READOUT_ROWS, SAIP_CLEARANCE_SUMMA
 SAIP_CLEARANCE_CAPSULE, SAIP_CLEARANCE_HALF_SPACE = 0, 1
 SAIP_LINK_CONTACT_MAX_SPHERES, SAIP_LINK_CONTACT_MAX_OBSTACLES, SAIP_LINK_CONTACT_OBSTACLE_WORDS = 32, 16, 8
 SAIP_LINK_CONTACT_MATERIAL_WORDS, SAIP_LINK_CONTACT_READOUT_ROWS, SAIP_LINK_CONTACT_SUMMARY_ROWS = 4, 8, 4
+SAIP_LINK_OBJECT_MAX_SPHERES, SAIP_LINK_OBJECT_STATE_ROWS, SAIP_LINK_OBJECT_INERTIAL_WORDS = 8, 13, 4
+SAIP_LINK_OBJECT_READOUT_ROWS, SAIP_LINK_OBJECT_SUMMARY_ROWS = 12, 4
 SAIP_ENV_MAX_SCHEDULES, SAIP_ENV_PLANE_WORDS = 4, 12
 SAIP_ENV_TARGET_OBSTACLES, SAIP_ENV_TARGET_PLANES, SAIP_ENV_TARGET_PATCH = 0, 1, 2
 SAIP_ENV_HOLD, SAIP_ENV_LINEAR = 0, 1
@@ -277,6 +279,19 @@ def lib():
         "saip_batch_link_contact_add_cost": (C.c_int, [vp, C.c_double, C.c_double]),
         "saip_batch_link_contact_torques_device": (vp, [vp]),
         "saip_batch_link_contact_keep_device": (vp, [vp]),
+        "saip_batch_link_object_attach": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, C.c_int]),
+        "saip_batch_link_object_detach": (C.c_int, [vp]),
+        "saip_batch_link_object_info": (C.c_int, [vp, ip, ip]),
+        "saip_batch_link_object_set_state_host": (C.c_int, [vp, dp, C.c_int]),
+        "saip_batch_link_object_state_host": (C.c_int, [vp, dp]),
+        "saip_batch_link_object_state_device": (vp, [vp]),
+        "saip_batch_link_object_set_inertial_host": (C.c_int, [vp, dp]),
+        "saip_batch_link_object_readout_host": (C.c_int, [vp, dp]),
+        "saip_batch_link_object_readout_device": (vp, [vp]),
+        "saip_batch_link_object_summary_host": (C.c_int, [vp, dp]),
+        "saip_batch_link_object_summary_device": (vp, [vp]),
+        "saip_batch_link_object_summary_reset": (C.c_int, [vp]),
+        "saip_batch_link_object_add_cost": (C.c_int, [vp, dp, C.c_double, dp, C.c_double]),
         "saip_batch_env_schedule_attach": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_int]),
         "saip_batch_env_schedule_detach": (C.c_int, [vp, C.c_int, C.c_int]),
         "saip_batch_env_schedule_rewind": (C.c_int, [vp, C.c_longlong]),

@@ -1967,6 +1967,119 @@ class RobotController:
         """cost += w_impulse * summary impulse + w_peak * summary peak force on the device, after rolloutCost()"""
         self._call("saip_batch_link_contact_add_cost", float(w_impulse), float(w_peak))
 
+    # -- link object: a free rigid body the robot's link spheres push, the second stage of link contact (saip.h)
+    def attachLinkObject(self, spheres, material, inertial, per_instance=False, state=None):
+        """attach the pushed object (needs attachLinkContact).  spheres: up to 8 of (centre in the body frame (3), radius); material: (4,)
+        { k, c, mu, v_s } of robot-object contact; inertial: (4,) { m, Ix, Iy, Iz }, or (B, 4) with per_instance; state: as setObjectState
+        takes it (default: the body frame on the world frame, at rest).  While attached every integration substep of integrate() and
+        rolloutAsync() lets the robot's spheres and the link-contact obstacles push the body and integrates it; objectState() is part of
+        saveState() / restoreState()."""
+        spheres = list(spheres)
+        centres, radii = np.zeros((len(spheres), 3)), np.zeros(len(spheres))
+        for s, sph in enumerate(spheres):
+            if len(sph) != 2:
+                raise ValueError(f"attachLinkObject: sphere {s}: (centre, radius) expected")
+            c = np.asarray(sph[0], float).reshape(-1)
+            if c.shape != (3,):
+                raise ValueError(f"attachLinkObject: sphere {s}: a centre of shape (3,) expected, got {c.shape}")
+            centres[s], radii[s] = c, float(sph[1])
+        m = np.ascontiguousarray(material, float)
+        if m.shape != (capi.SAIP_LINK_CONTACT_MATERIAL_WORDS,):
+            raise ValueError(f"attachLinkObject: a material of shape ({capi.SAIP_LINK_CONTACT_MATERIAL_WORDS},) expected, got {m.shape}")
+        inr = self._object_inertial(inertial, per_instance, "attachLinkObject")
+        x = None if state is None else self._object_state(state, "attachLinkObject")
+        self._call("saip_batch_link_object_attach", len(spheres), _dptr(centres), _dptr(radii), _dptr(m), _dptr(inr), int(bool(per_instance)))
+        if x is not None:
+            try:
+                self._call("saip_batch_link_object_set_state_host", _dptr(x[0]), x[1])
+            except Exception:
+                self._call("saip_batch_link_object_detach")
+                raise
+
+    def _object_inertial(self, inertial, per_instance, who):
+        a, W = np.asarray(inertial, float), capi.SAIP_LINK_OBJECT_INERTIAL_WORDS
+        want = (self.batch_size, W) if per_instance else (W,)
+        if a.shape != want:
+            raise ValueError(f"{who}: {'per-instance ' if per_instance else ''}inertial words of shape {want} expected, got {a.shape}")
+        return np.ascontiguousarray(a.T)
+
+    def _object_state(self, state, who):
+        a, R = np.asarray(state, float), capi.SAIP_LINK_OBJECT_STATE_ROWS
+        if a.shape == (R,):
+            return np.ascontiguousarray(a), 0
+        if a.shape == (self.batch_size, R):
+            return np.ascontiguousarray(a.T), 1
+        raise ValueError(f"{who}: a state of shape ({R},) or ({self.batch_size}, {R}) expected, got {a.shape}")
+
+    def linkObjectInfo(self):
+        """dict n_spheres, per_instance (of the inertial words)"""
+        v = [C.c_int(0) for _ in range(2)]
+        self._call("saip_batch_link_object_info", C.byref(v[0]), C.byref(v[1]))
+        return dict(n_spheres=v[0].value, per_instance=bool(v[1].value))
+
+    def detachLinkObject(self):
+        self._call("saip_batch_link_object_detach")
+
+    def setObjectState(self, state):
+        """(13,) for every instance or (B, 13): p (3), quaternion (w, x, y, z) body to world (normalised here), v (3), omega (3, world frame)"""
+        x, per = self._object_state(state, "setObjectState")
+        self._call("saip_batch_link_object_set_state_host", _dptr(x), per)
+
+    def setObjectInertial(self, inertial):
+        """replace the inertial words { m, Ix, Iy, Iz } (same shape as attached)"""
+        info = self.linkObjectInfo()
+        self._call("saip_batch_link_object_set_inertial_host", _dptr(self._object_inertial(inertial, info["per_instance"], "setObjectInertial")))
+
+    def objectState(self):
+        """(B, 13) the object's state (waits for the engine stream)"""
+        self.linkObjectInfo()
+        out = np.empty((capi.SAIP_LINK_OBJECT_STATE_ROWS, self.batch_size))
+        self._call("saip_batch_link_object_state_host", _dptr(out))
+        return np.ascontiguousarray(out.T)
+
+    def objectReadout(self):
+        """dict of the last link-contact launch: force (B, 3) and moment (B, 3) (about the body origin) of the robot on the object,
+        world_force (B, 3), distance (B,) the smallest robot-object distance, item (B,) its number s P + p (-1: invalid instance),
+        closest: per instance (robot sphere, object sphere) or None, active (B,) active robot-object items, raw (B, 12)"""
+        info = self.linkObjectInfo()
+        out = np.empty((capi.SAIP_LINK_OBJECT_READOUT_ROWS, self.batch_size))
+        self._call("saip_batch_link_object_readout_host", _dptr(out))
+        P = info["n_spheres"]
+        item = np.where(np.isnan(out[10]), -1, out[10]).astype(int)
+        closest = [None if k < 0 else (int(k) // P, int(k) % P) for k in item]
+        return dict(force=out[0:3].T.copy(), moment=out[3:6].T.copy(), world_force=out[6:9].T.copy(), distance=out[9].copy(), item=item, closest=closest,
+                    active=np.where(np.isnan(out[11]), 0, out[11]).astype(int), raw=np.ascontiguousarray(out.T))
+
+    def objectSummary(self):
+        """dict over the integrated substeps: impulse (B,) sum dt sum f_n of the robot on the object (NaN once an instance was invalid),
+        max_penetration (B,) robot-object, max_world_penetration (B,) object-world, substeps_in_contact (B,), raw (B, 4)"""
+        self.linkObjectInfo()
+        out = np.empty((capi.SAIP_LINK_OBJECT_SUMMARY_ROWS, self.batch_size))
+        self._call("saip_batch_link_object_summary_host", _dptr(out))
+        return dict(impulse=out[0].copy(), max_penetration=out[1].copy(), max_world_penetration=out[2].copy(), substeps_in_contact=out[3].astype(int),
+                    raw=np.ascontiguousarray(out.T))
+
+    def resetObjectSummary(self):
+        """summaries back to 0 (they are not part of a snapshot; the object's state is)"""
+        self._call("saip_batch_link_object_summary_reset")
+
+    def objectStateDevice(self):
+        """device pointer of the (13, ld) object state; None when detached"""
+        return capi.lib().saip_batch_link_object_state_device(self._h)
+
+    def objectCost(self, target_p, w_pos, target_quat=None, w_ori=0.0):
+        """cost += w_pos |p - target_p|^2 + w_ori (1 - (q . target_quat)^2) on the device, after rolloutCost(); an object state that is
+        not finite costs +inf"""
+        tp = np.ascontiguousarray(target_p, float).reshape(-1)
+        if tp.shape != (3,):
+            raise ValueError(f"objectCost: a target position of shape (3,) expected, got {tp.shape}")
+        tq = None
+        if target_quat is not None:
+            tq = np.ascontiguousarray(target_quat, float).reshape(-1)
+            if tq.shape != (4,):
+                raise ValueError(f"objectCost: a target quaternion of shape (4,) expected, got {tq.shape}")
+        self._call("saip_batch_link_object_add_cost", _dptr(tp), float(w_pos), None if tq is None else _dptr(tq), float(w_ori))
+
     # -- environment schedules: obstacles and contact surfaces that move inside rollouts (saip.h)
     _ENV_MODES = {"hold": capi.SAIP_ENV_HOLD, "linear": capi.SAIP_ENV_LINEAR}
 

@@ -23,6 +23,7 @@
 #include "saip_contact_patch.h"
 #include "saip_clearance.h"
 #include "saip_link_contact.h"
+#include "saip_link_object.h"
 #include "saip_env_schedule.h"
 #include "saip_plant.h"
 #include "saip_plant_chain.h"
@@ -70,6 +71,8 @@ hipError_t launch_clearance_summary_reset(int B, int ld, double* summary, hipStr
 hipError_t launch_link_contact_apply(const LinkContactParams& P, bool tree, hipStream_t stream);
 hipError_t launch_link_contact_summary_reset(int B, int ld, double* summary, hipStream_t stream);
 hipError_t launch_link_contact_add_cost(int B, int ld, const double* summary, double* cost, double w_impulse, double w_peak, hipStream_t stream);
+hipError_t launch_link_object_apply(const LinkObjectParams& Q, bool tree, hipStream_t stream);
+hipError_t launch_link_object_add_cost(int B, int ld, const double* state, double* cost, const double* tp, double w_pos, const double* tq, double w_ori, hipStream_t stream);
 hipError_t launch_plant_apply(const PlantParams& P, bool tree, hipStream_t stream);
 hipError_t launch_plant_randomize(const PlantRandomParams& P, hipStream_t stream);
 hipError_t launch_plant_chain_apply(const PlantChainParams& C, bool tree, hipStream_t stream);
@@ -259,6 +262,19 @@ struct saip_batch {
 		double* summary = nullptr;           // [4][ld]
 		double* keep_dev = nullptr;          // [9 S][ld], keep only
 	} link_contact;
+	// saip_batch_link_object_attach: the pushed object, the optional second stage of link contact (saip_link_object.h), at most one per
+	// batch; detached with link contact.  `state` is state: on the snapshot directory while attached (segment link_object.state).  The other
+	// arrays are configuration, readout and summaries, its own (freed by _detach), not part of `allocs`.
+	struct LinkObject {
+		bool attached = false;
+		int per_instance = 0;                // of the inertial words
+		saip::LinkObjectGeom geom;           // the host copy of *geom_dev (zeroed by _attach)
+		saip::LinkObjectGeom* geom_dev = nullptr;
+		double* inertial = nullptr;          // [4] (batch-uniform) or [4][ld]
+		double* state = nullptr;             // [13][ld]
+		double* readout = nullptr;           // [12][ld]
+		double* summary = nullptr;           // [4][ld]
+	} link_object;
 	// saip_batch_env_schedule_attach: time-varying obstacle and plane tables of the rollout periods (saip_env_schedule.hip), at most one per
 	// table.  Keyframes and plane velocities are the schedule's own allocations (freed by _detach, or with the attachment whose table it
 	// writes), not part of `allocs` or of a snapshot: tables are configuration.
@@ -438,7 +454,8 @@ saip_status clearance_launch(saip_batch* b, int mode, double dt);
 bool clearance_check_obstacles(const double* obst, int O, size_t cols, char* msg, size_t len);  // false: `msg` says what is wrong with which entry
 // ---- saip_engine_link_contact.cpp
 void link_contact_free(saip_batch* b);
-saip_status link_contact_launch(saip_batch* b, int mode, double dt);
+saip_status link_contact_launch(saip_batch* b, int mode, double dt, const double* gravity = nullptr);  // gravity: of the substep (the pushed object's weight)
+void link_object_free(saip_batch* b);
 // ---- saip_engine_chain.cpp: the host side of a chain (saip_batch::Chain), written once.  What differs between the two is a ChainKind;
 // the extern "C" entries stay with the carriers (saip_engine_sensing.cpp, saip_engine_plant.cpp), which pick the struct and the kind
 struct ChainKind {

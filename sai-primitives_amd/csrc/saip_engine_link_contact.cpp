@@ -8,6 +8,7 @@ static saip_status need_link_contact(const saip_batch* b, const char* fn) {
 	return SAIP_OK;
 }
 void saip::eng::link_contact_free(saip_batch* b) {
+	link_object_free(b);  // the second stage goes with the first
 	auto& C = b->link_contact;
 	for (void* p : {(void*)C.geom_dev, (void*)C.obst, (void*)C.mat, (void*)C.tau_sim, (void*)C.readout, (void*)C.summary, (void*)C.keep_dev})
 		if (p) (void)hipFree(p);
@@ -149,7 +150,7 @@ extern "C" double* saip_batch_link_contact_readout_device(saip_batch* b) { retur
 extern "C" double* saip_batch_link_contact_summary_device(saip_batch* b) { return b ? b->link_contact.summary : nullptr; }
 extern "C" double* saip_batch_link_contact_keep_device(saip_batch* b) { return b ? b->link_contact.keep_dev : nullptr; }
 // one launch of the link-contact kernel at the resident state; dt: the substep an APPLY launch stands in front of
-saip_status saip::eng::link_contact_launch(saip_batch* b, int mode, double dt) {
+saip_status saip::eng::link_contact_launch(saip_batch* b, int mode, double dt, const double* gravity) {
 	const auto& C = b->link_contact;
 	saip::LinkContactParams P;
 	memset(&P, 0, sizeof(P));
@@ -172,7 +173,24 @@ saip_status saip::eng::link_contact_launch(saip_batch* b, int mode, double dt) {
 	P.readout = C.readout;
 	P.summary = C.summary;
 	P.keep = C.keep_dev;
-	hipError_t e = saip::launch_link_contact_apply(P, b->model->dev.is_tree != 0, b->stream);
+	hipError_t e;
+	if (b->link_object.attached) {
+		// the launch with the object replaces the plain one
+		const auto& J = b->link_object;
+		saip::LinkObjectParams Q;
+		memset(&Q, 0, sizeof(Q));
+		Q.lc = P;
+		Q.geom = J.geom_dev;
+		Q.inertial = J.inertial;
+		Q.inertial_per_instance = J.per_instance;
+		for (int i = 0; i < 3; i++) Q.gravity[i] = gravity ? gravity[i] : b->model->dev.gravity[i];
+		Q.state = J.state;
+		Q.readout = J.readout;
+		Q.summary = J.summary;
+		e = saip::launch_link_object_apply(Q, b->model->dev.is_tree != 0, b->stream);
+	} else {
+		e = saip::launch_link_contact_apply(P, b->model->dev.is_tree != 0, b->stream);
+	}
 	if (e != hipSuccess) return fail(SAIP_ERR_DEVICE, "link contact launch failed: %s", hipGetErrorString(e));
 	return SAIP_OK;
 }
@@ -207,5 +225,193 @@ extern "C" saip_status saip_batch_link_contact_add_cost(saip_batch* b, double w_
 	if (w_impulse != w_impulse || w_peak != w_peak) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a weight is NaN", fn);
 	if ((st = need_ready(b, fn))) return st;
 	HIP_TRY(saip::launch_link_contact_add_cost(b->B, b->ld, b->link_contact.summary, b->samp_cost, w_impulse, w_peak, b->stream));
+	return SAIP_OK;
+}
+
+// ---- the pushed object (saip_link_object.h): a free rigid body of spheres, the optional second stage of link contact
+static saip_status need_link_object(const saip_batch* b, const char* fn) {
+	saip_status st = need_controller(b, fn);
+	if (st) return st;
+	if (!b->link_object.attached) return fail(SAIP_ERR_ORDER, "%s: no link object is attached (saip_batch_link_object_attach)", fn);
+	return SAIP_OK;
+}
+void saip::eng::link_object_free(saip_batch* b) {
+	auto& J = b->link_object;
+	for (void* p : {(void*)J.geom_dev, (void*)J.inertial, (void*)J.state, (void*)J.readout, (void*)J.summary})
+		if (p) (void)hipFree(p);
+	J = saip_batch::LinkObject();
+}
+// the inertial words [4] or [4][cols] = { m, Ix, Iy, Iz }: all > 0 and finite
+static bool link_object_check_inertial(const double* in, size_t cols, bool per_instance, char* msg, size_t len) {
+	static const char* const names[saip::LINK_OBJECT_INERTIAL_WORDS] = {"m", "Ix", "Iy", "Iz"};
+	for (int k = 0; k < saip::LINK_OBJECT_INERTIAL_WORDS; k++)
+		for (size_t i = 0; i < cols; i++) {
+			const double v = in[(size_t)k * cols + i];
+			if (v > 0 && std::isfinite(v)) continue;
+			if (per_instance) snprintf(msg, len, "inertial word %d (%s) of instance %zu = %g: > 0 and finite required", k, names[k], i, v);
+			else snprintf(msg, len, "inertial word %d (%s) = %g: > 0 and finite required", k, names[k], v);
+			return false;
+		}
+	return true;
+}
+// state [13] or [13][cols] -> out [13][cols] with unit quaternions; false: `msg` names the instance whose quaternion cannot be normalised
+static bool link_object_prepare_state(const double* state, size_t cols, bool per_instance, std::vector<double>& out, char* msg, size_t len) {
+	out.assign((size_t)saip::LINK_OBJECT_STATE_ROWS * cols, 0.0);
+	for (size_t i = 0; i < cols; i++) {
+		double x[saip::LINK_OBJECT_STATE_ROWS];
+		for (int r = 0; r < saip::LINK_OBJECT_STATE_ROWS; r++) x[r] = per_instance ? state[(size_t)r * cols + i] : state[r];
+		const double n = std::sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5] + x[6] * x[6]);
+		if (!(n > 0) || !std::isfinite(n)) {
+			if (per_instance) snprintf(msg, len, "instance %zu: the quaternion is zero or not finite", i);
+			else snprintf(msg, len, "the quaternion is zero or not finite");
+			return false;
+		}
+		for (int r = 3; r < 7; r++) x[r] /= n;
+		for (int r = 0; r < saip::LINK_OBJECT_STATE_ROWS; r++) out[(size_t)r * cols + i] = x[r];
+	}
+	return true;
+}
+extern "C" saip_status saip_batch_link_object_attach(saip_batch* b, int n_spheres, const double* centres, const double* radii, const double* material,
+													 const double* inertial, int per_instance) {
+	const char* fn = "saip_batch_link_object_attach";
+	saip_status st = need_controller(b, fn);
+	if (st) return st;
+	const int P = n_spheres;
+	if (P < 1 || P > saip::LINK_OBJECT_MAX_SPHERES) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: 1..%d spheres required (got %d)", fn, saip::LINK_OBJECT_MAX_SPHERES, P);
+	if (!centres || !radii) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null centres or radii", fn);
+	if (!material) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null material", fn);
+	if (!inertial) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null inertial words", fn);
+	per_instance = per_instance ? 1 : 0;
+	for (int s = 0; s < P; s++) {
+		for (int e = 0; e < 3; e++)
+			if (!std::isfinite(centres[3 * s + e])) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: sphere %d: the centre is not finite", fn, s);
+		if (!std::isfinite(radii[s])) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: sphere %d: the radius is not finite", fn, s);
+		if (radii[s] < 0) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: sphere %d: radius %g below 0", fn, s, radii[s]);
+	}
+	char msg[200];
+	if (!link_contact_check_materials(material, 1, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, msg);
+	if (!link_object_check_inertial(inertial, per_instance ? (size_t)b->B : 1, per_instance, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, msg);
+	// (the arguments first: a configuration-only batch, which can hold no link contact, still reports them)
+	if (!b->link_contact.attached) return fail(SAIP_ERR_ORDER, "%s: no link contact is attached (saip_batch_link_contact_attach first: the object is its second stage)", fn);
+	if (b->link_object.attached) return fail(SAIP_ERR_ORDER, "%s: a link object is already attached (saip_batch_link_object_detach first)", fn);
+	if ((st = need_ready(b, fn))) return st;
+	auto& J = b->link_object;
+	J = saip_batch::LinkObject();
+	saip::LinkObjectGeom& G = J.geom;
+	memset(&G, 0, sizeof(G));
+	G.P = P;
+	for (int s = 0; s < P; s++) {
+		for (int e = 0; e < 3; e++) G.r[s][e] = centres[3 * s + e];
+		G.radius[s] = radii[s];
+	}
+	for (int k = 0; k < saip::LINK_CONTACT_MATERIAL_WORDS; k++) G.mat[k] = material[k];
+	auto upload_geom = [&]() -> saip_status {
+		HIP_TRY(hipMalloc((void**)&J.geom_dev, sizeof(G)));
+		HIP_TRY(hipMemcpyAsync(J.geom_dev, &G, sizeof(G), hipMemcpyHostToDevice, b->stream));
+		HIP_TRY(hipStreamSynchronize(b->stream));
+		return SAIP_OK;
+	};
+	// the state at attach: the body frame on the world frame, at rest
+	std::vector<double> x0((size_t)saip::LINK_OBJECT_STATE_ROWS * b->B, 0.0);
+	for (int i = 0; i < b->B; i++) x0[(size_t)3 * b->B + i] = 1.0;
+	const size_t ld = b->ld;
+	if ((st = upload_geom()) || (st = alloc_zero(b, &J.inertial, (size_t)saip::LINK_OBJECT_INERTIAL_WORDS * (per_instance ? ld : 1))) ||
+		(st = alloc_zero(b, &J.state, (size_t)saip::LINK_OBJECT_STATE_ROWS * ld)) || (st = alloc_zero(b, &J.readout, (size_t)saip::LINK_OBJECT_READOUT_ROWS * ld)) ||
+		(st = alloc_zero(b, &J.summary, (size_t)saip::LINK_OBJECT_SUMMARY_ROWS * ld)) ||
+		(st = upload_table(b, J.inertial, inertial, saip::LINK_OBJECT_INERTIAL_WORDS, per_instance, "inertial", fn)) ||
+		(st = upload_table(b, J.state, x0.data(), saip::LINK_OBJECT_STATE_ROWS, 1, "state", fn))) {
+		link_object_free(b);
+		return st;
+	}
+	J.attached = true;
+	J.per_instance = per_instance;
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_link_object_detach(saip_batch* b) {
+	const char* fn = "saip_batch_link_object_detach";
+	saip_status st = need_link_object(b, fn);
+	if (st || (st = need_ready(b, fn))) return st;
+	HIP_TRY(hipStreamSynchronize(b->stream));  // a substep may still be in flight
+	link_object_free(b);
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_link_object_info(saip_batch* b, int* n_spheres, int* per_instance) {
+	saip_status st = need_link_object(b, "saip_batch_link_object_info");
+	if (st) return st;
+	if (n_spheres) *n_spheres = b->link_object.geom.P;
+	if (per_instance) *per_instance = b->link_object.per_instance;
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_link_object_set_state_host(saip_batch* b, const double* state, int per_instance) {
+	const char* fn = "saip_batch_link_object_set_state_host";
+	saip_status st = need_link_object(b, fn);
+	if (st) return st;
+	if (!state) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null state", fn);
+	char msg[200];
+	std::vector<double> x;
+	if (!link_object_prepare_state(state, per_instance ? (size_t)b->B : 1, per_instance != 0, x, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, msg);
+	if ((st = need_ready(b, fn))) return st;
+	if (!per_instance) {  // one column for all
+		std::vector<double> all((size_t)saip::LINK_OBJECT_STATE_ROWS * b->B);
+		for (int r = 0; r < saip::LINK_OBJECT_STATE_ROWS; r++)
+			for (int i = 0; i < b->B; i++) all[(size_t)r * b->B + i] = x[r];
+		x.swap(all);
+	}
+	return upload_table(b, b->link_object.state, x.data(), saip::LINK_OBJECT_STATE_ROWS, 1, "state", fn);
+}
+extern "C" saip_status saip_batch_link_object_set_inertial_host(saip_batch* b, const double* inertial) {
+	const char* fn = "saip_batch_link_object_set_inertial_host";
+	saip_status st = need_link_object(b, fn);
+	if (st) return st;
+	const auto& J = b->link_object;
+	if (!inertial) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null inertial words", fn);
+	char msg[200];
+	if (!link_object_check_inertial(inertial, J.per_instance ? (size_t)b->B : 1, J.per_instance, msg, sizeof(msg))) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: %s", fn, msg);
+	if ((st = need_ready(b, fn))) return st;
+	return upload_table(b, J.inertial, inertial, saip::LINK_OBJECT_INERTIAL_WORDS, J.per_instance, "inertial", fn);
+}
+extern "C" double* saip_batch_link_object_state_device(saip_batch* b) { return b ? b->link_object.state : nullptr; }
+extern "C" double* saip_batch_link_object_readout_device(saip_batch* b) { return b ? b->link_object.readout : nullptr; }
+extern "C" double* saip_batch_link_object_summary_device(saip_batch* b) { return b ? b->link_object.summary : nullptr; }
+extern "C" saip_status saip_batch_link_object_state_host(saip_batch* b, double* out) {
+	const char* fn = "saip_batch_link_object_state_host";
+	const saip_status st = need_link_object(b, fn);
+	return rows_to_host(b, st, out, st ? nullptr : b->link_object.state, saip::LINK_OBJECT_STATE_ROWS, fn);
+}
+extern "C" saip_status saip_batch_link_object_readout_host(saip_batch* b, double* out) {
+	const char* fn = "saip_batch_link_object_readout_host";
+	const saip_status st = need_link_object(b, fn);
+	return rows_to_host(b, st, out, st ? nullptr : b->link_object.readout, saip::LINK_OBJECT_READOUT_ROWS, fn);
+}
+extern "C" saip_status saip_batch_link_object_summary_host(saip_batch* b, double* out) {
+	const char* fn = "saip_batch_link_object_summary_host";
+	const saip_status st = need_link_object(b, fn);
+	return rows_to_host(b, st, out, st ? nullptr : b->link_object.summary, saip::LINK_OBJECT_SUMMARY_ROWS, fn);
+}
+static_assert(saip::LINK_OBJECT_SUMMARY_ROWS == saip::LINK_CONTACT_SUMMARY_ROWS, "the reset kernel of link contact zeroes the object's summaries too");
+extern "C" saip_status saip_batch_link_object_summary_reset(saip_batch* b) {
+	const char* fn = "saip_batch_link_object_summary_reset";
+	saip_status st = need_link_object(b, fn);
+	if (st || (st = need_ready(b, fn))) return st;
+	HIP_TRY(saip::launch_link_contact_summary_reset(b->B, b->ld, b->link_object.summary, b->stream));
+	return SAIP_OK;
+}
+extern "C" saip_status saip_batch_link_object_add_cost(saip_batch* b, const double* target_p, double w_pos, const double* target_quat, double w_ori) {
+	const char* fn = "saip_batch_link_object_add_cost";
+	saip_status st = need_link_object(b, fn);
+	if (st) return st;
+	if (b->n_samp == 0) return fail(SAIP_ERR_ORDER, "%s: no sampler is attached (saip_batch_sampler_attach): there is no cost to add to", fn);
+	if (!target_p) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: null target position", fn);
+	for (int e = 0; e < 3; e++)
+		if (!std::isfinite(target_p[e])) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the target position is not finite", fn);
+	if (w_pos != w_pos || w_ori != w_ori) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: a weight is NaN", fn);
+	double tq[4];
+	if (target_quat) {
+		const double n = std::sqrt(target_quat[0] * target_quat[0] + target_quat[1] * target_quat[1] + target_quat[2] * target_quat[2] + target_quat[3] * target_quat[3]);
+		if (!(n > 0) || !std::isfinite(n)) return fail(SAIP_ERR_INVALID_ARGUMENT, "%s: the target quaternion is zero or not finite", fn);
+		for (int i = 0; i < 4; i++) tq[i] = target_quat[i] / n;
+	}
+	if ((st = need_ready(b, fn))) return st;
+	HIP_TRY(saip::launch_link_object_add_cost(b->B, b->ld, b->link_object.state, b->samp_cost, target_p, w_pos, target_quat ? tq : nullptr, w_ori, b->stream));
 	return SAIP_OK;
 }

@@ -61,7 +61,7 @@ static saip_status enqueue_integrate(saip_batch* b, const saip::SimPlan& plan, d
 		for (int s = 0; s < substeps && e == hipSuccess; s++) {
 			saip_status st = b->plant.attached ? plant_launch(b, dt, s) : SAIP_OK;  // s == 0: the actuation chain advances its delay line
 			if (st) return st;
-			if (b->link_contact.attached && (st = link_contact_launch(b, saip::LINK_CONTACT_APPLY, dt))) return st;
+			if (b->link_contact.attached && (st = link_contact_launch(b, saip::LINK_CONTACT_APPLY, dt, S.gravity))) return st;
 			if (b->n_patch > 0) st = patch_launch(b, saip::CONTACT_APPLY, dt);
 			else if (b->contact.attached) st = contact_launch(b, saip::CONTACT_APPLY, dt);
 			if (st) return st;

@@ -83,6 +83,8 @@ static void snapshot_directory(const saip_batch* b, std::vector<SnapSegHost>& D)
 		soa("guard.fires", P.fires, P.G, 4);
 		soa("guard.latch", P.latch, saip::GUARD_LATCH_ROWS, 8);
 	}
+	// the pushed object of link contact: pose and twist of every instance's body; absent while detached
+	if (b->link_object.attached) soa("link_object.state", b->link_object.state, saip::LINK_OBJECT_STATE_ROWS, 8);
 }
 static_assert(sizeof(saip::ShState) % 4 == 0, "ShState is moved as 4- or 8-byte words");
 static uint64_t snapshot_fingerprint(const saip_batch* b, const std::vector<SnapSegHost>& D) {

@@ -137,6 +137,27 @@ struct LinkContactView {
 	const double* mat;       // [O][4]
 };
 
+// Sorted sphere i (centre c, velocity v) against the obstacles in ascending order: F_s accumulates in Fs (from what the caller put
+// there), the lane's partial p takes minimum, sum f_n and largest |f|; returns the number of active items
+SAIP_LC_HD inline int lc_sphere_items(const LinkContactView& W, int i, const double* c, const double* v, LinkContactPartial& p, double* Fs) {
+#pragma clang fp contract(off)
+	int act = 0;
+	for (int o = 0; o < W.O; o++) {
+		LinkContactItem it;
+		lc_item(W.obst + (long long)o * LINK_CONTACT_OBSTACLE_WORDS * W.stride + W.col, W.stride, W.mat + LINK_CONTACT_MATERIAL_WORDS * o, c, v, W.radius[i], &it);
+		const int k = W.slot[i] * W.O + o;
+		if (it.d < p.dmin || (it.d == p.dmin && k < p.k)) {  // (a lane does not meet its items in ascending k: the tie is explicit)
+			p.dmin = it.d;
+			p.k = k;
+		}
+		if (!it.active) continue;
+		act++;
+		for (int e = 0; e < 3; e++) Fs[e] = Fs[e] + it.f[e];
+		p.fn_sum = p.fn_sum + it.fn;
+		p.fmax = lc_max(p.fmax, sqrt(cl_dot(it.f, it.f)));
+	}
+	return act;
+}
 // Lane `lane` of the instance in group g: C, V the centres and velocities (cl_centre_index by sorted position), F and A receive F_s
 // (cl_centre_index) and the flag "has an active item" (lc_flag_index) of the lane's spheres.
 SAIP_LC_HD inline void lc_lane(const LinkContactView& W, const double* C, const double* V, double* F, int* A, int g, int lane, LinkContactPartial* out) {
@@ -148,21 +169,7 @@ SAIP_LC_HD inline void lc_lane(const LinkContactView& W, const double* C, const 
 		for (int e = 0; e < 3; e++)
 			if (!cl_finite(c[e])) p.bad = 1;  // explicit: the comparisons below drop NaNs
 		double Fs[3] = {0.0, 0.0, 0.0};
-		int act = 0;
-		for (int o = 0; o < W.O; o++) {
-			LinkContactItem it;
-			lc_item(W.obst + (long long)o * LINK_CONTACT_OBSTACLE_WORDS * W.stride + W.col, W.stride, W.mat + LINK_CONTACT_MATERIAL_WORDS * o, c, v, W.radius[i], &it);
-			const int k = W.slot[i] * W.O + o;
-			if (it.d < p.dmin || (it.d == p.dmin && k < p.k)) {  // (a lane does not meet its items in ascending k: the tie is explicit)
-				p.dmin = it.d;
-				p.k = k;
-			}
-			if (!it.active) continue;
-			act++;
-			for (int e = 0; e < 3; e++) Fs[e] = Fs[e] + it.f[e];
-			p.fn_sum = p.fn_sum + it.fn;
-			p.fmax = lc_max(p.fmax, sqrt(cl_dot(it.f, it.f)));
-		}
+		const int act = lc_sphere_items(W, i, c, v, p, Fs);
 		for (int e = 0; e < 3; e++) {
 			F[cl_centre_index(i, e, g)] = Fs[e];
 			p.f[e] = p.f[e] + Fs[e];

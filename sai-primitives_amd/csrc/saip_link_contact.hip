@@ -18,6 +18,7 @@
 
 #include "saip_fk.h"
 #include "saip_link_contact.h"
+#include "saip_link_object.h"
 
 namespace saip {
 
@@ -113,16 +114,12 @@ __device__ __forceinline__ void lc_walk(const LinkContactParams& P, LinkContactS
 	}
 }
 
-}  // namespace
-
-template <bool TREE>
-__global__ void __launch_bounds__(64) saip_link_contact_apply(const LinkContactParams P) {
-	__shared__ LinkContactShared sh;
-	const int t = threadIdx.x, lane = t & (LC_L - 1), g = t >> 3;
-	const int b0 = blockIdx.x * LC_G, b = b0 + g;
-	const bool live = b < P.B;  // (a lane of a group past the batch still has to reach the barriers)
-	const int ld = P.ld, n = P.n;
-	// ---- staging: independent loads, eight consecutive doubles of a row per instance array (thread t: column t & 7, rows t >> 3, + 8, ...)
+// ---- what saip_link_contact_apply and saip_link_object_apply share besides the walk: each written once
+// staging: independent loads, eight consecutive doubles of a row per instance array (thread t: column t & 7, rows t >> 3, + 8, ...); and
+// the commanded torques of this lane's joints lane, lane + 8, ... (APPLY: requested now, used in phase 3)
+__device__ __forceinline__ void lc_stage(const LinkContactParams& P, LinkContactShared& sh, const int t, const int lane, const int g, const int b0, const bool live,
+										 double* u0) {
+	const int ld = P.ld, n = P.n, O = P.O, b = b0 + g;
 	for (int w = t; w < LC_GEOM_DOUBLES; w += 64) sh.geom.words[w] = ((const double*)P.geom)[w];
 	{
 		const bool in = b0 + lane < P.B;
@@ -131,7 +128,6 @@ __global__ void __launch_bounds__(64) saip_link_contact_apply(const LinkContactP
 			sh.DQ[r * LC_G + lane] = in ? P.dq[(size_t)r * ld + b0 + lane] : 0.0;
 		}
 	}
-	const int S = P.S, O = P.O;
 	if (P.per_instance) {
 		const bool in = b0 + lane < P.B;
 		for (int r = g; r < O * LINK_CONTACT_OBSTACLE_WORDS; r += LC_G) sh.OB[r * LC_G + lane] = in ? P.obst[(size_t)r * ld + b0 + lane] : 0.0;
@@ -139,32 +135,28 @@ __global__ void __launch_bounds__(64) saip_link_contact_apply(const LinkContactP
 		for (int w = t; w < O * LINK_CONTACT_OBSTACLE_WORDS; w += 64) sh.OB[w] = P.obst[w];
 	}
 	if (t < O * LINK_CONTACT_MATERIAL_WORDS) sh.MAT[t] = P.mat[t];
-	// APPLY: the commanded torques of this lane's joints lane, lane + 8, ... (requested now, used in phase 3)
-	double u0[SAIP_MAXN / LC_L];
 #pragma unroll
 	for (int r = 0; r < SAIP_MAXN / LC_L; r++) {
 		const int j = lane + LC_L * r;
 		u0[r] = (P.mode == LINK_CONTACT_APPLY && live && j < n) ? lc_u0(P.tau_cmd[(size_t)j * ld + b]) : 0.0;
 	}
-	__syncthreads();
-	const LinkContactGeom& G = sh.geom.G;
-	// ---- phase 1: centres, velocities, joint axes and origins
-	if (live) lc_walk<TREE>(P, sh, *P.model, lane, g, b);
-	__syncthreads();
-	// ---- phase 2: the items of this lane, then the fold over the group: cross-lane moves, no LDS traffic and no atomics
-	LinkContactPartial v = {{0.0, 0.0, 0.0}, INFINITY, 0.0, 0.0, -1, 0, 0};
-	if (live) {
-		LinkContactView W;
-		W.S = S;
-		W.O = O;
-		W.slot = G.slot;
-		W.radius = G.radius;
-		W.obst = sh.OB;
-		W.stride = P.per_instance ? LC_G : 1;
-		W.col = P.per_instance ? g : 0;
-		W.mat = sh.MAT;
-		lc_lane(W, sh.C, sh.V, sh.F, sh.A, g, lane, &v);
-	}
+}
+// what the lanes of group g read in phase 2: the staged tables
+__device__ __forceinline__ LinkContactView lc_view(const LinkContactParams& P, const LinkContactShared& sh, const int g) {
+	LinkContactView W;
+	W.S = P.S;
+	W.O = P.O;
+	W.slot = sh.geom.G.slot;
+	W.radius = sh.geom.G.radius;
+	W.obst = sh.OB;
+	W.stride = P.per_instance ? LC_G : 1;
+	W.col = P.per_instance ? g : 0;
+	W.mat = sh.MAT;
+	return W;
+}
+// the fold over the group: cross-lane moves, no LDS traffic and no atomics (lanes off.. of the group fold with themselves: their values
+// are not used again)
+__device__ __forceinline__ void lc_fold_group(LinkContactPartial& v) {
 	for (int off = LC_L / 2; off >= 1; off >>= 1) {
 		LinkContactPartial w;
 		for (int e = 0; e < 3; e++) w.f[e] = __shfl_down(v.f[e], off, LC_L);
@@ -174,22 +166,21 @@ __global__ void __launch_bounds__(64) saip_link_contact_apply(const LinkContactP
 		w.k = __shfl_down(v.k, off, LC_L);
 		w.active = __shfl_down(v.active, off, LC_L);
 		w.bad = __shfl_down(v.bad, off, LC_L);
-		lc_fold(&v, w);  // (lanes off.. of the group fold with themselves: their values are not used again)
+		lc_fold(&v, w);
 	}
-	const int run = __shfl((!v.bad && v.active > 0) ? 1 : 0, 0, LC_L);  // lane 0's verdict for the whole group: does the torque loop run?
-	__syncthreads();
-	if (!live) return;
+}
+// F_s of this lane's spheres to the kept array
+__device__ __forceinline__ void lc_keep_forces(const LinkContactParams& P, const LinkContactShared& sh, const int lane, const int g, const int b) {
+	const int S = P.S;
 	if (P.keep)
 		for (int i = lane; i < S; i += LC_L)
-			for (int e = 0; e < 3; e++) P.keep[(size_t)(3 * (2 * S + G.slot[i]) + e) * ld + b] = sh.F[cl_centre_index(i, e, g)];
-	if (lane == 0) {
-		double ro[LINK_CONTACT_READOUT_ROWS];
-		lc_readout(v, ro);
-		for (int r = 0; r < LINK_CONTACT_READOUT_ROWS; r++) P.readout[(size_t)r * ld + b] = ro[r];
-		if (P.mode == LINK_CONTACT_APPLY) lc_summary_advance(P.summary + b, ld, P.dt, ro);
-	}
-	if (P.mode != LINK_CONTACT_APPLY) return;
-	// ---- phase 3: the torques of joints lane, lane + 8, ...
+			for (int e = 0; e < 3; e++) P.keep[(size_t)(3 * (2 * S + sh.geom.G.slot[i]) + e) * P.ld + b] = sh.F[cl_centre_index(i, e, g)];
+}
+// phase 3: the torques of joints lane, lane + 8, ...; run: the group's verdict "valid and something active"
+__device__ __forceinline__ void lc_torques(const LinkContactParams& P, const LinkContactShared& sh, const int lane, const int g, const int b, const int run,
+										   const double* u0) {
+	const LinkContactGeom& G = sh.geom.G;
+	const int n = P.n, S = P.S;
 #pragma unroll
 	for (int r = 0; r < SAIP_MAXN / LC_L; r++) {
 		const int j = lane + LC_L * r;
@@ -204,8 +195,162 @@ __global__ void __launch_bounds__(64) saip_link_contact_apply(const LinkContactP
 			}
 			tau = lc_tau(tau, x);
 		}
-		P.tau_sim[(size_t)j * ld + b] = tau;
+		P.tau_sim[(size_t)j * P.ld + b] = tau;
 	}
+}
+
+}  // namespace
+
+template <bool TREE>
+__global__ void __launch_bounds__(64) saip_link_contact_apply(const LinkContactParams P) {
+	__shared__ LinkContactShared sh;
+	const int t = threadIdx.x, lane = t & (LC_L - 1), g = t >> 3;
+	const int b0 = blockIdx.x * LC_G, b = b0 + g;
+	const bool live = b < P.B;  // (a lane of a group past the batch still has to reach the barriers)
+	const int ld = P.ld;
+	double u0[SAIP_MAXN / LC_L];
+	lc_stage(P, sh, t, lane, g, b0, live, u0);
+	__syncthreads();
+	// ---- phase 1: centres, velocities, joint axes and origins
+	if (live) lc_walk<TREE>(P, sh, *P.model, lane, g, b);
+	__syncthreads();
+	// ---- phase 2: the items of this lane, then the fold over the group
+	LinkContactPartial v = {{0.0, 0.0, 0.0}, INFINITY, 0.0, 0.0, -1, 0, 0};
+	if (live) lc_lane(lc_view(P, sh, g), sh.C, sh.V, sh.F, sh.A, g, lane, &v);
+	lc_fold_group(v);
+	const int run = __shfl((!v.bad && v.active > 0) ? 1 : 0, 0, LC_L);  // lane 0's verdict for the whole group: does the torque loop run?
+	__syncthreads();
+	if (!live) return;
+	lc_keep_forces(P, sh, lane, g, b);
+	if (lane == 0) {
+		double ro[LINK_CONTACT_READOUT_ROWS];
+		lc_readout(v, ro);
+		for (int r = 0; r < LINK_CONTACT_READOUT_ROWS; r++) P.readout[(size_t)r * ld + b] = ro[r];
+		if (P.mode == LINK_CONTACT_APPLY) lc_summary_advance(P.summary + b, ld, P.dt, ro);
+	}
+	if (P.mode != LINK_CONTACT_APPLY) return;
+	lc_torques(P, sh, lane, g, b, run, u0);
+}
+
+// ---- the pushed object (saip_link_object.h): the launch that replaces the one above while an object is attached.  The same walk, lanes,
+// blocks and staging; on top of them the object's 13 state words, its inertial words and its shape are staged with the other independent
+// loads, lane p < P forms c_p and v_p of object sphere p in phase 1 (they live in the LDS beside C and V), phase 2 is lo_lane (the robot
+// spheres of the lane against the obstacles, then against the object spheres) and, on lane p < P, lo_world (object sphere p against the
+// obstacles); both partials fold by cross-lane moves and lane 0 integrates the body and writes its new state, rows of [ld].  No atomics,
+// and nothing inside the item loops reads global memory.
+namespace {
+enum { LO_GEOM_DOUBLES = sizeof(LinkObjectGeom) / sizeof(double) };
+static_assert(sizeof(LinkObjectGeom) % sizeof(double) == 0, "the shape is staged by doubles");
+// 46 096 bytes of link contact + 2 x 1.5 KB object sphere vectors, 832 B state, 256 B inertial words, 296 B shape: 50 552 bytes
+struct LinkObjectShared {
+	LinkContactShared lc;
+	double OC[LINK_OBJECT_VEC_WORDS], OV[LINK_OBJECT_VEC_WORDS];  // per object sphere: centre, velocity
+	double X[LINK_OBJECT_STATE_ROWS * LC_G];                      // [13][8]
+	double IN[LINK_OBJECT_INERTIAL_WORDS * LC_G];                 // [4][8]
+	union {
+		LinkObjectGeom G;
+		double words[LO_GEOM_DOUBLES];
+	} og;
+};
+}  // namespace
+
+template <bool TREE>
+__global__ void __launch_bounds__(64) saip_link_object_apply(const LinkObjectParams Q) {
+	__shared__ LinkObjectShared so;
+	LinkContactShared& sh = so.lc;
+	const LinkContactParams& P = Q.lc;
+	const int t = threadIdx.x, lane = t & (LC_L - 1), g = t >> 3;
+	const int b0 = blockIdx.x * LC_G, b = b0 + g;
+	const bool live = b < P.B;
+	const int ld = P.ld;
+	// ---- staging: link contact's, and the object's words
+	double u0[SAIP_MAXN / LC_L];
+	lc_stage(P, sh, t, lane, g, b0, live, u0);
+	if (t < LO_GEOM_DOUBLES) so.og.words[t] = ((const double*)Q.geom)[t];
+	{
+		const bool in = b0 + lane < P.B;
+		for (int r = g; r < LINK_OBJECT_STATE_ROWS; r += LC_G) so.X[r * LC_G + lane] = in ? Q.state[(size_t)r * ld + b0 + lane] : 0.0;
+		if (g < LINK_OBJECT_INERTIAL_WORDS) so.IN[g * LC_G + lane] = Q.inertial_per_instance ? (in ? Q.inertial[(size_t)g * ld + b0 + lane] : 1.0) : Q.inertial[g];
+	}
+	__syncthreads();
+	const LinkObjectGeom& OG = so.og.G;
+	// ---- phase 1: the robot's walk, and the object spheres
+	double x[LINK_OBJECT_STATE_ROWS];
+	for (int r = 0; r < LINK_OBJECT_STATE_ROWS; r++) x[r] = so.X[r * LC_G + g];
+	if (live) {
+		lc_walk<TREE>(P, sh, *P.model, lane, g, b);
+		if (lane < OG.P) {
+			double R[9], c[3], v[3];
+			lo_rotation(x + 3, R);
+			lo_sphere(x, R, OG.r[lane], c, v);
+			for (int e = 0; e < 3; e++) {
+				so.OC[lo_index(lane, e, g)] = c[e];
+				so.OV[lo_index(lane, e, g)] = v[e];
+			}
+		}
+	}
+	__syncthreads();
+	// ---- phase 2: the items of this lane, then the two folds over the group
+	LinkContactPartial v = {{0.0, 0.0, 0.0}, INFINITY, 0.0, 0.0, -1, 0, 0};
+	LinkObjectPartial q;
+	lo_partial_clear(&q);
+	if (live) {
+		const LinkContactView W = lc_view(P, sh, g);
+		lo_lane(W, OG, sh.C, sh.V, so.OC, so.OV, x, sh.F, sh.A, g, lane, &v, &q);
+		if (lane < OG.P) lo_world(W, OG, so.OC, so.OV, x, g, lane, &q);
+	}
+	lc_fold_group(v);
+	for (int off = LC_L / 2; off >= 1; off >>= 1) {
+		LinkObjectPartial y;
+		for (int e = 0; e < 3; e++) {
+			y.rf[e] = __shfl_down(q.rf[e], off, LC_L);
+			y.rm[e] = __shfl_down(q.rm[e], off, LC_L);
+			y.wf[e] = __shfl_down(q.wf[e], off, LC_L);
+			y.wm[e] = __shfl_down(q.wm[e], off, LC_L);
+		}
+		y.dmin = __shfl_down(q.dmin, off, LC_L);
+		y.fn_sum = __shfl_down(q.fn_sum, off, LC_L);
+		y.wpen = __shfl_down(q.wpen, off, LC_L);
+		y.k = __shfl_down(q.k, off, LC_L);
+		y.active = __shfl_down(q.active, off, LC_L);
+		lo_fold(&q, y);
+	}
+	const bool bad = v.bad || !lo_state_finite(x);  // (lane 0's word counts)
+	const int run = __shfl((!bad && v.active + q.active > 0) ? 1 : 0, 0, LC_L);
+	__syncthreads();
+	if (!live) return;
+	lc_keep_forces(P, sh, lane, g, b);
+	if (lane == 0) {
+		double ro[LINK_CONTACT_READOUT_ROWS], rq[LINK_OBJECT_READOUT_ROWS];
+		lc_readout(v, ro);
+		for (int r = 0; r < LINK_CONTACT_READOUT_ROWS; r++) P.readout[(size_t)r * ld + b] = ro[r];
+		lo_readout(q, bad, rq);
+		for (int r = 0; r < LINK_OBJECT_READOUT_ROWS; r++) Q.readout[(size_t)r * ld + b] = rq[r];
+		if (P.mode == LINK_CONTACT_APPLY) {
+			lc_summary_advance(P.summary + b, ld, P.dt, ro);
+			lo_summary_advance(Q.summary + b, ld, P.dt, q, bad);
+			if (!bad) {
+				double in[LINK_OBJECT_INERTIAL_WORDS], xn[LINK_OBJECT_STATE_ROWS];
+				for (int r = 0; r < LINK_OBJECT_INERTIAL_WORDS; r++) in[r] = so.IN[r * LC_G + g];
+				lo_integrate(x, in, Q.gravity, P.dt, q, xn);
+				for (int r = 0; r < LINK_OBJECT_STATE_ROWS; r++) Q.state[(size_t)r * ld + b] = xn[r];
+			}
+		}
+	}
+	if (P.mode != LINK_CONTACT_APPLY) return;
+	lc_torques(P, sh, lane, g, b, run, u0);
+}
+
+// cost[i] += w_pos |p - target|^2 + w_ori (1 - (q . q_t)^2) on the sampler's cost, one lane per instance
+__global__ void __launch_bounds__(64) saip_link_object_add_cost(const int B, const int ld, const double* state, double* cost, const double tx, const double ty,
+																 const double tz, const double w_pos, const int has_quat, const double q0, const double q1, const double q2,
+																 const double q3, const double w_ori) {
+	const int b = blockIdx.x * blockDim.x + threadIdx.x;
+	if (b >= B) return;
+	double x[LINK_OBJECT_STATE_ROWS];
+	for (int r = 0; r < LINK_OBJECT_STATE_ROWS; r++) x[r] = state[(size_t)r * ld + b];
+	const double tp[3] = {tx, ty, tz}, tq[4] = {q0, q1, q2, q3};
+	cost[b] = lo_add_cost(cost[b], x, tp, w_pos, tq, has_quat != 0, w_ori);
 }
 
 __global__ void __launch_bounds__(64) saip_link_contact_add_cost(const int B, const int ld, const double* summary, double* cost, const double w_impulse,
@@ -226,6 +371,19 @@ hipError_t launch_link_contact_apply(const LinkContactParams& P, bool tree, hipS
 	const dim3 grid((P.B + LC_G - 1) / LC_G);
 	if (tree) hipLaunchKernelGGL(saip_link_contact_apply<true>, grid, dim3(64), 0, stream, P);
 	else hipLaunchKernelGGL(saip_link_contact_apply<false>, grid, dim3(64), 0, stream, P);
+	return hipGetLastError();
+}
+
+hipError_t launch_link_object_apply(const LinkObjectParams& Q, bool tree, hipStream_t stream) {
+	const dim3 grid((Q.lc.B + LC_G - 1) / LC_G);
+	if (tree) hipLaunchKernelGGL(saip_link_object_apply<true>, grid, dim3(64), 0, stream, Q);
+	else hipLaunchKernelGGL(saip_link_object_apply<false>, grid, dim3(64), 0, stream, Q);
+	return hipGetLastError();
+}
+
+hipError_t launch_link_object_add_cost(int B, int ld, const double* state, double* cost, const double* tp, double w_pos, const double* tq, double w_ori, hipStream_t stream) {
+	hipLaunchKernelGGL(saip_link_object_add_cost, dim3((B + 63) / 64), dim3(64), 0, stream, B, ld, state, cost, tp[0], tp[1], tp[2], w_pos, tq ? 1 : 0, tq ? tq[0] : 0.0,
+					   tq ? tq[1] : 0.0, tq ? tq[2] : 0.0, tq ? tq[3] : 0.0, w_ori);
 	return hipGetLastError();
 }
 

@@ -30,6 +30,9 @@
    period without and with link contact of S link spheres against O obstacles (capsules, every fourth a floor; soft materials with
    friction), and prints the event-timed mean of 200 back-to-back EVALUATE launches alone and of 200 one-substep integrate calls both
    ways: their difference is the APPLY launch.
+   --link-contact --link-object [--lo-spheres P] times, interleaved in the same run, the period with that link contact alone and with the
+   pushed object of P corner spheres on top (the launch with the object replaces the link-contact launch), the one-substep integrate
+   call and the EVALUATE launch alone both ways.
    --plant [--plant-wrenches W] [--substeps S] times, interleaved in the same run, the closed-loop period without and with a per-instance
    plant model (tight actuators, friction, stops at the model's limits and W payload-like wrenches, 0..4) and the event-timed mean of 200
    one-substep integrate calls both ways: the difference is the plant launch alone.
@@ -118,6 +121,8 @@ ap.add_argument("--link-contact", action="store_true")
 ap.add_argument("--lc-spheres", type=int, default=8)
 ap.add_argument("--lc-obstacles", type=int, default=4)
 ap.add_argument("--lc-per-instance", action="store_true")
+ap.add_argument("--link-object", action="store_true", help="with --link-contact: the pushed object on top; the leg with link contact alone runs interleaved")
+ap.add_argument("--lo-spheres", type=int, default=8)
 ap.add_argument("--guards", action="store_true")
 ap.add_argument("--env-schedule", choices=("obstacles", "planes", "both"), default=None)
 ap.add_argument("--env-mode", choices=("hold", "linear"), default="linear")
@@ -472,6 +477,38 @@ for B in [int(x) for x in os.environ.get("BATCHES", "4096,65536").split(",")]:
         def evaluate_us():
             return timed_us(lambda: ctrl._call("saip_batch_link_contact_evaluate"), 200, first=ctrl.evaluateLinkContact)
 
+        if args.link_object:
+            # the pushed object on top of link contact: a box of corner spheres in front of the end-effector, resting state; the leg with link
+            # contact alone (the launch the object's launch replaces) runs before and after it in the same process.  Every instance of this
+            # bench starts at the same posture, so instance 0's end-effector position places the object for all of them
+            P = args.lo_spheres
+            corners = [(np.array([sx, sy, sz]) * 0.04, 0.03) for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)][:P]
+            ctrl.attachLinkContact(spheres, obst, mats, per_instance=args.lc_per_instance)
+            place = np.r_[robot.position("end-effector", (0.0, 0.0, 0.03))[0] + [0.08, 0.0, 0.0], 1.0, np.zeros(9)]
+            for _ in range(args.repeats):
+                snap = ctrl.saveState()
+                plain, plain_i, plain_e = period_us(), integrate_us(), evaluate_us()
+                ctrl.restoreState(snap)
+                ctrl.attachLinkObject(corners, [2.0e3, 40.0, 0.3, 1e-3], [0.5, 1e-3, 1e-3, 1e-3], state=place)
+                both = ctrl.saveState()                                      # (the directory has the object's segment now)
+                period_us()
+                ctrl.restoreState(both)
+                ctrl.resetObjectSummary()
+                with_o, with_i, alone = period_us(), integrate_us(), evaluate_us()
+                touched = int((ctrl.objectSummary()["substeps_in_contact"] > 0).sum())
+                ctrl.detachLinkObject()
+                ctrl.restoreState(snap)
+                again = period_us()
+                ctrl.restoreState(snap)
+                both.close()
+                snap.close()
+                n_sub = args.substeps
+                print(f"{os.path.basename(os.environ.get('SAIP_LIB', 'libsaip.so'))} B={B} otg {'off' if args.no_otg else 'on'} substeps {n_sub}, link contact of {S} spheres, {O} obstacles: "
+                      f"period {plain:.1f} us, integrate {plain_i:.2f} us, EVALUATE launch {plain_e:.2f} us; with the object of {P} spheres: period {with_o:.1f} us "
+                      f"(+{(with_o - plain) / n_sub:.2f} us per substep), integrate {with_i:.2f} us, launch alone {alone:.2f} us; without it again {again:.1f} us "
+                      f"({touched} of {B} instances pushed)")
+            ctrl.detachLinkContact()
+            continue
         for _ in range(args.repeats):
             snap = ctrl.saveState()
             plain, plain_i = period_us(), integrate_us()
